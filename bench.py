@@ -14,16 +14,23 @@ row pass): synthetic N = M = 100 000 3-D points, fp32 pair arithmetic, w = 0.  W
 
 THE TIMED WINDOW IS PINNED: the E-step's cost depends on sigma2 (the sweeps skip blocks whose every pair is an exact
 fp32 zero), so after the W warm-up steps the EM state is put back to the start of the registration and the K timed
-steps are EM iterations 0 .. K-1 of that registration - `--warmup` cannot move the headline.  The line also carries
-`dense_it_s` (iteration 0 alone: every pair evaluated), `late_it_s` (iterations 45..49) and `trajectory_it_s` (= value).
+steps are EM iterations 0 .. K-1 of that registration - `--warmup` cannot move the headline.
 
-Rank 0 prints ONE JSON line.  With the defaults (1 GPU, C1) it also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`),
+`config` and `result` (the EM state after the window).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float64) before the line is printed: the transformation, sigma2, q, the E-step's moment block and its column sums
+pt1 (C1 / C2), W (C3), the device state (C4), the combined transformation (BCPD); the inputs are seeded, so two builds can be
+compared output for output.
+
+`--full` measures everything beside the headline as well.  The line then also carries `dense_it_s` (iteration 0 alone: every
+pair evaluated), `late_it_s` (iterations 45..49), `trajectory_it_s` (= value), and with the defaults (1 GPU, C1)
   roofline        binding roofline of the dominant kernel (row pass): fp32 VALU, from the pairs the kernel actually
                   evaluated (device counters) x its flop per pair, HIP-event timed on the plan's stream
   parity          GPU vs the CPU oracle on the cpu_baseline sample (same inputs, same iterations)
   cpu_baseline    oracle/cpd_estep_c.c timed on the host cores at three sizes, fitted t = a M N
   other_workloads C2 (affine 200k), C3 (non-rigid 50k), C4 (FilterReg 500k) measured the same way, each with its roofline
                   and its own GPU-vs-oracle parity block (reduced samples of the same generators)
+(`--no-cpu-baseline`, `--no-other-workloads`, `--no-dense-compare` leave parts of it out; `--pairs-log` needs `--full`.)
 """
 import argparse
 import json
@@ -244,6 +251,22 @@ def _pmc_traffic(workload, key):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64; an array past its share of the 64 MB budget is replaced by a
+    fixed, seeded sample of its rows (none of the workloads' outputs comes near it)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in sorted(arrays.items()):
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            rows = max(1, share // max(a[0].nbytes, 1))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _base(metric, value, elapsed, steps, warmup, desc, dtype, world=1):
     return {"metric": metric, "value": value, "unit": "EM iterations/s", "n_gpus": world, "steps": steps,
             "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True,
@@ -254,7 +277,33 @@ def _base(metric, value, elapsed, steps, warmup, desc, dtype, world=1):
 # ----------------------------------------------------------------------------------------------------------------
 # C1 / C2: rigid / affine CPD
 # ----------------------------------------------------------------------------------------------------------------
-def bench_cpd(workload, steps, warmup, tuning="", pairs_log=None):
+def _cpd_line(workload, steps, warmup, elapsed, world, plan, res, truth):
+    """The headline part of a C1 / C2 line: rate of the timed window, its configuration and the EM state after it."""
+    import torch
+
+    kind, n, desc = WORKLOADS[workload]
+    out = _base("EM iterations/sec (RigidCPD, N=M=100k fp32)" if workload == "rigid_100k"
+                else "EM iterations/sec (%s)" % desc, steps / elapsed, elapsed, steps, warmup, desc, "f32", world)
+    out["config"].update({
+        "window": "EM iterations 0..%d of the registration (state reset after the warm-up steps)" % (steps - 1),
+        "target_sharding": "cells of a recursive bisection of the target (probreg_amd.dist.bisection_shards) over %d rank(s)" % world,
+        "collective": (("1 ncclAllReduce (RCCL, issued by libprobreg_hip.so on the plan's stream) of the moment block's 24 fp64 sums per iteration"
+                        if getattr(plan, "_comm", None) is not None else
+                        "1 torch.distributed all_reduce (%s) of 32 fp64 per iteration" % torch.distributed.get_backend())
+                       if world > 1 else "none"),
+        "collective_path": ("library-side RCCL (prg_cpd_set_comm: ncclAllReduce inside prg_cpd_estep, plan's stream)"
+                            if getattr(plan, "_comm", None) is not None else
+                            "torch.distributed (%s)" % torch.distributed.get_backend()
+                            if torch.distributed.is_available() and torch.distributed.is_initialized() else "none: one process"),
+        "m": plan.m, "n_local": plan.n, "n_global": n})
+    out["result"] = {"sigma2": res.sigma2, "q": res.q}
+    if kind == "rigid":
+        r_true, _t_true, _ = truth
+        out["result"]["rot_err_vs_truth"] = float(np.max(np.abs(res.transformation.rot - r_true)))
+    return out
+
+
+def bench_cpd(workload, steps, warmup, tuning="", pairs_log=None, full=False):
     import torch
     from probreg_amd import _lib, cpd, synthetic
 
@@ -306,6 +355,17 @@ def bench_cpd(workload, steps, warmup, tuning="", pairs_log=None):
     reg._restart()                 # EM state back to iteration 0: the timed window is iterations 0 .. steps-1
     elapsed = timed(steps)
     res = reg._result_from_params(plan.get_params())
+    outputs = None
+    if rank == 0:  # what the last timed step left: the caller's transformation, sigma2, q, and the E-step's sums
+        tfm = res.transformation
+        outputs = {"sigma2": res.sigma2, "q": res.q, "t": tfm.t, "moments": plan.get_moments(), "pt1": plan.get_estep_pt1()}
+        outputs.update({"rot": tfm.rot, "scale": tfm.scale} if kind == "rigid" else {"b": tfm.b})
+    if not full:
+        if rank != 0:
+            return None
+        out = _cpd_line(workload, steps, warmup, elapsed, world, plan, res, truth)
+        out["_outputs"] = outputs
+        return out
 
     # regimes: iteration 0 alone (every pair evaluated) and iterations 45..49 (sigma2 ~ noise level: ~97 % culled)
     reg._restart()
@@ -375,20 +435,8 @@ def bench_cpd(workload, steps, warmup, tuning="", pairs_log=None):
     # SURVEY.md 8(d) figure kept beside it: algorithmic bytes of the reference's formulation at fp32 (P written once
     # by the column pass, read once by the row pass) over the measured time - an EFFECTIVE rate, not a roofline
     alg_row = 4.0 * m_pts * n_loc + 4.0 * (m_pts + n_loc) * 5
-    out = _base("EM iterations/sec (RigidCPD, N=M=100k fp32)" if workload == "rigid_100k"
-                else "EM iterations/sec (%s)" % desc, steps / elapsed, elapsed, steps, warmup, desc, "f32", world)
-    out["config"].update({
-        "window": "EM iterations 0..%d of the registration (state reset after the warm-up steps)" % (steps - 1),
-        "target_sharding": "cells of a recursive bisection of the target (probreg_amd.dist.bisection_shards) over %d rank(s)" % world,
-        "collective": (("1 ncclAllReduce (RCCL, issued by libprobreg_hip.so on the plan's stream) of the moment block's 24 fp64 sums per iteration"
-                        if getattr(plan, "_comm", None) is not None else
-                        "1 torch.distributed all_reduce (%s) of 32 fp64 per iteration" % torch.distributed.get_backend())
-                       if world > 1 else "none"),
-        "collective_path": ("library-side RCCL (prg_cpd_set_comm: ncclAllReduce inside prg_cpd_estep, plan's stream)"
-                            if getattr(plan, "_comm", None) is not None else
-                            "torch.distributed (%s)" % torch.distributed.get_backend()
-                            if torch.distributed.is_available() and torch.distributed.is_initialized() else "none: one process"),
-        "m": m_pts, "n_local": n_loc, "n_global": n})
+    out = _cpd_line(workload, steps, warmup, elapsed, world, plan, res, truth)
+    out["_outputs"] = outputs
     out["trajectory_it_s"] = steps / elapsed
     out["dense_it_s"] = 1.0 / t_dense
     out["late_it_s"] = 1.0 / t_late
@@ -447,21 +495,18 @@ def bench_cpd(workload, steps, warmup, tuning="", pairs_log=None):
                           "hbm_peak_GBs": HBM_PEAK_GBS},
     }
     out["kernel_ms"] = {"mean_over_timed_iterations": acc, "first_timed_iteration": first, "last_timed_iteration": last}
-    out["result"] = {"sigma2": res.sigma2, "q": res.q}
-    if kind == "rigid":
-        r_true, _t_true, _ = truth
-        out["result"]["rot_err_vs_truth"] = float(np.max(np.abs(res.transformation.rot - r_true)))
     return out
 
 
 # ----------------------------------------------------------------------------------------------------------------
 # C3: non-rigid CPD
 # ----------------------------------------------------------------------------------------------------------------
-def bench_nonrigid(workload, steps, warmup, dense_compare=True):
+def bench_nonrigid(workload, steps, warmup, dense_compare=True, full=False):
     """One step = E-step (fp32 sweeps over all M x N pairs) + M-step (cpd.py:284-303) on the low-rank factor of G
     (G = F F^T, pivoted Cholesky at set_source).  The timed window is EM iterations 0..steps-1 of the
-    registration (state reset after the warm-up).  `dense_solver` times the same M-step through the M x M fp64
-    Cholesky the plan falls back to when G is not low rank, and how far the two solutions are apart."""
+    registration (state reset after the warm-up).  With `full`: the split of one iteration into kernels, and
+    `dense_solver` times the same M-step through the M x M fp64 Cholesky the plan falls back to when G is not low rank,
+    and how far the two solutions are apart."""
     import numpy as np
     import torch
     from probreg_amd import cpd, synthetic
@@ -494,7 +539,15 @@ def bench_nonrigid(workload, steps, warmup, dense_compare=True):
         step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    sigma2_end = float(plan.get_params()[13])
+    params_end = plan.get_params()
+    sigma2_end = float(params_end[13])
+    outputs = {"w": plan.get_w(), "sigma2": sigma2_end, "q": float(params_end[14])}
+    out = _base("EM iterations/sec (%s)" % desc, steps / elapsed, elapsed, steps, warmup, desc, "f32 E-step / f64 M-step")
+    out["config"]["window"] = "EM iterations 0..%d of the registration (state reset after the warm-up steps)" % (steps - 1)
+    out["result"] = {"sigma2": sigma2_end}
+    out["_outputs"] = outputs
+    if not full:
+        return out
     # split of one iteration: E-step kernels by HIP events, M-step by synchronised wall time
     restart()
     ms = plan.estep_timed(0.0)
@@ -506,8 +559,6 @@ def bench_nonrigid(workload, steps, warmup, dense_compare=True):
     t_m = time.perf_counter() - t0
     w_lr = plan.get_w()
     t_lr = plan.nonrigid_apply()
-    out = _base("EM iterations/sec (%s)" % desc, steps / elapsed, elapsed, steps, warmup, desc, "f32 E-step / f64 M-step")
-    out["config"]["window"] = "EM iterations 0..%d of the registration (state reset after the warm-up steps)" % (steps - 1)
     row_tf = row_pairs * (FLOP_ROW_LEAN if plan.last_estep_lean() else FLOP_ROW) / (ms["rowpass"] * 1e-3) / 1e12
     out["roofline"] = {"bound": "valu", "kernel": "k_rowpass (E-step sweep 2 over all M x N pairs; the M-step is no longer "
                        "the dominant kernel: G = F F^T, rank %d)" % rank,
@@ -517,7 +568,6 @@ def bench_nonrigid(workload, steps, warmup, dense_compare=True):
     out["kernel_ms"] = {"estep": {k: float(v) for k, v in ms.items()}, "mstep_wall": 1e3 * t_m}
     out["kernel_factor"] = {"rank": rank, "build_ms_incl_upload": 1e3 * t_build,
                             "what": "pivoted Cholesky of G, columns evaluated on the fly in fp64, stops at 1e-14 per entry"}
-    out["result"] = {"sigma2": sigma2_end}
     if rank > 0 and dense_compare:  # the dense fallback on the same E-step, for the record
         try:
             class _Dense(cpd.NonRigidCPD):
@@ -548,8 +598,9 @@ def bench_nonrigid(workload, steps, warmup, dense_compare=True):
     return out
 
 
-def bench_bcpd(workload, steps, warmup):
-    """BCPD: one step = weighted E-step + Woodbury M-step (bcpd.py:82-98 loop body without the convergence test)."""
+def bench_bcpd(workload, steps, warmup, full=False):
+    """BCPD: one step = weighted E-step + Woodbury M-step (bcpd.py:82-98 loop body without the convergence test).  The window
+    opens at the end of the last warm-up iteration (with `--warmup 0`, of one untimed first iteration)."""
     import torch
     from probreg_amd import bcpd, synthetic
 
@@ -559,9 +610,14 @@ def bench_bcpd(workload, steps, warmup):
     reg = bcpd.CombinedBCPD(src)
     stamps = []
     reg.set_callbacks([lambda tr: (torch.cuda.synchronize(), stamps.append(time.perf_counter()))])
-    reg.registration(tgt, w=0.05, maxiter=warmup + steps, tol=-1.0)
-    elapsed = stamps[-1] - stamps[warmup - 1] if warmup > 0 else stamps[-1] - stamps[0]
-    nsteps = steps if warmup > 0 else steps - 1
+    lead = max(warmup, 1)
+    tfm = reg.registration(tgt, w=0.05, maxiter=lead + steps, tol=-1.0)
+    elapsed = stamps[-1] - stamps[lead - 1]
+    out = _base("EM iterations/sec (%s)" % desc, steps / elapsed, elapsed, steps, warmup, desc, "f32 E-step / f64 M-step")
+    rig = tfm.rigid_trans
+    out["_outputs"] = {"rot": rig.rot, "t": rig.t, "scale": rig.scale, "v": tfm.v}
+    if not full:
+        return out
     plan = reg._plan
     nu, resid = np.ones(n), np.zeros((n, 3))
     plan.bcpd_solve(2.0, 10.0, resid, nu)
@@ -571,7 +627,6 @@ def bench_bcpd(workload, steps, warmup):
     torch.cuda.synchronize()
     t_m = time.perf_counter() - t0
     flops = 4.0 / 3.0 * n ** 3  # Cholesky (1/3) + triangular solve with M right-hand sides (1)
-    out = _base("EM iterations/sec (%s)" % desc, nsteps / elapsed, elapsed, nsteps, warmup, desc, "f32 E-step / f64 M-step")
     out["roofline"] = {"bound": "mfma", "kernel": "k_gemm_nt_f64 (Cholesky of S + triangular solve for diag(Sigma))",
                        "achieved": flops / t_m / 1e12, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                        "frac": flops / t_m / 1e12 / F64_MFMA_PEAK_TFLOPS, "traffic": None,
@@ -614,6 +669,7 @@ def bench_filterreg(workload, steps, warmup):
     elapsed = time.perf_counter() - t0
     out = plan.get_state()
     state["rot"], state["sigma2"] = out[:9].reshape(3, 3).copy(), out[15]
+    outputs = {"state": out.copy(), "rot": state["rot"], "sigma2": state["sigma2"]}
     d, c = 3, 5
     lat = float(np.mean(sizes))
     alg = (2 * n) * (4 * d + 8 * (d + 1)) + n * (4 * c + 8 * (d + 1) + 8 * c * (d + 1)) \
@@ -627,6 +683,7 @@ def bench_filterreg(workload, steps, warmup):
                        "algorithmic_bytes_per_iteration": alg, "mean_lattice_vertices": lat,
                        "lattice_vertices_first_last": [sizes[0], sizes[-1]]}
     out["result"] = {"sigma2": state["sigma2"], "rot_err_vs_truth": float(np.max(np.abs(state["rot"] - r_true)))}
+    out["_outputs"] = outputs
     return out
 
 
@@ -653,10 +710,19 @@ def main():
     ap.add_argument("--pairs-log", default="", help="write the per-iteration (engine, pairs, ms) table of the timed window here")
     ap.add_argument("--no-dense-compare", action="store_true",
                     help="non-rigid: skip the M-step through the dense fallback (profiles of the product path alone)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: dense / late regimes, per-kernel roofline replay, CPU "
+                         "baselines and parity, the other workloads (the options above trim it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.pairs_log and not args.full:
+        raise SystemExit("--pairs-log comes from the per-kernel replay of the window: it needs --full")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` on its own: start the N ranks here (one process per GPU under torch.distributed.run,
         # exactly the command the docstring gives); rank 0 of that run prints the one JSON line on this stdout
@@ -705,21 +771,30 @@ def main():
         if world > 1:
             raise SystemExit("%s runs as single-GPU replicas (DESIGN.md section 6)" % args.workload)
         if kind == "nonrigid":
-            out = bench_nonrigid(args.workload, args.steps, args.warmup, dense_compare=not args.no_dense_compare)
+            out = bench_nonrigid(args.workload, args.steps, args.warmup, dense_compare=not args.no_dense_compare,
+                                 full=args.full)
+        elif kind == "bcpd":
+            out = bench_bcpd(args.workload, args.steps, args.warmup, full=args.full)
         else:
-            out = {"filterreg": bench_filterreg, "bcpd": bench_bcpd}[kind](args.workload, args.steps, args.warmup)
+            out = bench_filterreg(args.workload, args.steps, args.warmup)
+        outputs = out.pop("_outputs")
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
         return
-    out = bench_cpd(args.workload, args.steps, args.warmup, args.tuning, args.pairs_log or None)
+    out = bench_cpd(args.workload, args.steps, args.warmup, args.tuning, args.pairs_log or None, full=args.full)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        outputs = out.pop("_outputs")
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, outputs)
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(n)
-        if world == 1 and args.workload == "rigid_100k" and not args.no_other_workloads:
+        if world == 1 and args.full and args.workload == "rigid_100k" and not args.no_other_workloads:
             others = {}
             for name, fn, k, w in (("affine_200k", bench_cpd, 20, 1), ("nonrigid_50k", bench_nonrigid, 20, 2),
                                    ("filterreg_500k", bench_filterreg, 20, 3)):
                 try:
-                    others[name] = _slim(fn(name, k, w))
+                    others[name] = _slim(fn(name, k, w) if fn is bench_filterreg else fn(name, k, w, full=True))
                 except Exception as e:  # a failing side workload must not take the headline line with it
                     others[name] = {"error": "%s: %s" % (type(e).__name__, e)}
                 torch.cuda.empty_cache()

@@ -1,5 +1,5 @@
 """The bench contract on the committed line of the round (the newest profiles/r<N>_bench_default_line_1gpu*.json = an
-unprofiled `python bench.py` run on one MI355X): every key the driver and the judge read is there, with the promised meaning."""
+unprofiled `python bench.py --full` run on one MI355X): every key the driver and the judge read is there, with the promised meaning."""
 import glob
 import json
 import os

@@ -8,7 +8,7 @@ tag=${TAG:-r6}
 out=gpurun_out/${tag}_$step
 mkdir -p $out
 quiet='amdgpu.ids\|^RCCL\|^HIP version\|^ROCm\|^Hostname\|^Librccl'
-c1="python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-other-workloads"
+c1="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-other-workloads"
 line() { python - "$@" <<'PY'
 import json, sys
 for f in sys.argv[1:]:

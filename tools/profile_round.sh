@@ -10,10 +10,10 @@ sum() { python tools/rocpd_summary.py "$@"; }
 db() { ls $1/*.db $1/*/*.db 2>/dev/null | head -1; }
 
 # Ordered by importance: a round's GPU budget may end before the script does (set PROFILE_FULL=1 for every pass).
-# 1. the driver's own command, un-profiled: the line tests/test_bench_line_schema.py checks
-python bench.py > $out/${tag}_bench_default_line_1gpu.json 2> $out/default_line.err
+# 1. the full line (`--full`: the headline and every figure beside it), un-profiled: the line tests/test_bench_line_schema.py checks
+python bench.py --full > $out/${tag}_bench_default_line_1gpu.json 2> $out/default_line.err
 
-c1="python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-other-workloads"
+c1="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-other-workloads"
 # 2. C1 alone: the un-profiled line with its per-iteration (engine, pairs, ms) table, then the kernel trace of the same command -
 # roofline.frac can be recomputed from these two committed files
 $c1 --pairs-log $out/${tag}_c1_pairs_per_iteration.log > $out/${tag}_bench_c1_line.json 2> $out/c1_line.err
@@ -57,13 +57,13 @@ for spec in 8,3,3 8,3,9 8,3,19 1,0,19; do
 done
 
 # 3b. C2 (the 8-GPU configuration): HBM traffic of its two sweeps, and the shard replay the 6x projection rests on
-c2="python bench.py --workload affine_200k --steps 20 --warmup 1 --no-cpu-baseline"
+c2="python bench.py --full --workload affine_200k --steps 20 --warmup 1 --no-cpu-baseline"
 pmc c2 $c2
 sum --pmc $(db $out/c2_FETCH_SIZE) $(db $out/c2_WRITE_SIZE) > $out/${tag}_affine_200k_pmc.txt
 [ -z "$SKIP_SHARD_C2" ] && python tools/shard_window.py 200000 20 affine 2>&1 | grep -v "amdgpu.ids\|^RCCL\|^HIP version\|^ROCm\|^Hostname\|^Librccl" > $out/${tag}_shard_window_c2_allranks.log
 
 # 4. C3 and C4: kernel traces and HBM traffic
-c3="python bench.py --workload nonrigid_50k --steps 20 --warmup 2 --no-dense-compare"
+c3="python bench.py --full --workload nonrigid_50k --steps 20 --warmup 2 --no-dense-compare"
 rocprofv3 --kernel-trace --stats -d $out/c3_kt -o b -- $c3 > $out/c3_line.json 2> $out/c3_kt.err
 sum $(db $out/c3_kt) > $out/${tag}_nonrigid_50k_kernel_trace.txt
 c4="python bench.py --workload filterreg_500k --steps 20 --warmup 3"
@@ -76,7 +76,7 @@ sum --pmc $(db $out/c4_FETCH_SIZE) $(db $out/c4_WRITE_SIZE) > $out/${tag}_filter
 
 # 5. the whole default command under the kernel trace (C1, C2, C3, C4 mixed)
 if [ -n "$PROFILE_FULL" ]; then
-  rocprofv3 --kernel-trace --stats -d $out/kt_default -o b -- python bench.py --no-cpu-baseline > $out/bench_default_line_profiled.json 2> $out/kt_default.err
+  rocprofv3 --kernel-trace --stats -d $out/kt_default -o b -- python bench.py --full --no-cpu-baseline > $out/bench_default_line_profiled.json 2> $out/kt_default.err
   sum $(db $out/kt_default) > $out/${tag}_bench_default_kernel_trace.txt
 fi
 ls -la $out/*.txt
