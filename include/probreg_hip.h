@@ -413,6 +413,32 @@ int prg_fr_mstep_from_arrays(int device, void* hip_stream, const double* t_sourc
 int prg_kabsch_weighted(int device, void* hip_stream, const float* model_hd, const float* target_hd,
                         const float* weight_hd, int64_t n, int dim, double* rot_host, double* t_host);
 
+/* ---- GMMTree (hierarchical 8-ary GMM, probreg/gmmtree.py + cc/gmmtree.{h,cc}) ------------------------------------
+ * Everything in fp64 (the reference's native code is float).  Node records are 10 doubles:
+ *   pi, mu (3), Sigma (xx, xy, xz, yy, yz, zz); node j of level l sits at 8 (8^l - 1) / 7 + local index, the
+ *   children of j at (j + 1) 8 ... + 7 (gmmtree.cc:42-44).  1 <= tree_level <= 4.  Results are reproducible: every
+ *   sum over points is reduced in a fixed order (no floating-point atomics). */
+typedef struct prg_gmmtree prg_gmmtree;
+/* The pybind module probreg._gmmtree (cc/gmmtree_py.cc) as a handle: one device, one stream. */
+int prg_gmm_create(prg_gmmtree** out, int device, void* hip_stream);
+int prg_gmm_destroy(prg_gmmtree* h);
+/* buildGmmTree (gmmtree.cc:98-123) with initializeNodes (:46-73) on explicit leaf indices init_idx_host[8^tree_level]
+ * (the reference draws them from std::rand): points n x 3 float64.  Each level runs EM (gmmTreeEstep :125-163,
+ * gmmTreeMstep :165-173, logLikelihood :20-33) until |q - q_prev| < lambda_s or max_iter iterations.  Out per level
+ * (tree_level entries): iters_host, q_host (last q, may be NULL), dq_host (last |q - q_prev|, may be NULL). */
+int prg_gmm_build(prg_gmmtree* h, const double* points_hd, int64_t n, int tree_level, const int64_t* init_idx_host,
+                  double lambda_s, double lambda_d, int max_iter, int* iters_host, double* q_host, double* dq_host);
+/* Install a given tree (n_nodes x 10 doubles, host) instead of building one; get_nodes reads the current tree back. */
+int prg_gmm_set_nodes(prg_gmmtree* h, const double* nodes_host, int tree_level);
+int prg_gmm_get_nodes(prg_gmmtree* h, double* nodes_host);
+/* Target of the registration E-step: n x 3 float64, kept on the device across iterations. */
+int prg_gmm_set_target(prg_gmmtree* h, const double* target_hd, int64_t n);
+/* gmmTreeRegEstep (gmmtree.cc:175-214) on the target transformed by scale * rot9 (row-major) + t3
+ * (GMMTree.registration gmmtree.py:87): per node m01_host[n_nodes x 4] = (m0, m1) and, if m2_host is not NULL,
+ * m2_host[n_nodes x 6] = m2 (xx, xy, xz, yy, yz, zz).  Synchronises. */
+int prg_gmm_reg_estep(prg_gmmtree* h, const double* rot9, const double* t3, double scale, double lambda_c,
+                      double* m01_host, double* m2_host);
+
 #ifdef __cplusplus
 }
 #endif

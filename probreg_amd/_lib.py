@@ -142,6 +142,13 @@ SIGNATURES = {
     "prg_fr_mstep_pt2pl": [_vp, _d, _i, _d, _vp],
     "prg_fr_mstep_from_arrays": [_i, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp],
     "prg_kabsch_weighted": [_i, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp],
+    "prg_gmm_create": [_pp, _i, _vp],
+    "prg_gmm_destroy": [_vp],
+    "prg_gmm_build": [_vp, _vp, _i64, _i, _vp, _d, _d, _i, _vp, _vp, _vp],
+    "prg_gmm_set_nodes": [_vp, _vp, _i],
+    "prg_gmm_get_nodes": [_vp, _vp],
+    "prg_gmm_set_target": [_vp, _vp, _i64],
+    "prg_gmm_reg_estep": [_vp, _vp, _vp, _d, _d, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():
