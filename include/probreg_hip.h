@@ -318,6 +318,12 @@ int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const double* nu_hd,
 int prg_gauss_transform_direct(int device, void* hip_stream, const double* source_hd, int64_t s,
                                const double* target_hd, int64_t t, int dim, const double* weights_hd,
                                int n_weight_rows, double h, double* out_hd);
+/* The same sum with squared distance, exponential and accumulation in fp64 (prg_gauss_transform_direct takes the
+ * exponential in fp32): the K x K component pairs of cost_functions.py:36-41 inside the GMMReg cost functions
+ * (cost_functions.py:57-65, 89-102), where BFGS differentiates the result. */
+int prg_gauss_transform_direct_f64(int device, void* hip_stream, const double* source_hd, int64_t s,
+                               const double* target_hd, int64_t t, int dim, const double* weights_hd,
+                               int n_weight_rows, double h, double* out_hd);
 
 /* sum_{m,n} |x_m - y_n|^2 / (M*D*N), closed form in fp64 on the device.
  * Replaces: mu.squared_kernel_sum, math_utils.py:28-29. */
@@ -438,6 +444,40 @@ int prg_gmm_set_target(prg_gmmtree* h, const double* target_hd, int64_t n);
  * m2_host[n_nodes x 6] = m2 (xx, xy, xz, yy, yz, zz).  Synchronises. */
 int prg_gmm_reg_estep(prg_gmmtree* h, const double* rot9, const double* t3, double scale, double lambda_c,
                       double* m01_host, double* m2_host);
+
+/* ---- Spherical Gaussian-mixture fit (the feature generator of GMMReg, probreg/features.py:54-69) ------------------
+ * features.GMM.compute calls scikit-learn's GaussianMixture(n_components, covariance_type = "spherical").fit; these
+ * entry points restate that fit in fp64 on the device.  Results are reproducible: every sum over points is reduced
+ * in a fixed order (no floating-point atomics).  Means are k x dim, weights / covariances / precisions k doubles. */
+typedef struct prg_gmmfit prg_gmmfit;
+/* One fit context on one device / stream (features.GMM.init, features.py:64-65, creates the sklearn estimator). */
+int prg_gmmfit_create(prg_gmmfit** out, int device, void* hip_stream);
+int prg_gmmfit_destroy(prg_gmmfit* h);
+/* The cloud of `self._clf.fit(data)` (features.py:68): n x dim float64, dim 2 or 3, uploaded once. */
+int prg_gmmfit_set_data(prg_gmmfit* h, const double* data_hd, int64_t n, int dim);
+/* Greedy k-means++ seeding of k centres (what sklearn's KMeans does first inside the fit's default init_params =
+ * "kmeans"): uniforms_host[k x n_trials] in [0, 1), entry 0 draws the first centre, row s the n_trials <= 16
+ * candidates of centre s by D^2 sampling; the candidate with the lowest potential is kept.  k <= n. */
+int prg_gmmfit_seed(prg_gmmfit* h, int k, const double* uniforms_host, int n_trials);
+/* Indices of the points the k seeds were taken from. */
+int prg_gmmfit_get_seeds(prg_gmmfit* h, int* index_host);
+/* Lloyd iterations from the seeds (sklearn KMeans: stop when no label changes or the summed squared centre shift is
+ * <= tol, at most max_iter); an empty cluster keeps its centre.  n_iter_host may be NULL. */
+int prg_gmmfit_lloyd(prg_gmmfit* h, int max_iter, double tol, int* n_iter_host);
+/* The parameters sklearn's fit starts from: its M-step on the one-hot responsibilities of the Lloyd labels, with
+ * weights = nk / n (BaseMixture._initialize_parameters -> GaussianMixture._initialize). */
+int prg_gmmfit_init_from_labels(prg_gmmfit* h, double reg_covar);
+/* Explicit start (sklearn's weights_init, means_init, precisions_init): precisions > 0, weights >= 0. */
+int prg_gmmfit_set_params(prg_gmmfit* h, int k, const double* weights_host, const double* means_host,
+                          const double* precisions_host);
+/* EM from the current parameters (the loop of BaseMixture.fit_predict): E-step, M-step, lower bound = mean per-point
+ * normaliser; stops when |change of the lower bound| < tol or after max_iter iterations.  lower_bounds_host (max_iter
+ * doubles, may be NULL) receives the lower bound of every iteration run. */
+int prg_gmmfit_em(prg_gmmfit* h, double tol, int max_iter, double reg_covar, int* n_iter_host, int* converged_host,
+                  double* lower_bounds_host);
+/* means_ / weights_ / covariances_ (features.py:69 returns the first two); each pointer may be NULL.  After seed or
+ * lloyd only the centres (means) exist. */
+int prg_gmmfit_get_params(prg_gmmfit* h, double* weights_host, double* means_host, double* covariances_host);
 
 #ifdef __cplusplus
 }

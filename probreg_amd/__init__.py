@@ -3,7 +3,8 @@
 Public modules mirror the reference package (neka-nat/probreg):
 ``cpd`` (registration_cpd, RigidCPD, AffineCPD, NonRigidCPD), ``filterreg``
 (registration_filterreg), ``transformation``, ``math_utils``, ``gauss_transform``,
-``gaussian_filtering``, ``cost_functions.compute_l2_dist``, ``bcpd``, ``gmmtree``.  All arithmetic of the hot path runs in ``csrc/libprobreg_hip.so``.
+``gaussian_filtering``, ``cost_functions``, ``bcpd``, ``gmmtree``, ``features``, ``l2dist_regs``
+(registration_gmmreg), ``se3_op``.  All arithmetic of the hot path runs in ``csrc/libprobreg_hip.so``.
 Sub-modules are imported on first attribute access so that ``import probreg_amd`` itself
 never touches the GPU.
 """
@@ -13,7 +14,7 @@ from .version import __version__
 
 _SUBMODULES = ("cpd", "filterreg", "transformation", "math_utils", "gauss_transform", "gaussian_filtering",
                "cost_functions", "dist", "engine", "synthetic", "bcpd",
-               "gmmtree")
+               "gmmtree", "features", "l2dist_regs", "se3_op")
 
 
 def __getattr__(name):

@@ -118,6 +118,7 @@ SIGNATURES = {
     "prg_cpd_bcpd_build_g": [_vp, _d],
     "prg_cpd_bcpd_solve": [_vp, _d, _d, _vp, _vp, _vp, _vp],
     "prg_gauss_transform_direct": [_i, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _d, _vp],
+    "prg_gauss_transform_direct_f64": [_i, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _d, _vp],
     "prg_squared_kernel_sum": [_i, _vp, _vp, _i64, _vp, _i64, _i, _c.POINTER(_d)],
     "prg_rbf_kernel": [_i, _vp, _vp, _i64, _vp, _i64, _i, _d, _vp],
     "prg_inverse_multiquadric_kernel": [_i, _vp, _vp, _i64, _vp, _i64, _i, _d, _vp],
@@ -149,6 +150,16 @@ SIGNATURES = {
     "prg_gmm_get_nodes": [_vp, _vp],
     "prg_gmm_set_target": [_vp, _vp, _i64],
     "prg_gmm_reg_estep": [_vp, _vp, _vp, _d, _d, _vp, _vp],
+    "prg_gmmfit_create": [_pp, _i, _vp],
+    "prg_gmmfit_destroy": [_vp],
+    "prg_gmmfit_set_data": [_vp, _vp, _i64, _i],
+    "prg_gmmfit_seed": [_vp, _i, _vp, _i],
+    "prg_gmmfit_get_seeds": [_vp, _vp],
+    "prg_gmmfit_lloyd": [_vp, _i, _d, _c.POINTER(_i)],
+    "prg_gmmfit_init_from_labels": [_vp, _d],
+    "prg_gmmfit_set_params": [_vp, _i, _vp, _vp, _vp],
+    "prg_gmmfit_em": [_vp, _d, _i, _d, _c.POINTER(_i), _c.POINTER(_i), _vp],
+    "prg_gmmfit_get_params": [_vp, _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

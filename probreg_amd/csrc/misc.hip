@@ -144,6 +144,35 @@ __global__ __launch_bounds__(kBlock) void k_gauss_direct(const double* __restric
     }
 }
 
+// The same transform with everything in fp64 (squared distance, exponential, sums): the K x K component pairs of the
+// GMMReg cost functions, where BFGS differentiates the value and 1e-7 per term is visible.  kk = -1 / h^2.
+template <int C>
+__global__ __launch_bounds__(kBlock) void k_gauss_direct_f64(const double* __restrict__ src3, int64_t s_cap,
+                                                             const double* __restrict__ wrows,
+                                                             const double* __restrict__ tgt, int64_t t, int dim, double kk,
+                                                             double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    double tx = 0.0, ty = 0.0, tz = 0.0;
+    if (i < t) {
+        tx = tgt[i * dim];
+        ty = tgt[i * dim + 1];
+        tz = dim > 2 ? tgt[i * dim + 2] : 0.0;
+    }
+    double acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 0.0;
+    for (int64_t j = 0; j < s_cap; ++j) {
+        const double dx = tx - src3[3 * j], dy = ty - src3[3 * j + 1], dz = tz - src3[3 * j + 2];
+        const double e = exp(kk * (dx * dx + dy * dy + dz * dz));
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = fma(wrows[(int64_t)c * s_cap + j], e, acc[c]);
+    }
+    if (i < t) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) out[(int64_t)c * t + i] = acc[c];
+    }
+}
+
 // source rows (dim doubles each) -> [cap][3] doubles, pads far away; weight rows -> [rows][cap], pads 0
 __global__ __launch_bounds__(kBlock) void k_pack_gauss(const double* __restrict__ s, const double* __restrict__ w, int64_t n,
                                                        int dim, int rows, int64_t cap, double* __restrict__ src3,
@@ -424,6 +453,52 @@ int prg_gauss_transform_direct(int device, void* hip_stream, const double* sourc
             c += 2;
         } else {
             k_gauss_direct<1><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            c += 1;
+        }
+    }
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipMemcpyAsync(out_hd, bo.p, (size_t)t * rows * sizeof(double), hipMemcpyDefault, st));
+    PRG_HIP(hipStreamSynchronize(st));
+    return PRG_OK;
+}
+
+int prg_gauss_transform_direct_f64(int device, void* hip_stream, const double* source_hd, int64_t s, const double* target_hd,
+                               int64_t t, int dim, const double* weights_hd, int n_weight_rows, double h,
+                               double* out_hd) {
+    PRG_REQUIRE(source_hd && target_hd && weights_hd && out_hd, PRG_ERR_INVALID,
+                "prg_gauss_transform_direct_f64: NULL argument");
+    PRG_REQUIRE(s > 0 && t > 0 && (dim == 2 || dim == 3) && n_weight_rows > 0 && h > 0, PRG_ERR_INVALID,
+                "prg_gauss_transform_direct_f64: need s, t, rows > 0, dim in {2,3}, h > 0");
+    prg::DeviceGuard g(device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_gauss_transform_direct_f64: hipSetDevice(%d) failed", device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int64_t cap = prg::round_up(s, 256);
+    const int rows = n_weight_rows;
+    TmpBuf bs, bt, bw, b3, bwr, bo;
+    PRG_HIP(hipMalloc(&bs.p, (size_t)s * dim * sizeof(double)));
+    PRG_HIP(hipMalloc(&bt.p, (size_t)t * dim * sizeof(double)));
+    PRG_HIP(hipMalloc(&bw.p, (size_t)s * rows * sizeof(double)));
+    PRG_HIP(hipMalloc(&b3.p, (size_t)cap * 3 * sizeof(double)));
+    PRG_HIP(hipMalloc(&bwr.p, (size_t)cap * rows * sizeof(double)));
+    PRG_HIP(hipMalloc(&bo.p, (size_t)t * rows * sizeof(double)));
+    PRG_HIP(hipMemcpyAsync(bs.p, source_hd, (size_t)s * dim * sizeof(double), hipMemcpyDefault, st));
+    PRG_HIP(hipMemcpyAsync(bt.p, target_hd, (size_t)t * dim * sizeof(double), hipMemcpyDefault, st));
+    PRG_HIP(hipMemcpyAsync(bw.p, weights_hd, (size_t)s * rows * sizeof(double), hipMemcpyDefault, st));
+    const double kk = -1.0 / (h * h);
+    k_pack_gauss<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>((const double*)bs.p, (const double*)bw.p, s, dim, rows, cap,
+                                                                         (double*)b3.p, (double*)bwr.p);
+    const unsigned grid = (unsigned)prg::ceil_div(t, kBlock);
+    for (int c = 0; c < rows;) {  // four weight rows per sweep (compute_l2_dist: 1 + D rows = one sweep), then 2, then 1
+        const double* w = (const double*)bwr.p + (size_t)c * cap;
+        double* o = (double*)bo.p + (size_t)c * t;
+        if (rows - c >= 4) {
+            k_gauss_direct_f64<4><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            c += 4;
+        } else if (rows - c >= 2) {
+            k_gauss_direct_f64<2><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            c += 2;
+        } else {
+            k_gauss_direct_f64<1><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
             c += 1;
         }
     }

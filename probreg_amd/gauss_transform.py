@@ -13,8 +13,10 @@ from ._lib import check, lib, ptr
 from .engine import _current_device_and_stream
 
 
-def _gauss_transform_direct(source, target, weights, h):
-    r"""\sum_j weights[j] * exp(-||target[i] - source[j]||^2 / h^2)   (gauss_transform.py:10-16)."""
+def _gauss_transform_direct(source, target, weights, h, exact=False):
+    r"""\sum_j weights[j] * exp(-||target[i] - source[j]||^2 / h^2)   (gauss_transform.py:10-16).
+
+    ``exact``: exponential in fp64 instead of fp32 (``prg_gauss_transform_direct_f64``)."""
     _lib.require_gpu()
     source = np.ascontiguousarray(source, dtype=np.float64)  # float64 across the ABI: differences are formed in fp64
     target = np.ascontiguousarray(target, dtype=np.float64)
@@ -31,28 +33,30 @@ def _gauss_transform_direct(source, target, weights, h):
         raise ValueError("weights must have one entry per source point.")
     dev, st = _current_device_and_stream()
     out = np.empty((rows, target.shape[0]), dtype=np.float64)
-    check(lib.prg_gauss_transform_direct(dev, ctypes.c_void_p(st), ptr(source), source.shape[0], ptr(target),
-                                         target.shape[0], source.shape[1], ptr(np.ascontiguousarray(wmat)), rows,
-                                         float(h), ptr(out)))
+    fn = lib.prg_gauss_transform_direct_f64 if exact else lib.prg_gauss_transform_direct
+    check(fn(dev, ctypes.c_void_p(st), ptr(source), source.shape[0], ptr(target),
+             target.shape[0], source.shape[1], ptr(np.ascontiguousarray(wmat)), rows, float(h), ptr(out)))
     return out[0] if weights.ndim == 1 else out
 
 
 class Direct(object):
-    def __init__(self, source, h):
+    def __init__(self, source, h, exact=False):
         self._source = source
         self._h = h
+        self._exact = exact
 
     def compute(self, target, weights):
-        return _gauss_transform_direct(self._source, target, weights, self._h)
+        return _gauss_transform_direct(self._source, target, weights, self._h, self._exact)
 
 
 class GaussTransform(object):
     """``GaussTransform(source, h).compute(target, weights)`` as in reference gauss_transform.py:28-60: weights may be
-    one row (S) or several (C x S); ``eps`` and ``sw_h`` only mattered for the reference's IFGT switch."""
+    one row (S) or several (C x S); ``eps`` and ``sw_h`` only mattered for the reference's IFGT switch.  ``exact``
+    (an extension) takes the exponentials in fp64 instead of fp32."""
 
-    def __init__(self, source, h, eps=1.0e-4, sw_h=0.01):
+    def __init__(self, source, h, eps=1.0e-4, sw_h=0.01, exact=False):
         self._m = source.shape[0]
-        self._impl = Direct(source, h)
+        self._impl = Direct(source, h, exact)
 
     def compute(self, target, weights=None):
         if weights is None:

@@ -40,6 +40,27 @@ def rbf_kernel(x, y, beta):
     return out
 
 
+def tps_kernel(x, y):
+    """Thin-plate-spline kernel as float32 (reference math_utils.py:40-47 -> cc/math_utils.cc:21-30): 2-D
+    ``r^2 log r`` (0 where r^2 <= 1e-9), 3-D ``-r``.  K x K and M x K on mixture components: host NumPy."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if x.ndim != 2 or y.ndim != 2 or x.shape[1] != y.shape[1]:
+        raise ValueError("x and y must be 2-D with the same number of columns.")
+    if x.shape[1] not in (2, 3):
+        raise ValueError("Invalid dimension of x: %d." % x.shape[1])
+    d2 = np.zeros((x.shape[0], y.shape[0]), dtype=np.float32)
+    for k in range(x.shape[1]):
+        d = x[:, k, None] - y[None, :, k]
+        d2 += d * d
+    if x.shape[1] == 3:
+        return -np.sqrt(d2)
+    out = np.zeros_like(d2)
+    far = d2 > np.float32(1.0e-9)
+    out[far] = d2[far] * np.log(np.sqrt(d2[far]))
+    return out
+
+
 def inverse_multiquadric_kernel(x, y, c=1.0):
     """K_ij = 1 / sqrt(|x_i - y_j|^2 + c) as float32 (reference math_utils.py:50-51 -> cc/math_utils.cc:32-34)."""
     _lib.require_gpu()

@@ -1,4 +1,4 @@
-"""Transformation result types of the registration API (reference probreg/transformation.py:17-102).
+"""Transformation result types of the registration API (reference probreg/transformation.py:17-160).
 
 These are small host-side value objects (a 3x3 matrix, a vector, an M x D weight matrix); the
 per-iteration transform of the *source cloud* inside the EM loop runs fused on the GPU
@@ -123,3 +123,40 @@ class NonRigidTransformation(Transformation):
             disp = self._plan.nonrigid_apply() - self._plan_points.astype(np.float32).astype(np.float64)
             return np.asarray(points) + disp
         return points + np.dot(self.g, self.w)
+
+
+def _tps_kernel(x, y):
+    from . import math_utils as mu
+
+    return mu.tps_kernel(x, y)
+
+
+class TPSTransformation(Transformation):
+    """Thin-plate spline x -> [1 x] a + U(x, control_pts) N v (reference transformation.py:124-160): ``a`` the affine
+    part (dim + 1, dim), ``v`` the warp coefficients (K - dim - 1, dim) in the null space N of [1 control_pts]^T, the
+    result type of ``registration_gmmreg(..., "nonrigid")``."""
+
+    def __init__(self, a, v, control_pts, kernel=_tps_kernel):
+        super(TPSTransformation, self).__init__()
+        self.a = a
+        self.v = v
+        self.control_pts = control_pts
+        self._kernel = kernel
+
+    def prepare(self, landmarks):
+        """(basis (m, K), kernel (K - dim - 1, K - dim - 1)): ``basis @ [a; v]`` moves the landmarks and
+        ``trace(v^T kernel v)`` is the bending energy."""
+        ctrl = self.control_pts
+        m, d = landmarks.shape
+        n = ctrl.shape[0]
+        u, _, _ = np.linalg.svd(np.c_[np.ones((n, 1)), ctrl])
+        null = u[:, d + 1:]
+        basis = np.c_[np.ones((m, 1)), landmarks, np.dot(self._kernel(landmarks, ctrl), null)]
+        return basis, np.dot(null.T, np.dot(self._kernel(ctrl, ctrl), null))
+
+    def transform_basis(self, basis):
+        return np.dot(basis, np.r_[self.a, self.v])
+
+    def _transform(self, points):
+        basis, _ = self.prepare(points)
+        return self.transform_basis(basis)
