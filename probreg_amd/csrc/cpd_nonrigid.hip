@@ -10,15 +10,10 @@
 #include <vector>
 
 #include "cpd_plan.h"
+#include "prg_device.h"
 
 namespace {
 constexpr int kBlock = 256;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // G[i][j] = exp(-|y_i - y_j|^2 / (2 beta)) in float32: squared distance in float32 without FMA
 // contraction (as the reference's Eigen expression), exponential in fp64 rounded once.

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "cpd_plan.h"
+#include "prg_device.h"
 
 namespace {
 
@@ -24,12 +25,6 @@ constexpr int kBlock = 256;
 constexpr int NB = 128;          // Cholesky block size == GEMM tile edge
 constexpr int LDP = NB + 1;      // padded LDS row stride (doubles)
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // ---- right-hand side and S --------------------------------------------------------------------
 // B = px - p1 * y   (cpd.py:296, right-hand side), rows >= m zero.  sp = sqrt(p1).

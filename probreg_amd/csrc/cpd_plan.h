@@ -28,7 +28,7 @@ struct EngineDecision {
 static_assert(sizeof(EngineDecision) % 8 == 0, "the engine state behind EngineDecision needs 8-byte alignment");
 struct EngineArgs {  // host -> k_chunk_meta_bbox, by value
     double ext2;
-    // matrix-core sweeps while they evaluate at least this many pairs per owned point (see estep_impl)
+    // matrix-core sweeps while they evaluate at least this many pairs per owned point (engine_leave_below, cpd_estep.hip)
     double r_col_bound, r_row_bound;  // (r_row_bound: for the lean row pass)
     double r_col_bound_fused;         // ... the dense regime's lower end while the fused single sweep may run (it competes with TWO vector-pipe sweeps)
     double r_row_bound_full;          // ... for the row pass with its residual sums (amplification above the lean factor)
@@ -46,6 +46,46 @@ struct EngineArgs {  // host -> k_chunk_meta_bbox, by value
     unsigned seq;
     EngineDecision* dev;
     EngineDecision* host;
+};
+
+// What the engine switch remembers from one E-step of a registration to the next (host side; EngineDecision::r_col / r_row /
+// row_off are the device's share).  A default-constructed value is "a new registration starts".
+struct EngineSwitch {
+    bool reset = true;       // the device's share is void (new registration, engine mode changed): the next decision starts it afresh
+    bool mfma_off = false;   // this registration has left the dense regime: no more engine decisions
+    int pred_col = 1;        // the column-pass engine the host launches ahead of the decision (= the previous decision)
+    int pred_fine = 0;       // ... and whether that decision had the per-wave tile masks on (0: dense regime -> stream mode)
+    int pred_fused = 0;      // ... the previous E-step ran the fused sweep
+    bool grid_fine = false;  // the previous matrix-core column pass skipped >= 10 % of its pairs: launches are cut into >= 3 rounds of shorter segments
+};
+
+// Environment knobs of the CPD plan, read ONCE per process (prg::cpd_env(), cpd.hip).  Precedence everywhere: the plan's setter,
+// then the environment, then the built-in default.  They exist for A/B measurements (tools/) - the defaults are the product.
+//   PRG_MFMA_SEG          segments of every matrix-core launch (0: fill the chip once; pins mfma_fine_segments and the cost model)
+//   PRG_MFMA_FINE_GRID    =0: never cut a culling matrix-core launch finer (profiles/r4_shard_window.log is the case it fixes)
+//   PRG_ENGINE_RCOL/RROW  > 0: leave the matrix cores below this many evaluated pairs per owned point instead of the cost model's
+//                         bound (engine_leave_below; profiles/r3_engine_switch_*.log, r4_engine_switch_*.log)
+//   PRG_FUSED_RCOL_SCALE  > 0: lower end of the dense regime while a single sweep may run, as a multiple of the column pass' bound
+//                         (fused_lower_bound_scale; profiles/r4_, r5_, r6_fused_lower_bound.log)
+//   PRG_LEAN_FACTOR       >= 0: lean row pass while mean |x|^2 / (sigma2 D) <= this (kLeanFactor; profiles/r4_lean_error_rigid_100k_*.log)
+//   PRG_FUSED_FACTOR      >= 0: replaces prg_cpd_set_fused_factor's value (fused sweep while the amplification is <= this)
+//   PRG_OWNER_SWEEP       =0: no owner sweep (cpd_sweeps_owner.hip): round 5's grid / queue run the single sweep
+//   PRG_DEBUG_ENGINE      set: one line per engine decision on stderr
+//   PRG_SPATIAL_ORDER     morton / kd_host: the Z-curve of rounds 1 - 5 / the host build of the kd-tree order (default: device build)
+// Three more are the defaults of a NEW plan and are read whenever one is created (tests/test_queue_engine_gpu.py changes them
+// between plans of one process), see prg_cpd_create:
+//   PRG_DENSE_ENGINE      prg_cpd_set_dense_engine's mode, clamped to [0, 2]
+//   PRG_SPARSE_ENGINE     prg_cpd_set_sparse_engine's mode, clamped to [0, 2]
+//   PRG_RESID_SWEEP       prg_cpd_set_resid_sweep (A/B runs of the two-sweep sparse regime)
+struct CpdEnv {
+    int mfma_seg = 0;
+    bool fine_grid_off = false;
+    double r_col = 0.0, r_row = 0.0;
+    double fused_rcol_scale = -1.0;
+    double lean_factor = -1.0, fused_factor = -1.0;
+    bool owner_off = false;
+    bool debug_engine = false;
+    std::string spatial_order;
 };
 
 // Work queue of one sparse-regime sweep (cpd_sweeps_queue.hip): 16-bit need-masks per (owned block of 128 points, segment of 16
@@ -127,25 +167,22 @@ struct prg_cpd {
     bool init_rot_orthonormal = true;  // ... only from a rotation: the column-side sums are mapped back through s R
     bool resid_sweep = true;    // ... and, where the column pass runs on the vector pipe, the residual-form single sweep (DESIGN.md 3.1f;
                                 // prg_cpd_set_resid_sweep(0): two sweeps there)
-    int pred_fused = 0;         // the previous E-step ran the fused sweep (what the host launches ahead of the decision)
     bool last_estep_fused = false;
     bool rowacc_valid = false;  // the per-point block (p1, px) holds the last E-step's result (not after a fused sweep)
     float* zchunk = nullptr;    // [Mcap/256][8] box of every 256-point chunk of the transformed source (per E-step)
     float* tchunk = nullptr;    // [Ncap/256][8] box + largest b_n of every 256-point chunk of the target (per E-step)
     int dense_engine = 1;       // 0: VALU sweeps only, 1: matrix-core sweeps in the dense regime,
                                 // 2: both sweeps on the matrix cores, always (tests)
-    double dense_bound = 0.0;    // > 0: matrix-core column pass while it evaluates at least this many source points per target (0: estep_impl's model)
+    double dense_bound = 0.0;    // > 0: matrix-core column pass while it evaluates at least this many source points per target (0: the cost model, engine_leave_below)
     double* tsum_local = nullptr;            // (sum x, sum y, sum z, sum |x|^2) of the local target, beside the decision
     unsigned long long* eng_work = nullptr;  // [2] tiles evaluated by the matrix-core column / row pass (read + cleared by the decision)
+    // (the work queues' memory - q_first_*, q*_live below - is NOT part of the switch's: a sweep over a queue sizes its units from the
+    // previous sweep over that queue, whichever registration ran it)
     int q_first_col = 32, q_first_row = 32;  // groups per unit of the first queue sweep after a matrix-core one
-    bool eng_reset = true;       // the switch's memory is void (new registration, engine mode changed)
-    bool mfma_off = false;      // this registration has left the dense regime: no more engine decisions
+    EngineSwitch eng;            // the engine switch's memory of this registration (prg_cpd_init_params: eng = EngineSwitch())
     EngineDecision* eng_dev = nullptr;   // device copy of the current E-step's decision (guard of the column-pass launches)
     EngineDecision* eng_host = nullptr;  // mapped, coherent host memory: the mailbox the host polls
     EngineDecision* eng_host_dev = nullptr;  // ... as the device addresses it
-    int pred_col = 1;           // the column-pass engine the host launches ahead of the decision (= the previous decision)
-    int pred_fine = 0;          // ... and whether that decision had the per-wave tile masks on (0: dense regime -> stream mode)
-    bool mfma_grid_fine = false; // the previous matrix-core column pass skipped >= 10 % of its pairs: launches are cut into >= 3 rounds of shorter segments
     bool mfma_stream = true;    // dense-regime launches of the matrix-core sweeps are cut in stream mode (prg_cpd_set_stream_mode)
     int mfma_col_planes = 0, mfma_row_planes = 0;  // partial planes the last matrix-core column / row pass wrote (grid or stream mode)
     bool last_estep_row_lean = false;  // ... matrix-core row pass without its residual sums
@@ -218,6 +255,7 @@ namespace prg {
 struct UniqueId { char bytes[PRG_COMM_ID_BYTES]; };  // ncclUniqueId
 int comm_all_reduce_f64(prg_comm* c, double* buf_dev, int64_t count, hipStream_t st);
 int ensure_stage(prg_cpd* h, size_t bytes);
+const CpdEnv& cpd_env();
 // kd-tree order of a cloud built on the device (spatial_order.hip): pts_dev [n][dim] floats in the caller's order -> perm_dev [n]
 int device_kd_order(const float* pts_dev, int64_t n, int dim, int* perm_dev, hipStream_t st, int leaf = 32);
 // non-rigid (cpd_nonrigid.hip)

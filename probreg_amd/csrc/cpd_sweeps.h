@@ -1,4 +1,4 @@
-// Launchers of the two E-step pair sweeps (see cpd.hip header comment).
+// Launchers of the two E-step pair sweeps (see cpd_estep.hip header comment).
 //   packed : explicit float2 (v_pk_*_f32) arithmetic, R = 2 or 4 points per lane
 //   scalar : one fp32 op per pair (translation unit built with -fno-slp-vectorize), for A/B
 //            comparison on hardware; selected by negative R in prg_cpd_set_tuning.

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, FUSED
                                                          float4* __restrict__ corig) {
     __shared__ __attribute__((aligned(16))) float stage[2][kChunkTiles * kTileFloats];
     __shared__ unsigned wave_tiles[kBlock / 64];
-    if (guard) {  // launched ahead of the engine decision (cpd.hip, estep_impl): run only if it came out this way
+    if (guard) {  // launched ahead of the engine decision (cpd_estep.hip, estep_impl): run only if it came out this way
         const bool fused_wanted = guard->col == 1 && guard->fused == 1;
         if (FUSED ? !fused_wanted : (guard->col != 1 || fused_wanted)) return;
         fine = guard->fine;
@@ -888,7 +888,7 @@ int mfma_chunks_per_seg(int64_t owned_points, int64_t streamed_points, int S) {
 }
 
 // Round 4's segment rule (whole rounds of the chip x chunks per workgroup): what the engine switch's cost model was fitted with
-// (cpd.hip: engine_leave_below) - its constants describe launches cut this way, and its bounds are held to measured crossovers
+// (cpd_estep.hip: engine_leave_below) - its constants describe launches cut this way, and its bounds are held to measured crossovers
 // (tests/test_host_logic.py), so the model keeps this rule while the launches themselves follow the simulated schedule above.
 int mfma_chunks_per_seg_model(int64_t owned_points, int64_t streamed_points) {
     const int64_t chunks = ceil_div(streamed_points, kChunk), blocks = ceil_div(owned_points, kWgPoints);

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(kBlock) void k_colpass_cull(const float4* __restric
                                                          const EngineDecision* __restrict__ guard,
                                                          unsigned char* __restrict__ colflag) {
     PRG_TRACE_BEGIN();
-    // launched ahead of the E-step's engine decision (cpd.hip, estep_impl; dense regime only - null afterwards): run
+    // launched ahead of the E-step's engine decision (cpd_estep.hip, estep_impl; dense regime only - null afterwards): run
     // only if the decision names this engine
     if (guard && guard->col != 0) return;
     __shared__ float4 part[RESID ? 1 : 4][64];

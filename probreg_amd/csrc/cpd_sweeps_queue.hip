@@ -14,7 +14,7 @@
 //                   persistent waves (8 per SIMD) take one unit each, then pop further ones with an atomicAdd, and evaluate
 //                   them with the arithmetic of the culled sweeps - every wave busy, eight to a SIMD to hide the scalar
 //                   loads, nobody with more than Q blocks in a row; a unit leaves its partial sums in ITS OWN slot;
-//   consumers       k_colfinal / k_row_moments (cpd.hip) walk a block's chunks and their units IN ORDER and add the slots up.
+//   consumers       k_colfinal / k_row_moments (cpd_estep.hip) walk a block's chunks and their units IN ORDER and add the slots up.
 //
 // Results: the same pairs are evaluated with the same arithmetic as in the culled sweeps; the partials of a block are
 // combined in a fixed order (chunk, then unit) wherever the atomics placed them in the queue, so the sweep is reproducible

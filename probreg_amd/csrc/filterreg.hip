@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "morton.h"
+#include "prg_device.h"
 #include "prg_common.h"
 #include "small_linalg.h"
 
@@ -36,12 +37,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr unsigned long long kEmpty = 0xFFFFFFFFFFFFFFFFull;
 constexpr int kMaxD = 3;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ unsigned long long pack_key(const short* k, int d) {
     unsigned long long r = 0;

@@ -8,6 +8,7 @@
 #include <stdarg.h>
 
 #include "prg_common.h"
+#include "prg_device.h"
 
 namespace prg {
 static thread_local char g_err[512] = "";
@@ -21,12 +22,6 @@ void set_error(const char* fmt, ...) {
 
 namespace {
 constexpr int kBlock = 256;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // partial sums (sum x, sum y, sum z, sum |p|^2) in fp64 over a row-major n x dim float cloud
 __global__ __launch_bounds__(kBlock) void k_sums_rowmajor(const float* __restrict__ p, int64_t n, int dim,

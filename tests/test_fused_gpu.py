@@ -1,5 +1,5 @@
 """The FUSED single sweep of a rigid EM iteration (csrc/cpd_sweeps_mfma.hip k_colpass_mfma<FUSED>,
-csrc/cpd.hip k_colfinal_fused / k_fused_final): while sigma2 is large the rigid M-step's 23 moments (cpd.py:160-192) are
+csrc/cpd_estep.hip k_colfinal_fused / k_fused_final): while sigma2 is large the rigid M-step's 23 moments (cpd.py:160-192) are
 taken from per-column sums of ONE sweep over the pairs instead of a column pass and a row pass.  Held to the two-sweep
 engine from the same state, to the fp64 oracle along registrations (north-star tolerances), and to the error behaviour of
 the interface (no per-point p1 / px after such an E-step)."""

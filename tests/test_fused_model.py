@@ -1,4 +1,4 @@
-"""The algebra of the fused single sweep (csrc/cpd.hip k_colfinal_fused / k_fused_final), in numpy fp64 on the
+"""The algebra of the fused single sweep (csrc/cpd_estep.hip k_colfinal_fused / k_fused_final), in numpy fp64 on the
 CPU: the 23 moments of the rigid M-step (cpd.py:160-192) taken from per-COLUMN sums over the TRANSFORMED source, relative to
 per-block origins and with per-column exponent offsets, mapped back to the source's own frame - against the same moments taken
 the reference's way (rows of P, cpd.py:84-88, 169-183), and the M-step that follows against the oracle's."""

@@ -1,5 +1,5 @@
 """The residual-form single sweep of a rigid EM iteration on the VECTOR pipe (csrc/cpd_sweeps_packed.hip
-k_colpass_cull<true>, csrc/cpd_sweeps_queue.hip k_colpass_queue<true>, csrc/cpd.hip k_colfinal_resid / k_fused_final): below the
+k_colpass_cull<true>, csrc/cpd_sweeps_queue.hip k_colpass_queue<true>, csrc/cpd_estep.hip k_colfinal_resid / k_fused_final): below the
 dense regime the rigid M-step's moments (cpd.py:160-192) come from per-column sums A = sum K, U = sum K (x - z), R = sum K |x - z|^2
 of ONE culled sweep instead of a column pass and a row pass.  Held to the two-sweep engine from the same state (grid of culled
 waves and work queue), to the fp64 oracle along whole registrations into the deep sparse regime (north-star tolerances), on
