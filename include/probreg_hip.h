@@ -479,6 +479,42 @@ int prg_gmmfit_em(prg_gmmfit* h, double tol, int max_iter, double reg_covar, int
  * lloyd only the centres (means) exist. */
 int prg_gmmfit_get_params(prg_gmmfit* h, double* weights_host, double* means_host, double* covariances_host);
 
+/* ---- One-class nu-SVM with the RBF kernel (the feature generator of SVR, probreg/features.py:72-100) ---------------
+ * features.OneClassSVM.compute calls scikit-learn's svm.OneClassSVM(nu, kernel = "rbf", gamma).fit (libsvm); these
+ * entry points solve the same dual in fp64 on the device, in libsvm's scaling: minimise 1/2 a'Qa subject to
+ * 0 <= a_i <= 1 and sum a_i = nu n, with Q_ij = exp(-gamma |x_i - x_j|^2).  Working-set decomposition (csrc/ocsvm.hip);
+ * two solves of the same input give byte-identical results (fixed-order reductions, no floating-point atomics). */
+typedef struct prg_ocsvm prg_ocsvm;
+/* One solver context on one device / stream (features.OneClassSVM.init, features.py:91-92, creates the estimator). */
+int prg_ocsvm_create(prg_ocsvm** out, int device, void* hip_stream);
+int prg_ocsvm_destroy(prg_ocsvm* h);
+/* Points per working set (no counterpart in scikit-learn: libsvm works on pairs).  Needs no device. */
+int prg_ocsvm_working_set_size(int* q_host);
+/* The cloud of `self._clf.fit(data)` (features.py:95): n x dim float64, dim 2 or 3, finite, uploaded once. */
+int prg_ocsvm_set_data(prg_ocsvm* h, const double* data_hd, int64_t n, int dim);
+/* The fit itself (libsvm solve_one_class / Solver::Solve): from libsvm's start (the first floor(nu n) points at the
+ * bound), rounds of working-set selection, second-order SMO on the set (at most inner_cap steps) and gradient update,
+ * until the maximal KKT violation m - M < tol (scikit-learn's `tol`, default 1e-3) or max_iter rounds are done
+ * (scikit-learn's `max_iter` counts single SMO steps instead).  gamma > 0, 0 < nu <= 1.  n_iter_host: rounds that
+ * changed a; n_inner_host (may be NULL): SMO steps of all rounds; converged_host: 0 when max_iter ended the loop (the
+ * solution is feasible all the same, as with libsvm's warning); gap_host: m - M of the returned solution (-inf when
+ * every a is at the upper bound). */
+int prg_ocsvm_solve(prg_ocsvm* h, double gamma, double nu, double tol, int max_iter, int inner_cap, int* n_iter_host,
+                    int* n_inner_host, int* converged_host, double* gap_host);
+/* The solution: alpha_host[n] (dense; scikit-learn's dual_coef_ is its non-zero part), rho (scikit-learn's offset_),
+ * the objective 1/2 a'Qa and the number of support vectors; each pointer may be NULL. */
+int prg_ocsvm_get_solution(prg_ocsvm* h, double* alpha_host, double* rho_host, double* objective_host,
+                           int* n_support_host);
+/* scikit-learn's support_: the indices with a_i > 0, ascending. */
+int prg_ocsvm_get_support(prg_ocsvm* h, int* index_host);
+/* sum_i a_i exp(-gamma |x_i - p|^2) at k points (k x dim float64, host or device) with the gamma of the last solve:
+ * scikit-learn's score_samples; decision_function is this minus rho.  Synchronises. */
+int prg_ocsvm_decision(prg_ocsvm* h, const double* points_hd, int64_t k, double* out_hd);
+/* Timing split for tools (no counterpart): with profile on, a solve records device milliseconds of
+ * ms4_host = (initial gradient, selection, subproblem, gradient sweep) summed over its rounds. */
+int prg_ocsvm_set_profile(prg_ocsvm* h, int on);
+int prg_ocsvm_get_profile(prg_ocsvm* h, double* ms4_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,16 @@ SIGNATURES = {
     "prg_gmmfit_set_params": [_vp, _i, _vp, _vp, _vp],
     "prg_gmmfit_em": [_vp, _d, _i, _d, _c.POINTER(_i), _c.POINTER(_i), _vp],
     "prg_gmmfit_get_params": [_vp, _vp, _vp, _vp],
+    "prg_ocsvm_create": [_pp, _i, _vp],
+    "prg_ocsvm_destroy": [_vp],
+    "prg_ocsvm_working_set_size": [_c.POINTER(_i)],
+    "prg_ocsvm_set_data": [_vp, _vp, _i64, _i],
+    "prg_ocsvm_solve": [_vp, _d, _d, _d, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_d)],
+    "prg_ocsvm_get_solution": [_vp, _vp, _c.POINTER(_d), _c.POINTER(_d), _c.POINTER(_i)],
+    "prg_ocsvm_get_support": [_vp, _vp],
+    "prg_ocsvm_decision": [_vp, _vp, _i64, _vp],
+    "prg_ocsvm_set_profile": [_vp, _i],
+    "prg_ocsvm_get_profile": [_vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

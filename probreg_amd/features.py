@@ -15,7 +15,8 @@ Differences a caller can see (on purpose):
     (DESIGN.md).
   * ``weights_init``, ``means_init`` and ``precisions_init`` are given together or not at all; given, EM starts from
     them and reproduces scikit-learn's result to rounding.
-  * Clouds of dimension 2 or 3.  ``FPFH`` and ``OneClassSVM`` are not provided.
+  * Clouds of dimension 2 or 3.  ``FPFH`` is not provided.  The reference's third generator, ``OneClassSVM``, is
+    provided in ``probreg_amd.svm`` and not under this module's name.
 """
 import abc
 import ctypes

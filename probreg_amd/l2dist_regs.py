@@ -1,16 +1,20 @@
-"""GMMReg: registration by the L2 distance between Gaussian mixtures - drop-in for the GMMReg half of
-``probreg.l2dist_regs`` (reference probreg/l2dist_regs.py:16-118, 158-181; Jian & Vemuri, "Robust Point Set Registration
-Using Gaussian Mixture Models", PAMI 2011).
+"""GMMReg and SVR: registration by the L2 distance between Gaussian mixtures - drop-in for ``probreg.l2dist_regs``
+(reference probreg/l2dist_regs.py; Jian & Vemuri, "Robust Point Set Registration Using Gaussian Mixture Models", PAMI
+2011; Campbell & Petersson, "An Adaptive Data Representation for Robust Point-Set Registration and Merging", ICCV 2015).
 
 What runs where
   * The mixture fit of both clouds (``features.GMM``; the reference calls scikit-learn, and that fit dominates): HIP,
     ``prg_gmmfit_*``.
+  * The one-class SVM fit of both clouds (``svm.OneClassSVM``; the reference calls scikit-learn / libsvm): HIP,
+    ``prg_ocsvm_*``.
   * Every BFGS evaluation's Gauss transforms over the K x K component pairs (``cost_functions.compute_l2_dist``): HIP.
   * The optimiser itself, ``scipy.optimize.minimize(method="BFGS", jac=True)`` on 7 (rigid) or K * dim (thin-plate
     spline) unknowns, and the small algebra of the cost functions: host, as in the reference.
 
-``L2DistRegistration`` is generic in its feature generator and cost function; the support-vector variants of the
-reference (``RigidSVR``, ``TPSSVR``, ``registration_svr``) need a one-class SVM solver and are not provided.
+``L2DistRegistration`` is generic in its feature generator and cost function: GMMReg (``RigidGMMReg``, ``TPSGMMReg``,
+``registration_gmmreg``) feeds it mixture centres and weights, SVR (``RigidSVR``, ``TPSSVR``, ``registration_svr``) the
+support vectors and scaled dual coefficients of a one-class SVM.  The SVM feature generator is ``probreg_amd.svm.OneClassSVM``
+(the reference keeps it in ``features``).
 """
 import logging
 
@@ -20,6 +24,7 @@ from scipy.optimize import minimize
 from . import cost_functions as cf
 from . import features as ft
 from .cpd import _as_points
+from .svm import OneClassSVM
 from .log import log
 
 
@@ -122,6 +127,39 @@ class TPSGMMReg(L2DistRegistration):
         self._cost_fn._control_pts = control_pts
 
 
+class RigidSVR(L2DistRegistration):
+    """Support-vector registration with a rigid motion (l2dist_regs.py:121-135).  ``_estimate_sigma`` also hands the
+    estimated scale to the feature generator (its ``_sigma``, and ``_gamma = 1 / (2 sigma^2)``); the annealing of the
+    driver's ``sigma`` does not reach it.  Extension: ``svm_params`` (extra keywords of ``svm.OneClassSVM``)."""
+
+    def __init__(self, source, sigma=1.0, delta=0.9, gamma=0.5, nu=0.1, use_estimated_sigma=True, svm_params={}):
+        super(RigidSVR, self).__init__(source, OneClassSVM(source.shape[1], sigma, gamma, nu, **svm_params),
+                                       cf.RigidCostFunction(), sigma, delta, use_estimated_sigma)
+
+    def _estimate_sigma(self, data):
+        super(RigidSVR, self)._estimate_sigma(data)
+        self._feature_gen._sigma = self._sigma
+        self._feature_gen._gamma = 1.0 / (2.0 * np.square(self._sigma))
+
+
+class TPSSVR(L2DistRegistration):
+    """Support-vector registration with a thin-plate spline whose control points are the source's support vectors
+    (l2dist_regs.py:138-155).  ``svm_params``: extra keywords of ``svm.OneClassSVM``."""
+
+    def __init__(self, source, sigma=1.0, delta=0.9, gamma=0.5, nu=0.1, alpha=1.0, beta=0.1, use_estimated_sigma=True,
+                 svm_params={}):
+        super(TPSSVR, self).__init__(source, OneClassSVM(source.shape[1], sigma, gamma, nu, **svm_params),
+                                     cf.TPSCostFunction([], alpha, beta), sigma, delta, use_estimated_sigma)
+        self._feature_gen.init()
+        control_pts, _ = self._feature_gen.compute(source)
+        self._cost_fn._control_pts = control_pts
+
+    def _estimate_sigma(self, data):
+        super(TPSSVR, self)._estimate_sigma(data)
+        self._feature_gen._sigma = self._sigma
+        self._feature_gen._gamma = 1.0 / (2.0 * np.square(self._sigma))
+
+
 def registration_gmmreg(source, target, tf_type_name="rigid", callbacks=[], **kargs):
     """GMMReg with the reference's signature (l2dist_regs.py:158-181).
 
@@ -139,3 +177,25 @@ def registration_gmmreg(source, target, tf_type_name="rigid", callbacks=[], **ka
         raise ValueError("Unknown transform type %s" % tf_type_name)
     gmmreg.set_callbacks(callbacks)
     return gmmreg.registration(_as_points(target))
+
+
+def registration_svr(source, target, tf_type_name="rigid", maxiter=1, tol=1.0e-3, opt_maxiter=50, opt_tol=1.0e-3,
+                     callbacks=[], **kwargs):
+    """Support-vector registration with the reference's signature (l2dist_regs.py:184-219).
+
+    source, target : (n, dim) arrays or anything with ``.points`` (Open3D point clouds)
+    tf_type_name   : 'rigid' or 'nonrigid' (thin-plate spline)
+    maxiter, tol   : rounds of the outer loop and its stop tolerance on the cost
+    opt_maxiter, opt_tol : BFGS iterations per round and their tolerance
+    callbacks      : called after each BFGS iteration with the current transformation
+    **kwargs       : keywords of :class:`RigidSVR` / :class:`TPSSVR`
+    Returns the transformation from source to target.
+    """
+    if tf_type_name == "rigid":
+        svr = RigidSVR(_as_points(source), **kwargs)
+    elif tf_type_name == "nonrigid":
+        svr = TPSSVR(_as_points(source), **kwargs)
+    else:
+        raise ValueError("Unknown transform type %s" % tf_type_name)
+    svr.set_callbacks(callbacks)
+    return svr.registration(_as_points(target), maxiter, tol, opt_maxiter, opt_tol)
