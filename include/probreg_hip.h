@@ -515,6 +515,39 @@ int prg_ocsvm_decision(prg_ocsvm* h, const double* points_hd, int64_t k, double*
 int prg_ocsvm_set_profile(prg_ocsvm* h, int on);
 int prg_ocsvm_get_profile(prg_ocsvm* h, double* ms4_host);
 
+/* ---- FPFH descriptor (probreg/features.py:28-51, which calls Open3D) ---------------------------------------------
+ * features.FPFH.compute calls Open3D's estimate_normals(KDTreeSearchParamHybrid) and compute_fpfh_feature; these entry
+ * points restate both in fp64 on the device, one stage per call (csrc/fpfh.hip; the definition with every tie rule is
+ * DESIGN.md section 3.9).  Two runs on the same input give byte-identical results (no floating-point atomics). */
+typedef struct prg_fpfh prg_fpfh;
+/* One descriptor context on one device / stream (features.FPFH.__init__, features.py:36-38, builds the search parameters). */
+int prg_fpfh_create(prg_fpfh** out, int device, void* hip_stream);
+int prg_fpfh_destroy(prg_fpfh* h);
+/* Longest neighbour list a search can return (no counterpart: Open3D's max_nn is unbounded).  Needs no device. */
+int prg_fpfh_max_nn(int* max_nn_host);
+/* The cloud `pcd.points` (features.py:47-48): n x 3 float64, finite, host or device, uploaded once. */
+int prg_fpfh_set_data(prg_fpfh* h, const double* points_hd, int64_t n);
+/* Open3D's KDTreeSearchParamHybrid(radius, max_nn) for every point: which = 0 keeps the lists of the normals
+ * (features.py:37), which = 1 those of the histograms (features.py:38).  A list is the point itself, then the other
+ * points with d2 <= radius^2 by ascending (d2, index), cut to max_nn entries; 1 <= max_nn <= prg_fpfh_max_nn. */
+int prg_fpfh_search(prg_fpfh* h, int which, double radius, int max_nn);
+/* The lists of a search: idx_host / d2_host are n x max_nn (unused entries -1 / 0), count_host n; each may be NULL. */
+int prg_fpfh_get_neighbours(prg_fpfh* h, int which, int* idx_host, double* d2_host, int* count_host);
+/* estimate_normals (features.py:43-44) on the lists of search 0: unit eigenvector of the smallest eigenvalue of the
+ * population covariance of the listed points, largest component positive; (0, 0, 1) for fewer than 3 entries. */
+int prg_fpfh_normals(prg_fpfh* h);
+/* Caller-supplied normals instead (a cloud that arrives with normals): n x 3 float64, host or device. */
+int prg_fpfh_set_normals(prg_fpfh* h, const double* normals_hd);
+int prg_fpfh_get_normals(prg_fpfh* h, double* normals_host);
+/* The simplified point feature histograms over the lists of search 1 (first half of compute_fpfh_feature, features.py:50):
+ * n x 33, every 11-bin group of a row with neighbours sums to 100. */
+int prg_fpfh_spfh(prg_fpfh* h);
+int prg_fpfh_get_spfh(prg_fpfh* h, double* spfh_host);
+/* The descriptor (second half of compute_fpfh_feature): the neighbours' SPFH rows weighted by 1 / d2, every group scaled
+ * to sum 100, plus the point's own SPFH row; n x 33 (Open3D's `.data` is the transpose, features.py:51 transposes back). */
+int prg_fpfh_fpfh(prg_fpfh* h);
+int prg_fpfh_get_fpfh(prg_fpfh* h, double* fpfh_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,19 @@ SIGNATURES = {
     "prg_ocsvm_decision": [_vp, _vp, _i64, _vp],
     "prg_ocsvm_set_profile": [_vp, _i],
     "prg_ocsvm_get_profile": [_vp, _vp],
+    "prg_fpfh_create": [_pp, _i, _vp],
+    "prg_fpfh_destroy": [_vp],
+    "prg_fpfh_max_nn": [_c.POINTER(_i)],
+    "prg_fpfh_set_data": [_vp, _vp, _i64],
+    "prg_fpfh_search": [_vp, _i, _d, _i],
+    "prg_fpfh_get_neighbours": [_vp, _i, _vp, _vp, _vp],
+    "prg_fpfh_normals": [_vp],
+    "prg_fpfh_set_normals": [_vp, _vp],
+    "prg_fpfh_get_normals": [_vp, _vp],
+    "prg_fpfh_spfh": [_vp],
+    "prg_fpfh_get_spfh": [_vp, _vp],
+    "prg_fpfh_fpfh": [_vp],
+    "prg_fpfh_get_fpfh": [_vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

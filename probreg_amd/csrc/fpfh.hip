@@ -1,0 +1,757 @@
+// FPFH descriptor (Rusu et al. 2009) as the reference gets it from Open3D for `feature_fn` of FilterReg: a hybrid
+// (radius + max_nn) neighbour search, PCA normals, the simplified point feature histograms and their 1 / d^2 weighted
+// gather.  Everything in fp64; DESIGN.md section 3.9 is the definition with every tie rule.  One stage per entry point:
+//
+//   grid     cell edge = search radius.  Cell coordinates are clamped to [0, 2^30); the cell key is the row-major index
+//            while the whole box has at most `table` cells and a multiplicative hash of the coordinates into `table`
+//            buckets otherwise, so a far outlier costs no memory.  table = the power of two >= 2 n in [2^10, 2^26].
+//            Points are sorted by key (stable radix sort: ascending point index inside a bucket) and gathered, buckets
+//            get (begin, end).  A bucket may hold several cells; the search filters by distance, so that only costs time.
+//   search   one wave per query.  The cells that meet [p - r, p + r] (2 to 4 per axis) are dealt to the lanes, keys that
+//            repeat (hash collisions) are dropped, then the wave walks the buckets 64 candidates at a time.  Pass 1 counts
+//            the candidates.  If they do not fit the list, an MSB-first radix select (8 bits per pass, 256 counters in
+//            LDS) over the 96-bit key (bits of d2, point index) finds the key of the last entry that fits - non-negative
+//            doubles order as their bit patterns - recomputing d2 in every pass instead of storing candidates, so any
+//            number of candidates is handled in constant space.  The last pass compacts the entries at or below that
+//            key into LDS, a rank sort puts them into (d2, index) order behind the query itself.
+//   normals  one wave per point: the list is rank-sorted by point index into LDS, then mean and centred products are
+//            summed in that order (two passes), so equal neighbour sets give bit-identical normals; cyclic Jacobi on
+//            the symmetric 3 x 3 covariance.
+//   spfh     one wave per point: a lane per neighbour computes the pair feature and its three bins into LDS, then lane
+//            b counts bin b over the list; the row is 100 count / (L - 1).  No atomics.
+//   fpfh     one wave per point, lane b owns bin b and walks the stored list in list order.
+// Two runs on the same input give byte-identical results: the only atomics are integer counters of the radix select.
+//
+// d2 and every other decision value is computed with separately rounded multiplications and additions (no contraction
+// into FMAs), so that a restatement in plain IEEE arithmetic takes the same branches.
+#pragma clang fp contract(off)
+#include <math.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <limits>
+#include <new>
+#include <vector>
+
+#include "prg_common.h"
+
+namespace prg {
+int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
+                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream);  // lattice_sort.hip
+}
+
+namespace {
+
+constexpr int kWave = 64;              // every per-point kernel is one wave per workgroup: __syncthreads is wave-local
+constexpr int kBlock = 256;            // point-parallel helper kernels
+constexpr int kMaxNN = 512;            // longest neighbour list (LDS of the search, normals and spfh kernels)
+constexpr int kBins = 33;              // 3 groups of 11
+constexpr double kCellMax = 1073741823.0;  // cell coordinates are clamped to [0, 2^30)
+constexpr double kReach = 1.0 + 1.0e-12;   // the scanned box is a hair wider than r: covers the rounding of d2 <= r * r
+constexpr unsigned kMinTableBits = 10, kMaxTableBits = 26;
+
+struct Grid {
+    double lo[3];
+    double edge;
+    int dim[3];
+    unsigned mask;  // table - 1
+    int dense;
+};
+
+// Monotone in x, clamped: neighbours within one edge stay within one cell whatever the magnitudes.
+__host__ __device__ inline int cell_of(double x, double lo, double edge) {
+    double c = floor((x - lo) / edge);
+    c = c > 0.0 ? c : 0.0;  // (also NaN -> 0)
+    c = c < kCellMax ? c : kCellMax;
+    return (int)c;
+}
+
+__device__ inline unsigned cell_key(int cx, int cy, int cz, const Grid& g) {
+    if (g.dense) return ((unsigned)cz * (unsigned)g.dim[1] + (unsigned)cy) * (unsigned)g.dim[0] + (unsigned)cx;
+    // Teschner et al. 2003, "Optimized spatial hashing for collision detection of deformable objects"
+    const uint64_t h = ((uint64_t)cx * 73856093ull) ^ ((uint64_t)cy * 19349663ull) ^ ((uint64_t)cz * 83492791ull);
+    return (unsigned)(h ^ (h >> 29)) & g.mask;
+}
+
+__global__ __launch_bounds__(kBlock) void k_cell_keys(const double4* __restrict__ pts, int n, Grid g,
+                                                      unsigned* __restrict__ keys, int* __restrict__ vals) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const double4 p = pts[t];
+    keys[t] = cell_key(cell_of(p.x, g.lo[0], g.edge), cell_of(p.y, g.lo[1], g.edge), cell_of(p.z, g.lo[2], g.edge), g);
+    vals[t] = t;
+}
+
+// sorted points with the point index in .w, and (begin, end) of every bucket (both zeroed before)
+__global__ __launch_bounds__(kBlock) void k_cell_bounds(const double4* __restrict__ pts, const unsigned* __restrict__ skeys,
+                                                        const int* __restrict__ order, int n, double4* __restrict__ sp,
+                                                        int* __restrict__ cbegin, int* __restrict__ cend) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const int i = order[t];
+    double4 p = pts[i];
+    p.w = (double)i;
+    sp[t] = p;
+    const unsigned key = skeys[t];
+    if (t == 0 || skeys[t - 1] != key) cbegin[key] = t;
+    if (t == n - 1 || skeys[t + 1] != key) cend[key] = t + 1;
+}
+
+__device__ inline int wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The 96-bit sort key (k1 = bits of d2, k0 = point index), 8 bits at a time; s is the bit offset of the digit.
+__device__ inline unsigned key_digit(uint64_t k1, unsigned k0, int s) {
+    return s >= 32 ? (unsigned)(k1 >> (s - 32)) & 255u : (k0 >> s) & 255u;
+}
+__device__ inline bool key_prefix_match(uint64_t k1, unsigned k0, uint64_t p1, unsigned p0, int s) {
+    if (s >= 32) {
+        const int sh = s - 32 + 8;
+        return sh >= 64 || (k1 >> sh) == (p1 >> sh);
+    }
+    return k1 == p1 && (s + 8 >= 32 || (k0 >> (s + 8)) == (p0 >> (s + 8)));
+}
+__device__ inline bool key_le(uint64_t k1, unsigned k0, uint64_t t1, unsigned t0) {
+    return k1 < t1 || (k1 == t1 && k0 <= t0);
+}
+
+// Calls f(valid, j, d2) in every lane for every 64 candidates of the buckets (my_b, my_e) of lanes 0 .. ncell - 1;
+// valid: a point other than the query within the radius.  All loop bounds are wave-uniform.
+template <class F>
+__device__ inline void for_candidates(const double4* __restrict__ sp, int my_b, int my_e, int ncell, const double4 p,
+                                      int self, double r2, F&& f) {
+    const int lane = threadIdx.x;
+    for (int c = 0; c < ncell; ++c) {
+        const int b = __shfl(my_b, c, 64), e = __shfl(my_e, c, 64);
+        for (int t0 = b; t0 < e; t0 += kWave) {
+            const int t = t0 + lane;
+            bool v = t < e;
+            int j = -1;
+            double d2 = 0.0;
+            if (v) {
+                const double4 q = sp[t];
+                j = (int)q.w;
+                const double dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+                d2 = dx * dx + dy * dy + dz * dz;
+                v = d2 <= r2 && j != self;
+            }
+            f(v, j, d2);
+        }
+    }
+}
+
+// One wave per query (workgroup q handles the q-th point in cell order).  Row `self` of out_idx / out_d2 (k entries) gets
+// the query first, then its neighbours by ascending (d2, index), cut to k; unused entries are (-1, 0).
+__global__ __launch_bounds__(kWave) void k_search(const double4* __restrict__ sp, const int* __restrict__ cbegin,
+                                                  const int* __restrict__ cend, Grid g, double r, int k,
+                                                  int* __restrict__ out_idx, double* __restrict__ out_d2,
+                                                  int* __restrict__ out_cnt) {
+    __shared__ int hist[256];
+    __shared__ double l_d2[kMaxNN];
+    __shared__ int l_j[kMaxNN];
+    const int lane = threadIdx.x;
+    const double4 p = sp[blockIdx.x];
+    const int self = (int)p.w;
+    const double r2 = r * r, reach = r * kReach;
+
+    // the cells that meet [p - reach, p + reach], dealt to the lanes
+    const double pc[3] = {p.x, p.y, p.z};
+    int c0[3], nc[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        int lo = cell_of(pc[a] - reach, g.lo[a], g.edge), hi = cell_of(pc[a] + reach, g.lo[a], g.edge);
+        lo = min(lo, g.dim[a] - 1);
+        hi = min(min(hi, g.dim[a] - 1), lo + 3);
+        c0[a] = lo;
+        nc[a] = hi - lo + 1;  // 1 .. 4
+    }
+    const int ncell = nc[0] * nc[1] * nc[2];  // <= 64
+    unsigned key = 0;
+    if (lane < ncell)
+        key = cell_key(c0[0] + lane % nc[0], c0[1] + (lane / nc[0]) % nc[1], c0[2] + lane / (nc[0] * nc[1]), g);
+    bool dup = false;  // a bucket is walked once, however many of the cells hash to it
+    for (int c = 0; c < ncell; ++c) {
+        const unsigned kc = __shfl(key, c, 64);
+        dup = dup || (c < lane && kc == key);
+    }
+    const bool live = lane < ncell && !dup;
+    const int my_b = live ? cbegin[key] : 0, my_e = live ? cend[key] : 0;
+
+    int cand = 0;
+    for_candidates(sp, my_b, my_e, ncell, p, self, r2, [&](bool v, int, double) { cand += v ? 1 : 0; });
+    cand = wave_sum(cand);
+
+    const int need = k - 1;
+    uint64_t t1 = ~0ull;  // threshold key: everything at or below it is listed
+    unsigned t0 = ~0u;
+    if (cand > need && need > 0) {
+        uint64_t p1 = 0;
+        unsigned p0 = 0;
+        int remaining = need;  // entries still to take from the keys that share the prefix
+        for (int s = 88; s >= 0; s -= 8) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) hist[4 * lane + q] = 0;
+            __syncthreads();
+            for_candidates(sp, my_b, my_e, ncell, p, self, r2, [&](bool v, int j, double d2) {
+                const uint64_t k1 = (uint64_t)__double_as_longlong(d2);
+                if (v && key_prefix_match(k1, (unsigned)j, p1, p0, s)) atomicAdd(&hist[key_digit(k1, (unsigned)j, s)], 1);
+            });
+            __syncthreads();
+            const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+            const int tot = h0 + h1 + h2 + h3;
+            int inc = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int up = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += up;
+            }
+            const int exc = inc - tot;
+            const bool mine = exc < remaining && remaining <= inc;  // exactly one lane
+            int bin = 0, below = 0, hb = 0;
+            if (mine) {
+                if (exc + h0 >= remaining) { bin = 4 * lane; below = exc; hb = h0; }
+                else if (exc + h0 + h1 >= remaining) { bin = 4 * lane + 1; below = exc + h0; hb = h1; }
+                else if (exc + h0 + h1 + h2 >= remaining) { bin = 4 * lane + 2; below = exc + h0 + h1; hb = h2; }
+                else { bin = 4 * lane + 3; below = exc + h0 + h1 + h2; hb = h3; }
+            }
+            const unsigned long long mm = __ballot(mine);
+            const int src = mm ? __ffsll(mm) - 1 : 0;
+            bin = __shfl(bin, src, 64);
+            below = __shfl(below, src, 64);
+            hb = __shfl(hb, src, 64);
+            remaining -= below;
+            if (s >= 32) p1 |= (uint64_t)bin << (s - 32);
+            else p0 |= (unsigned)bin << s;
+            if (hb == remaining || s == 0) {  // the whole bin is taken: every lower bit of the threshold is one
+                if (s >= 32) { p1 |= (1ull << (s - 32)) - 1ull; p0 = ~0u; }
+                else p0 |= (1u << s) - 1u;
+                break;
+            }
+        }
+        t1 = p1;
+        t0 = p0;
+    }
+
+    int m = 0;
+    if (need > 0) {
+        for_candidates(sp, my_b, my_e, ncell, p, self, r2, [&](bool v, int j, double d2) {
+            const bool take = v && key_le((uint64_t)__double_as_longlong(d2), (unsigned)j, t1, t0);
+            const unsigned long long mask = __ballot(take);
+            const int pos = m + __popcll(mask & ((1ull << lane) - 1ull));
+            if (take && pos < kMaxNN) { l_d2[pos] = d2; l_j[pos] = j; }
+            m += __popcll(mask);
+        });
+        m = min(m, need);
+    }
+    __syncthreads();
+
+    const size_t base = (size_t)self * (size_t)k;
+    for (int e = lane; e < m; e += kWave) {
+        const double de = l_d2[e];
+        const int je = l_j[e];
+        int rank = 0;
+        for (int f = 0; f < m; ++f) {
+            const double df = l_d2[f];
+            rank += (df < de || (df == de && l_j[f] < je)) ? 1 : 0;
+        }
+        out_idx[base + 1 + rank] = je;
+        out_d2[base + 1 + rank] = de;
+    }
+    for (int e = m + 1 + lane; e < k; e += kWave) {
+        out_idx[base + e] = -1;
+        out_d2[base + e] = 0.0;
+    }
+    if (lane == 0) {
+        out_idx[base] = self;
+        out_d2[base] = 0.0;
+        out_cnt[self] = m + 1;
+    }
+}
+
+// Eigenvector of the smallest eigenvalue of the symmetric matrix (xx, xy, xz, yy, yz, zz): cyclic Jacobi with
+// compile-time indices only (small_linalg.h: a run-time index would move the arrays to scratch memory).
+__device__ inline void smallest_eigenvector(const double c[6], double nrm[3]) {
+    double a[3][3] = {{c[0], c[1], c[2]}, {c[1], c[3], c[4]}, {c[2], c[4], c[5]}};
+    double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    const double scale = fmax(fabs(a[0][0]), fmax(fabs(a[1][1]), fabs(a[2][2])));
+    for (int sweep = 0; sweep < 30 && scale > 0.0; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double apq = a[p][q];
+                if (fabs(apq) <= 1.0e-20 * scale) {
+                    a[p][q] = a[q][p] = 0.0;
+                    continue;
+                }
+                rotated = true;
+                const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+                a[p][p] -= t * apq;
+                a[q][q] += t * apq;
+                a[p][q] = a[q][p] = 0.0;
+                const int r = 3 - p - q;  // the third index (compile-time after unrolling)
+                const double arp = a[r][p], arq = a[r][q];
+                a[r][p] = a[p][r] = cs * arp - sn * arq;
+                a[r][q] = a[q][r] = sn * arp + cs * arq;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const double vp = V[i][p], vq = V[i][q];
+                    V[i][p] = cs * vp - sn * vq;
+                    V[i][q] = sn * vp + cs * vq;
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+    int col = 0;  // smallest eigenvalue, ties to the lowest column
+    if (a[1][1] < a[0][0]) col = 1;
+    if (a[2][2] < (col == 1 ? a[1][1] : a[0][0])) col = 2;
+    double v[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) v[i] = col == 0 ? V[i][0] : (col == 1 ? V[i][1] : V[i][2]);
+    const double inv = 1.0 / sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    const double a0 = fabs(v[0]), a1 = fabs(v[1]), a2 = fabs(v[2]);
+    const double lead = (a0 >= a1 && a0 >= a2) ? v[0] : (a1 >= a2 ? v[1] : v[2]);  // largest magnitude, ties: lowest axis
+    const double sgn = lead < 0.0 ? -inv : inv;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) nrm[i] = v[i] * sgn;
+}
+
+__global__ __launch_bounds__(kWave) void k_normals(const double4* __restrict__ pts, const int* __restrict__ idx,
+                                                   const int* __restrict__ cnt, int k, double* __restrict__ normals) {
+    __shared__ int s_idx[kMaxNN];
+    __shared__ double s_p[kMaxNN][3];
+    const int lane = threadIdx.x;
+    const size_t i = blockIdx.x;
+    const int L = min(cnt[i], min(k, kMaxNN));
+    if (L < 3) {
+        if (lane < 3) normals[i * 3 + lane] = lane == 2 ? 1.0 : 0.0;
+        return;
+    }
+    for (int e = lane; e < L; e += kWave) s_idx[e] = idx[i * k + e];
+    __syncthreads();
+    for (int e = lane; e < L; e += kWave) {  // ascending point index (the indices of a list are distinct)
+        const int je = s_idx[e];
+        int rank = 0;
+        for (int f = 0; f < L; ++f) rank += s_idx[f] < je ? 1 : 0;
+        const double4 q = pts[je];
+        s_p[rank][0] = q.x;
+        s_p[rank][1] = q.y;
+        s_p[rank][2] = q.z;
+    }
+    __syncthreads();
+    // every lane runs the same sequential sums (LDS broadcasts); lane 0 stores
+    double mx = 0.0, my = 0.0, mz = 0.0;
+    for (int e = 0; e < L; ++e) {
+        mx += s_p[e][0];
+        my += s_p[e][1];
+        mz += s_p[e][2];
+    }
+    const double cntd = (double)L;
+    mx /= cntd;
+    my /= cntd;
+    mz /= cntd;
+    double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int e = 0; e < L; ++e) {
+        const double dx = s_p[e][0] - mx, dy = s_p[e][1] - my, dz = s_p[e][2] - mz;
+        c[0] += dx * dx;
+        c[1] += dx * dy;
+        c[2] += dx * dz;
+        c[3] += dy * dy;
+        c[4] += dy * dz;
+        c[5] += dz * dz;
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) c[q] /= cntd;
+    double nrm[3];
+    smallest_eigenvector(c, nrm);
+    if (lane == 0) {
+        normals[i * 3 + 0] = nrm[0];
+        normals[i * 3 + 1] = nrm[1];
+        normals[i * 3 + 2] = nrm[2];
+    }
+}
+
+__device__ inline int bin11(double x) {  // floor, clamped to the group's 0 .. 10
+    const double b = floor(x);
+    return !(b > 0.0) ? 0 : (b > 10.0 ? 10 : (int)b);
+}
+
+// The three bins of the pair feature of (p1, n1), (p2, n2).
+__device__ inline void pair_bins(const double4 p1, const double* n1, const double4 p2, const double* n2, int bins[3]) {
+    double f1 = 0.0, f2 = 0.0, f3 = 0.0;
+    double dx = p2.x - p1.x, dy = p2.y - p1.y, dz = p2.z - p1.z;
+    const double rho = sqrt(dx * dx + dy * dy + dz * dz);
+    if (rho != 0.0) {
+        const double a1 = (n1[0] * dx + n1[1] * dy + n1[2] * dz) / rho;
+        const double a2 = (n2[0] * dx + n2[1] * dy + n2[2] * dz) / rho;
+        double ax = n1[0], ay = n1[1], az = n1[2], bx = n2[0], by = n2[1], bz = n2[2];
+        if (fabs(a1) < fabs(a2)) {
+            ax = n2[0]; ay = n2[1]; az = n2[2];
+            bx = n1[0]; by = n1[1]; bz = n1[2];
+            dx = -dx; dy = -dy; dz = -dz;
+            f3 = -a2;
+        } else {
+            f3 = a1;
+        }
+        double vx = dy * az - dz * ay, vy = dz * ax - dx * az, vz = dx * ay - dy * ax;  // d x n1
+        const double vn = sqrt(vx * vx + vy * vy + vz * vz);
+        if (vn != 0.0) {
+            vx /= vn; vy /= vn; vz /= vn;
+            const double wx = ay * vz - az * vy, wy = az * vx - ax * vz, wz = ax * vy - ay * vx;  // n1 x v
+            f2 = vx * bx + vy * by + vz * bz;
+            f1 = atan2(wx * bx + wy * by + wz * bz, ax * bx + ay * by + az * bz);
+        } else {
+            f3 = 0.0;
+        }
+    }
+    bins[0] = bin11(11.0 * (f1 + M_PI) / (2.0 * M_PI));
+    bins[1] = 11 + bin11(11.0 * (f2 + 1.0) / 2.0);
+    bins[2] = 22 + bin11(11.0 * (f3 + 1.0) / 2.0);
+}
+
+__global__ __launch_bounds__(kWave) void k_spfh(const double4* __restrict__ pts, const double* __restrict__ normals,
+                                                const int* __restrict__ idx, const int* __restrict__ cnt, int k,
+                                                double* __restrict__ spfh) {
+    __shared__ unsigned char s_bin[3][kMaxNN];
+    const int lane = threadIdx.x;
+    const size_t i = blockIdx.x;
+    const int L = min(cnt[i], min(k, kMaxNN));
+    if (L <= 1) {
+        if (lane < kBins) spfh[i * kBins + lane] = 0.0;
+        return;
+    }
+    const double4 p1 = pts[i];
+    const double n1[3] = {normals[i * 3], normals[i * 3 + 1], normals[i * 3 + 2]};
+    for (int e = 1 + lane; e < L; e += kWave) {
+        const size_t j = (size_t)idx[i * k + e];
+        const double n2[3] = {normals[j * 3], normals[j * 3 + 1], normals[j * 3 + 2]};
+        int bins[3];
+        pair_bins(p1, n1, pts[j], n2, bins);
+        s_bin[0][e] = (unsigned char)bins[0];
+        s_bin[1][e] = (unsigned char)bins[1];
+        s_bin[2][e] = (unsigned char)bins[2];
+    }
+    __syncthreads();
+    if (lane < kBins) {
+        const int grp = lane / 11;
+        int count = 0;
+        for (int e = 1; e < L; ++e) count += s_bin[grp][e] == lane ? 1 : 0;
+        spfh[i * kBins + lane] = 100.0 * (double)count / (double)(L - 1);
+    }
+}
+
+__global__ __launch_bounds__(kWave) void k_fpfh(const double* __restrict__ spfh, const int* __restrict__ idx,
+                                                const double* __restrict__ d2, const int* __restrict__ cnt, int k,
+                                                double* __restrict__ fpfh) {
+    __shared__ double s_acc[kBins];
+    const int lane = threadIdx.x;
+    const size_t i = blockIdx.x;
+    const int L = min(cnt[i], k);
+    double acc = 0.0;
+    if (lane < kBins)
+        for (int e = 1; e < L; ++e) {
+            const double d = d2[i * k + e];
+            if (d != 0.0) acc += spfh[(size_t)idx[i * k + e] * kBins + lane] / d;
+        }
+    if (lane < kBins) s_acc[lane] = acc;
+    __syncthreads();
+    if (lane < kBins) {
+        const int grp = lane / 11;
+        double sum = 0.0;
+        for (int q = 0; q < 11; ++q) sum += s_acc[grp * 11 + q];
+        const double scaled = sum != 0.0 ? acc / sum * 100.0 : 0.0;
+        fpfh[i * kBins + lane] = L <= 1 ? 0.0 : scaled + spfh[i * kBins + lane];
+    }
+}
+
+template <typename T>
+void free_dev(T*& p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
+
+struct NeighbourLists {
+    int* idx = nullptr;
+    double* d2 = nullptr;
+    int* cnt = nullptr;
+    int k = 0;
+    bool valid = false;
+};
+
+}  // namespace
+
+struct prg_fpfh {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int64_t n = 0;
+    double4* pts = nullptr;
+    double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0};
+    NeighbourLists nb[2];  // 0: normals, 1: features
+    double *normals = nullptr, *spfh = nullptr, *fpfh = nullptr;
+    bool have_normals = false, have_spfh = false, have_fpfh = false;
+};
+
+namespace {
+
+void free_lists(NeighbourLists& l) {
+    free_dev(l.idx);
+    free_dev(l.d2);
+    free_dev(l.cnt);
+    l.k = 0;
+    l.valid = false;
+}
+
+void free_cloud(prg_fpfh* h) {
+    free_dev(h->pts);
+    free_lists(h->nb[0]);
+    free_lists(h->nb[1]);
+    free_dev(h->normals);
+    free_dev(h->spfh);
+    free_dev(h->fpfh);
+    h->have_normals = h->have_spfh = h->have_fpfh = false;
+    h->n = 0;
+}
+
+struct GridScratch {
+    unsigned* keys = nullptr;  // 2 n: unsorted, sorted
+    int* vals = nullptr;       // 2 n: iota, order
+    int* cells = nullptr;      // 2 table: begin, end
+    double4* sp = nullptr;
+    void* tmp = nullptr;
+    ~GridScratch() {
+        free_dev(keys);
+        free_dev(vals);
+        free_dev(cells);
+        free_dev(sp);
+        if (tmp) (void)hipFree(tmp);
+    }
+};
+
+int run_search(prg_fpfh* h, NeighbourLists& out, double radius, int k) {
+    const int n = (int)h->n;
+    hipStream_t st = h->stream;
+    Grid g;
+    unsigned bits = kMinTableBits;
+    while (bits < kMaxTableBits && ((int64_t)1 << bits) < 2 * (int64_t)n) ++bits;
+    const int64_t table = (int64_t)1 << bits;
+    g.edge = radius;
+    g.mask = (unsigned)(table - 1);
+    double cells = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = h->lo[a];
+        g.dim[a] = cell_of(h->hi[a], h->lo[a], radius) + 1;
+        cells *= (double)g.dim[a];
+    }
+    g.dense = cells <= (double)table ? 1 : 0;
+
+    GridScratch s;
+    PRG_HIP(hipMalloc((void**)&s.keys, 2 * (size_t)n * sizeof(unsigned)));
+    PRG_HIP(hipMalloc((void**)&s.vals, 2 * (size_t)n * sizeof(int)));
+    PRG_HIP(hipMalloc((void**)&s.cells, 2 * (size_t)table * sizeof(int)));
+    PRG_HIP(hipMalloc((void**)&s.sp, (size_t)n * sizeof(double4)));
+    size_t need = 0;
+    PRG_TRY(prg::sort_pairs_u32(nullptr, &need, s.keys, s.keys + n, s.vals, s.vals + n, (unsigned)n, bits, st));
+    PRG_HIP(hipMalloc(&s.tmp, need + 256));
+    const unsigned nbk = (unsigned)prg::ceil_div(n, kBlock);
+    k_cell_keys<<<nbk, kBlock, 0, st>>>(h->pts, n, g, s.keys, s.vals);
+    PRG_HIP(hipGetLastError());
+    PRG_TRY(prg::sort_pairs_u32(s.tmp, &need, s.keys, s.keys + n, s.vals, s.vals + n, (unsigned)n, bits, st));
+    PRG_HIP(hipMemsetAsync(s.cells, 0, 2 * (size_t)table * sizeof(int), st));
+    k_cell_bounds<<<nbk, kBlock, 0, st>>>(h->pts, s.keys + n, s.vals + n, n, s.sp, s.cells, s.cells + table);
+    PRG_HIP(hipGetLastError());
+    k_search<<<(unsigned)n, kWave, 0, st>>>(s.sp, s.cells, s.cells + table, g, radius, k, out.idx, out.d2, out.cnt);
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipStreamSynchronize(st));  // the scratch goes away with this scope
+    return PRG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int prg_fpfh_create(prg_fpfh** out, int device, void* hip_stream) {
+    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_fpfh_create: out is NULL");
+    int count = 0;
+    PRG_HIP(hipGetDeviceCount(&count));
+    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_fpfh_create: device %d out of range", device);
+    prg_fpfh* h = new (std::nothrow) prg_fpfh();
+    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_fpfh_create: out of host memory");
+    h->device = device;
+    h->stream = (hipStream_t)hip_stream;
+    *out = h;
+    return PRG_OK;
+}
+
+int prg_fpfh_destroy(prg_fpfh* h) {
+    if (!h) return PRG_OK;
+    prg::DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    free_cloud(h);
+    delete h;
+    return PRG_OK;
+}
+
+int prg_fpfh_max_nn(int* max_nn_host) {
+    PRG_REQUIRE(max_nn_host != nullptr, PRG_ERR_INVALID, "prg_fpfh_max_nn: NULL argument");
+    *max_nn_host = kMaxNN;
+    return PRG_OK;
+}
+
+int prg_fpfh_set_data(prg_fpfh* h, const double* points_hd, int64_t n) {
+    PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_fpfh_set_data: NULL argument");
+    PRG_REQUIRE(n >= 1 && n <= (int64_t)1 << 30, PRG_ERR_INVALID, "prg_fpfh_set_data: need 1 <= n <= 2^30 points");
+    prg::DeviceGuard g(h->device);
+    std::vector<double> raw((size_t)n * 3), pad((size_t)n * 4, 0.0);
+    PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    double lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = raw[a];
+    for (int64_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const double v = raw[(size_t)i * 3 + a];
+            PRG_REQUIRE(std::isfinite(v), PRG_ERR_INVALID, "prg_fpfh_set_data: data contains NaN or infinity");
+            pad[(size_t)i * 4 + a] = v;
+            lo[a] = std::min(lo[a], v);
+            hi[a] = std::max(hi[a], v);
+        }
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    free_cloud(h);
+    hipError_t e = hipMalloc((void**)&h->pts, (size_t)n * sizeof(double4));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->normals, (size_t)n * 3 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->spfh, (size_t)n * kBins * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->fpfh, (size_t)n * kBins * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpyAsync(h->pts, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) free_cloud(h);  // no half-built cloud: the handle is back to "no data"
+    PRG_HIP(e);
+    h->n = n;
+    for (int a = 0; a < 3; ++a) {
+        h->lo[a] = lo[a];
+        h->hi[a] = hi[a];
+    }
+    return PRG_OK;
+}
+
+int prg_fpfh_search(prg_fpfh* h, int which, double radius, int max_nn) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_search: NULL argument");
+    PRG_REQUIRE(which == 0 || which == 1, PRG_ERR_INVALID, "prg_fpfh_search: which must be 0 (normals) or 1 (features)");
+    PRG_REQUIRE(radius > 0.0 && std::isfinite(radius), PRG_ERR_INVALID, "prg_fpfh_search: radius must be > 0 and finite");
+    PRG_REQUIRE(max_nn >= 1 && max_nn <= kMaxNN, PRG_ERR_INVALID, "prg_fpfh_search: max_nn must lie in 1 .. %d, got %d",
+                kMaxNN, max_nn);
+    PRG_REQUIRE(h->pts != nullptr, PRG_ERR_STATE, "prg_fpfh_search: no data (prg_fpfh_set_data first)");
+    prg::DeviceGuard g(h->device);
+    NeighbourLists& l = h->nb[which];
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    free_lists(l);
+    if (which == 1) h->have_spfh = h->have_fpfh = false;
+    const size_t slots = (size_t)h->n * (size_t)max_nn;
+    hipError_t e = hipMalloc((void**)&l.idx, slots * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&l.d2, slots * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&l.cnt, (size_t)h->n * sizeof(int));
+    if (e != hipSuccess) free_lists(l);
+    PRG_HIP(e);
+    l.k = max_nn;
+    const int st = run_search(h, l, radius, max_nn);
+    if (st != PRG_OK) {
+        free_lists(l);
+        return st;
+    }
+    l.valid = true;
+    return PRG_OK;
+}
+
+int prg_fpfh_get_neighbours(prg_fpfh* h, int which, int* idx_host, double* d2_host, int* count_host) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_get_neighbours: NULL argument");
+    PRG_REQUIRE(which == 0 || which == 1, PRG_ERR_INVALID, "prg_fpfh_get_neighbours: which must be 0 or 1");
+    const NeighbourLists& l = h->nb[which];
+    PRG_REQUIRE(l.valid, PRG_ERR_STATE, "prg_fpfh_get_neighbours: prg_fpfh_search first");
+    prg::DeviceGuard g(h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    const size_t slots = (size_t)h->n * (size_t)l.k;
+    if (idx_host) PRG_HIP(hipMemcpy(idx_host, l.idx, slots * sizeof(int), hipMemcpyDeviceToHost));
+    if (d2_host) PRG_HIP(hipMemcpy(d2_host, l.d2, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (count_host) PRG_HIP(hipMemcpy(count_host, l.cnt, (size_t)h->n * sizeof(int), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+int prg_fpfh_normals(prg_fpfh* h) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_normals: NULL argument");
+    PRG_REQUIRE(h->nb[0].valid, PRG_ERR_STATE, "prg_fpfh_normals: prg_fpfh_search(0, ...) first");
+    prg::DeviceGuard g(h->device);
+    k_normals<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts, h->nb[0].idx, h->nb[0].cnt, h->nb[0].k, h->normals);
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    h->have_normals = true;
+    h->have_spfh = h->have_fpfh = false;
+    return PRG_OK;
+}
+
+int prg_fpfh_set_normals(prg_fpfh* h, const double* normals_hd) {
+    PRG_REQUIRE(h && normals_hd, PRG_ERR_INVALID, "prg_fpfh_set_normals: NULL argument");
+    PRG_REQUIRE(h->pts != nullptr, PRG_ERR_STATE, "prg_fpfh_set_normals: no data (prg_fpfh_set_data first)");
+    prg::DeviceGuard g(h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(h->normals, normals_hd, (size_t)h->n * 3 * sizeof(double), hipMemcpyDefault));
+    h->have_normals = true;
+    h->have_spfh = h->have_fpfh = false;
+    return PRG_OK;
+}
+
+int prg_fpfh_get_normals(prg_fpfh* h, double* normals_host) {
+    PRG_REQUIRE(h && normals_host, PRG_ERR_INVALID, "prg_fpfh_get_normals: NULL argument");
+    PRG_REQUIRE(h->have_normals, PRG_ERR_STATE, "prg_fpfh_get_normals: prg_fpfh_normals or prg_fpfh_set_normals first");
+    prg::DeviceGuard g(h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(normals_host, h->normals, (size_t)h->n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+int prg_fpfh_spfh(prg_fpfh* h) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_spfh: NULL argument");
+    PRG_REQUIRE(h->nb[1].valid, PRG_ERR_STATE, "prg_fpfh_spfh: prg_fpfh_search(1, ...) first");
+    PRG_REQUIRE(h->have_normals, PRG_ERR_STATE, "prg_fpfh_spfh: prg_fpfh_normals or prg_fpfh_set_normals first");
+    prg::DeviceGuard g(h->device);
+    k_spfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts, h->normals, h->nb[1].idx, h->nb[1].cnt, h->nb[1].k, h->spfh);
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    h->have_spfh = true;
+    h->have_fpfh = false;
+    return PRG_OK;
+}
+
+int prg_fpfh_get_spfh(prg_fpfh* h, double* spfh_host) {
+    PRG_REQUIRE(h && spfh_host, PRG_ERR_INVALID, "prg_fpfh_get_spfh: NULL argument");
+    PRG_REQUIRE(h->have_spfh, PRG_ERR_STATE, "prg_fpfh_get_spfh: prg_fpfh_spfh first");
+    prg::DeviceGuard g(h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(spfh_host, h->spfh, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+int prg_fpfh_fpfh(prg_fpfh* h) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_fpfh: NULL argument");
+    PRG_REQUIRE(h->have_spfh && h->nb[1].valid, PRG_ERR_STATE, "prg_fpfh_fpfh: prg_fpfh_spfh first");
+    prg::DeviceGuard g(h->device);
+    k_fpfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->spfh, h->nb[1].idx, h->nb[1].d2, h->nb[1].cnt, h->nb[1].k, h->fpfh);
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    h->have_fpfh = true;
+    return PRG_OK;
+}
+
+int prg_fpfh_get_fpfh(prg_fpfh* h, double* fpfh_host) {
+    PRG_REQUIRE(h && fpfh_host, PRG_ERR_INVALID, "prg_fpfh_get_fpfh: NULL argument");
+    PRG_REQUIRE(h->have_fpfh, PRG_ERR_STATE, "prg_fpfh_get_fpfh: prg_fpfh_fpfh first");
+    prg::DeviceGuard g(h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(fpfh_host, h->fpfh, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+}  // extern "C"

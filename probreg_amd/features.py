@@ -15,8 +15,8 @@ Differences a caller can see (on purpose):
     (DESIGN.md).
   * ``weights_init``, ``means_init`` and ``precisions_init`` are given together or not at all; given, EM starts from
     them and reproduces scikit-learn's result to rounding.
-  * Clouds of dimension 2 or 3.  ``FPFH`` is not provided.  The reference's third generator, ``OneClassSVM``, is
-    provided in ``probreg_amd.svm`` and not under this module's name.
+  * Clouds of dimension 2 or 3.  The reference's other two generators are provided in modules of their own and not
+    under this module's name: ``FPFH`` in ``probreg_amd.fpfh``, ``OneClassSVM`` in ``probreg_amd.svm``.
 """
 import abc
 import ctypes
