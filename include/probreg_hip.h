@@ -414,6 +414,57 @@ int prg_fr_mstep_from_arrays(int device, void* hip_stream, const double* t_sourc
                              const float* nx_hd, const double* rot9, const double* t3, double sigma2, double w,
                              double* out_host);
 
+/* ---- Deformable kinematic FilterReg (dual-quaternion skinning) --------------------------------
+ * A dual quaternion is 8 doubles (r_w, r_x, r_y, r_z, d_w, d_x, d_y, d_z); a point is tied to two nodes (`pairs`
+ * [m x 2] int32) with two weights ([m x 2] float32, widened to fp64 on upload) and moves by their linear blend divided
+ * by |r| (no antipodal sign correction).  All sums are fp64 with a fixed order, per "segment" = run of one ordered node
+ * pair (pair0 * k_nodes + pair1, ascending); the 6K x 6K assembly and the minimum-norm solve are the caller's.
+ *
+ * prg_dq_skin: out[i] = blend(i).transform_point(points[i]), [m x 3] float64, no handle.
+ * Replaces: DeformableKinematicModel.__init__ / _transform, transformation.py:209-212 (dq3d op.dlb, transform_point). */
+int prg_dq_skin(int device, void* hip_stream, const double* points_hd, int64_t m, const int* pairs_hd,
+                const float* weights_hd, const double* dualquats_hd, int k_nodes, double* out_hd);
+/* Skinning weights of the plan's source (set the source first; a new source drops them).  Sorts the points by ordered
+ * pair key once; *n_segments = number of distinct ordered pairs.  PRG_ERR_INVALID on an index outside [0, k_nodes) or a
+ * wrong m - an earlier skinning then stays in place.  The dual quaternions start at the identity.
+ * Replaces: DeformableKinematicFilterReg.__init__ filterreg.py:200-208, SkinningWeight.pairs_set / in_pair
+ * transformation.py:187-194. */
+int prg_fr_set_skinning(prg_filterreg* h, const int* pairs_hd, const float* weights_hd, int64_t m, int k_nodes,
+                        int* n_segments);
+/* The model's dual quaternions [k_nodes x 8], host memory.  Replaces: trans_p.dualquats, filterreg.py:206-208, 261. */
+int prg_fr_set_dualquats(prg_filterreg* h, const double* dualquats_host, int k_nodes);
+int prg_fr_get_dualquats(prg_filterreg* h, double* dualquats_host, int k_nodes);
+/* Skin the stored source with the plan's dual quaternions on the device and run the lattice E-step of prg_fr_estep
+ * over [skinned source; target] / sqrt(sigma2); m0, m1, m2 stay on the device (prg_fr_get_estep reads them).
+ * Replaces: `self._tf_result.transform(self._source)` + expectation_step, filterreg.py:130-134, 78-100. */
+int prg_fr_kinematic_estep(prg_filterreg* h, double sigma2, double alpha, int* lattice_size, int* with_blur);
+/* E-step values from the caller instead of the plan's last E-step (m2 may be NULL), for the M-step on explicit arrays:
+ * t_source [m x 3] float64, m0 [m], m1 [m x 3], m2 [m] float32, m = the plan's source size.  Holds until the next
+ * prg_fr_kinematic_estep.  Replaces: the arguments of _maximization_step, filterreg.py:211-220. */
+int prg_fr_kinematic_set_arrays(prg_filterreg* h, const double* t_source_hd, const float* m0_hd, const float* m1_hd,
+                                const float* m2_hd, int64_t n_target);
+/* Normal-matrix sums, once per M-step.  out_host [n_segments x 34] per segment: with s^2 = m0/(m0+c)/sigma2,
+ * c = w/(1-w) n/m, and x the moved source: [0..9] sum w0^2 s^2 (1, x, y, z, xx, xy, xz, yy, yz, zz), [10..19] the same
+ * under w0 w1, [20..29] under w1^2 (J^T J of J = [-[x]x | I] is linear in these), [30] numerator and [31] sum m0/(m0+c)
+ * of the sigma2 update, [32] points that took part.  A point with m0 == 0 takes no part; reference_form != 0 gives it
+ * m0 = float32 eps instead (filterreg.py:223).  Replaces: filterreg.py:222-236, 263-264. */
+int prg_fr_kinematic_normal_sums(prg_filterreg* h, double sigma2, double w, int reference_form, int n_segments,
+                                 double* out_host);
+/* Gradient sums, once per inner iteration: twists_host [k_nodes x 6] are the current increments; every point is
+ * skinned with dualquat_from_twist of them, rx = s (x - m1/m0).  out_host [n_segments x 16]: [0..5] sum w0 s J^T rx,
+ * [6..11] sum w1 s J^T rx, [12] sum (rx_0 + rx_1 + rx_2)^2 (= np.dot(rx.T, rx).sum(), :265).  reference_form != 0
+ * leaves a point whose two nodes coincide at x = 0, as the reference's loop over permutations does.
+ * Replaces: filterreg.py:38-42, 238-254, 265. */
+int prg_fr_kinematic_grad_sums(prg_filterreg* h, const double* twists_host, int reference_form, int n_segments,
+                               double* out_host);
+/* Both sums in one call on explicit arrays, no handle (twists_host NULL = zero increments); n_segments must be the
+ * number of distinct ordered pairs.  Replaces: as the two calls above. */
+int prg_fr_kinematic_sums_from_arrays(int device, void* hip_stream, const double* t_source_hd, int64_t m,
+                                      int64_t n_target, const float* m0_hd, const float* m1_hd, const float* m2_hd,
+                                      const int* pairs_hd, const float* weights_hd, int k_nodes, double sigma2, double w,
+                                      int reference_form, const double* twists_host, int n_segments,
+                                      double* normal_out_host, double* grad_out_host);
+
 /* Weighted Kabsch on float32 clouds: centroids weighted by w, covariance by w^2; rot_host dim x dim
  * row-major, t_host dim.  Replaces: _kabsch.kabsch / kabsch2d (cc/kabsch_py.cc, cc/kabsch.cc:6-109). */
 int prg_kabsch_weighted(int device, void* hip_stream, const float* model_hd, const float* target_hd,

@@ -142,6 +142,16 @@ SIGNATURES = {
     "prg_fr_get_nx": [_vp, _vp],
     "prg_fr_mstep_pt2pl": [_vp, _d, _i, _d, _vp],
     "prg_fr_mstep_from_arrays": [_i, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp],
+    "prg_dq_skin": [_i, _vp, _vp, _i64, _vp, _vp, _vp, _i, _vp],
+    "prg_fr_set_skinning": [_vp, _vp, _vp, _i64, _i, _c.POINTER(_i)],
+    "prg_fr_set_dualquats": [_vp, _vp, _i],
+    "prg_fr_get_dualquats": [_vp, _vp, _i],
+    "prg_fr_kinematic_estep": [_vp, _d, _d, _c.POINTER(_i), _c.POINTER(_i)],
+    "prg_fr_kinematic_set_arrays": [_vp, _vp, _vp, _vp, _vp, _i64],
+    "prg_fr_kinematic_normal_sums": [_vp, _d, _d, _i, _i, _vp],
+    "prg_fr_kinematic_grad_sums": [_vp, _vp, _i, _i, _vp],
+    "prg_fr_kinematic_sums_from_arrays": [_i, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _vp, _i,
+                                          _vp, _vp],
     "prg_kabsch_weighted": [_i, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp],
     "prg_gmm_create": [_pp, _i, _vp],
     "prg_gmm_destroy": [_vp],

@@ -26,6 +26,7 @@
 #include "prg_device.h"
 #include "prg_common.h"
 #include "small_linalg.h"
+#include "fr_plan.h"
 
 namespace prg {
 int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
@@ -1570,6 +1571,11 @@ struct prg_filterreg {
     bool have_src = false, have_tgt = false, have_estep = false;
     FrFeat prod;             // feature producer handed to the embedding kernels
     int last_blur = 1;       // with_blur of the previous E-step: which lattice the next one tries first
+    // deformable kinematic model (filterreg_kinematic.hip, reached through fr_plan.h)
+    std::vector<int> src_order;            // host copy of src_perm (empty: caller's order)
+    const double* src_override = nullptr;  // non-null during prg_fr_kinematic_estep: the skinned source stands in for `src`
+    void* kin = nullptr;                   // skinning context, owned by the plan ...
+    void (*kin_free)(void*) = nullptr;     // ... and released through this
 };
 
 namespace {
@@ -2181,6 +2187,7 @@ int prg_fr_destroy(prg_filterreg* h) {
     if (!h) return PRG_OK;
     prg::DeviceGuard g(h->L.device);
     (void)hipStreamSynchronize(h->L.stream);
+    if (h->kin) h->kin_free(h->kin);
     lat_free(&h->L);
     for (void* p : {(void*)h->src, (void*)h->tgt, (void*)h->ts, (void*)h->vin, (void*)h->vout, (void*)h->state,
                     (void*)h->part, (void*)h->nrm, (void*)h->ref_pos, (void*)h->src_perm})
@@ -2213,6 +2220,10 @@ int prg_fr_set_source(prg_filterreg* h, const double* source_hd, int64_t m, int 
     PRG_REQUIRE(!h->have_tgt || h->D == dim, PRG_ERR_INVALID, "prg_fr_set_source: dim mismatch with target");
     prg::DeviceGuard g(h->L.device);
     PRG_HIP(hipStreamSynchronize(h->L.stream));
+    if (h->kin) {  // skinning weights belong to the previous source
+        h->kin_free(h->kin);
+        h->kin = nullptr;
+    }
     if (h->src) (void)hipFree(h->src);
     h->src = nullptr;
     PRG_HIP(hipMalloc((void**)&h->src, (size_t)m * 4 * sizeof(double)));  // (x, y, z, 0) per point: 16-byte accesses in k_embed
@@ -2237,6 +2248,7 @@ int prg_fr_set_source(prg_filterreg* h, const double* source_hd, int64_t m, int 
         }
         PRG_HIP(hipMemcpyAsync(h->src, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, h->L.stream));
         PRG_HIP(hipStreamSynchronize(h->L.stream));
+        h->src_order = order;
     }
     h->M = m;
     h->D = dim;
@@ -2302,7 +2314,7 @@ int prg_fr_estep(prg_filterreg* h, double alpha, int* lattice_size, int* with_bl
     prg::DeviceGuard g(h->L.device);
     const int64_t tot = h->M + h->N;
     // features are produced inside the embedding kernels (transform, division by sigma, float32 cast)
-    h->prod = FrFeat{h->src, h->tgt, h->state, h->ts, h->M, h->D};
+    h->prod = FrFeat{h->src_override ? h->src_override : h->src, h->tgt, h->state, h->ts, h->M, h->D};
     h->L.prod = &h->prod;
     h->L.ref_pos = h->ref_pos;
     int blur = 1;
@@ -2342,6 +2354,32 @@ int prg_fr_estep(prg_filterreg* h, double alpha, int* lattice_size, int* with_bl
     return PRG_OK;
 }
 
+static int fr_flush_slice(prg_filterreg* h);
+}  // extern "C"
+
+// what filterreg_kinematic.hip sees of a plan (fr_plan.h)
+namespace prg {
+int fr_view(prg_filterreg* h, FrView* v, bool flush_slice) {
+    if (flush_slice && h->have_estep) PRG_TRY(fr_flush_slice(h));
+    v->device = h->L.device;
+    v->stream = h->L.stream;
+    v->M = h->M; v->N = h->N; v->D = h->D; v->ch = h->ch;
+    v->src = h->src; v->ts = h->ts; v->vout = h->vout; v->state = h->state;
+    v->src_order = h->src_order.empty() ? nullptr : h->src_order.data();
+    v->have_src = h->have_src; v->have_tgt = h->have_tgt; v->have_estep = h->have_estep;
+    v->kin = &h->kin;
+    v->kin_free = &h->kin_free;
+    return PRG_OK;
+}
+int fr_estep_moved(prg_filterreg* h, const double* moved, double alpha, int* lattice_size, int* with_blur) {
+    h->src_override = moved;
+    const int st = prg_fr_estep(h, alpha, lattice_size, with_blur);
+    h->src_override = nullptr;
+    return st;
+}
+}  // namespace prg
+
+extern "C" {
 // the E-step's deferred slice, for every consumer of `vout` other than the point-to-point M-step
 static int fr_flush_slice(prg_filterreg* h) {
     if (!h->slice_pending) return PRG_OK;

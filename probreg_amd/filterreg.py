@@ -9,7 +9,13 @@ previous ``q`` when every ``m0`` is zero.
 Point-to-plane (``objective_type='pt2pl'``, filterreg.py:183-186 + cc/point_to_plane.cc) is built as well, and so are
 feature-space lattices: a ``feature_fn`` other than the identity (filterreg.py:121, 125-133; e.g. 33-dimensional FPFH
 descriptors) runs the reference's loop - transform, ``feature_fn`` on the host, lattice E-step over the features
-(1 <= d <= 64) and M-step on the GPU.  Out of scope: ``DeformableKinematicFilterReg``.
+(1 <= d <= 64) and M-step on the GPU.
+
+``DeformableKinematicFilterReg`` (filterreg.py:199-266) moves the source by dual-quaternion skinning, two nodes per point
+(``transformation.DeformableKinematicModel``).  Its M-step is the COMPLETE Gauss-Newton system of DESIGN.md section 3.10
+- the reference fills only the off-diagonal node blocks and diverges on anything but its own example; that system stays
+available as ``reference_form=True``.  Skinning, the lattice E-step and the per-node-pair sums of the M-step run on the
+GPU and stay there over the EM loop; the 6K x 6K assembly and the minimum-norm solve are host LAPACK.
 """
 import abc
 import ctypes
@@ -110,6 +116,48 @@ class _Plan(object):
         """The 20-double device state (prg_fr_get_state); synchronises."""
         out = np.zeros(20)
         check(lib.prg_fr_get_state(self._h, ptr(out)))
+        return out
+
+    # ---- deformable kinematic model (DESIGN.md section 3.10) ----
+    def set_skinning(self, pairs, vals, n_nodes):
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        vals = np.ascontiguousarray(vals, dtype=np.float32)
+        nseg = ctypes.c_int(0)
+        check(lib.prg_fr_set_skinning(self._h, ptr(pairs), ptr(vals), pairs.shape[0], int(n_nodes), ctypes.byref(nseg)))
+        self.n_nodes = int(n_nodes)
+        # the segments of the device sums: the distinct ordered pairs, ascending in pair0 * K + pair1
+        keys = np.unique(pairs[:, 0].astype(np.int64) * int(n_nodes) + pairs[:, 1])
+        assert keys.shape[0] == nseg.value
+        self.seg_a, self.seg_b = keys // int(n_nodes), keys % int(n_nodes)
+
+    def set_dualquats(self, dq):
+        dq = np.ascontiguousarray(dq, dtype=np.float64)
+        check(lib.prg_fr_set_dualquats(self._h, ptr(dq), dq.shape[0]))
+
+    def get_dualquats(self):
+        dq = np.empty((self.n_nodes, 8))
+        check(lib.prg_fr_get_dualquats(self._h, ptr(dq), self.n_nodes))
+        return dq
+
+    def kinematic_estep(self, sigma2, alpha=0.015):
+        size, blur = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib.prg_fr_kinematic_estep(self._h, float(sigma2), float(alpha), ctypes.byref(size), ctypes.byref(blur)))
+        return int(size.value), bool(blur.value)
+
+    def kinematic_set_arrays(self, t_source, m0, m1, m2, n_target):
+        check(lib.prg_fr_kinematic_set_arrays(self._h, ptr(t_source), ptr(m0), ptr(m1), None if m2 is None else ptr(m2),
+                                              int(n_target)))
+
+    def kinematic_normal_sums(self, sigma2, w, reference_form):
+        out = np.empty((self.seg_a.shape[0], 34))
+        check(lib.prg_fr_kinematic_normal_sums(self._h, float(sigma2), float(w), 1 if reference_form else 0, out.shape[0],
+                                               ptr(out)))
+        return out
+
+    def kinematic_grad_sums(self, tw, reference_form):
+        tw = np.ascontiguousarray(tw, dtype=np.float64)
+        out = np.empty((self.seg_a.shape[0], 16))
+        check(lib.prg_fr_kinematic_grad_sums(self._h, ptr(tw), 1 if reference_form else 0, out.shape[0], ptr(out)))
         return out
 
     def close(self):
@@ -229,6 +277,14 @@ class FilterReg(abc.ABC):
         target = _as_points(target)
         if self._source.shape[1] != target.shape[1] or target.shape[1] not in (2, 3):
             raise ValueError("source and target must both be (n, 2) or (n, 3) arrays.")
+        feature_fn = self._resolve_feature_fn(feature_fn)
+        if feature_fn is not _identity:
+            # any other callable takes the reference's loop (features on the host every iteration)
+            return self._registration_features(target, w, objective_type, maxiter, tol, min_sigma2, feature_fn)
+        return self._registration_device(target, w, objective_type, maxiter, tol, min_sigma2)
+
+    def _resolve_feature_fn(self, feature_fn):
+        """``_identity`` for every spelling of the identity, the callable itself otherwise."""
         if feature_fn is None:  # documented selector of the device-resident path
             feature_fn = _identity
         if feature_fn is not _identity:
@@ -240,15 +296,16 @@ class FilterReg(abc.ABC):
             probe = self._source.copy()
             if feature_fn(probe) is probe and np.array_equal(probe, self._source):
                 feature_fn = _identity
-        if feature_fn is not _identity:
-            # any other callable takes the reference's loop (features on the host every iteration)
-            return self._registration_features(target, w, objective_type, maxiter, tol, min_sigma2, feature_fn)
+        return feature_fn
+
+    def _registration_device(self, target, w, objective_type, maxiter, tol, min_sigma2):
+        """The device-resident loop of the identity ``feature_fn``."""
+        dim = target.shape[1]
         q = None
         if self._sigma2 is None:
             self._sigma2 = max(mu.squared_kernel_sum(self._source, target), min_sigma2)
         plan = self._ensure_plan(target)
         plan.set_normals(self._target_normals if objective_type == "pt2pl" else None)
-        dim = target.shape[1]
         res = MstepResult(self._tf_result, self._sigma2, None)
         # the transform and sigma2 live on the device: uploaded once, advanced by the M-step kernel
         plan.set_state(self._tf_result.rot, self._tf_result.t, self._sigma2)
@@ -371,6 +428,214 @@ class RigidFilterReg(FilterReg):
             return MstepResult(trans_p, sigma2, None)
         return MstepResult(tf.RigidTransformation(out[:9].reshape(3, 3)[:dim, :dim].copy(), out[9:9 + dim].copy()),
                            float(out[15]), float(out[13]))
+
+
+def _moment_block(mom):
+    """sum s^2 J^T J, J = [-[x]x | I] (se3_op.py:56-59), from the ten sums s^2 (1, x, y, z, xx, xy, xz, yy, yz, zz)."""
+    n, x, y, z, xx, xy, xz, yy, yz, zz = mom
+    blk = np.zeros((6, 6))
+    blk[:3, :3] = [[yy + zz, -xy, -xz], [-xy, xx + zz, -yz], [-xz, -yz, xx + yy]]
+    blk[:3, 3:] = [[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]]
+    blk[3:, :3] = blk[:3, 3:].T
+    blk[3:, 3:] = n * np.identity(3)
+    return blk
+
+
+def _assemble_normal(seg_a, seg_b, sums, k, reference_form):
+    """The 6K x 6K normal matrix from the per-segment device sums, segments in ascending key order."""
+    a = np.zeros((6 * k, 6 * k))
+    for na, nb, row in zip(seg_a, seg_b, sums):
+        ia, ib = slice(6 * na, 6 * na + 6), slice(6 * nb, 6 * nb + 6)
+        cross = _moment_block(row[10:20])
+        if reference_form:  # filterreg.py:228-236: off-diagonal node blocks only, ordered pairs of different nodes
+            if na != nb:
+                a[ia, ib] += cross
+                a[ib, ia] += cross
+        else:
+            a[ia, ia] += _moment_block(row[0:10])
+            a[ia, ib] += cross
+            a[ib, ia] += cross
+            a[ib, ib] += _moment_block(row[20:30])
+    return a
+
+
+def _assemble_gradient(seg_a, seg_b, sums, k, reference_form):
+    """(b, q) from the per-segment gradient sums."""
+    b = np.zeros(6 * k)
+    for na, nb, row in zip(seg_a, seg_b, sums):
+        if reference_form:  # filterreg.py:247-254: into the first node of the pair only
+            if na != nb:
+                b[6 * na:6 * na + 6] += row[0:6]
+        else:
+            b[6 * na:6 * na + 6] += row[0:6]
+            b[6 * nb:6 * nb + 6] += row[6:12]
+    return b, float(np.sum(sums[:, 12]))
+
+
+def _kinematic_weights(weights, m):
+    """(pairs int32 (m, 2), vals float32 (m, 2), K) of a SkinningWeight, checked."""
+    if weights is None:
+        raise ValueError("skinning weights are needed.")
+    pairs = np.ascontiguousarray(weights["pair"], dtype=np.int32).reshape(-1, 2)
+    vals = np.ascontiguousarray(weights["val"], dtype=np.float32).reshape(-1, 2)
+    if pairs.shape[0] != m:
+        raise ValueError("%d skinning weights for %d source points." % (pairs.shape[0], m))
+    return pairs, vals
+
+
+def _kinematic_solve(plan, dualquats, sigma2, w, update_sigma2, maxiter, tol, reference_form):
+    """The M-step of DESIGN.md section 3.10 on a plan that holds E-step values: normal sums once, then the Gauss-Newton
+    inner loop - per iteration 6K increments go to the device and the per-segment gradient sums come back.
+    Returns (dualquats, sigma2, q, inner iterations); q None when no point has m0 != 0."""
+    k = plan.n_nodes
+    nsum = plan.kinematic_normal_sums(sigma2, w, reference_form)
+    if float(np.sum(nsum[:, 32])) == 0.0:
+        return dualquats, sigma2, None, 0
+    a = _assemble_normal(plan.seg_a, plan.seg_b, nsum, k, reference_form)
+    # minimum-norm least squares with the cut-off of np.linalg.lstsq(rcond=None), factored once: A is constant over the loop
+    pinv = np.linalg.pinv(a, rcond=np.finfo(np.float64).eps * a.shape[0])
+    tw = np.zeros(6 * k)
+    q, n_iter = None, 0
+    for _ in range(maxiter):
+        b, q = _assemble_gradient(plan.seg_a, plan.seg_b, plan.kinematic_grad_sums(tw, reference_form), k, reference_form)
+        dtw = pinv @ b
+        tw -= dtw
+        n_iter += 1
+        if np.linalg.norm(dtw) < tol:
+            break
+    used = np.zeros(k, dtype=bool)
+    used[plan.seg_a] = used[plan.seg_b] = True  # (a node that no point names keeps its dual quaternion as it is)
+    new = np.array([tf.dualquat_mul(tf.dualquat_from_twist(tw[6 * i:6 * i + 6]), dualquats[i]) if used[i]
+                    else np.asarray(dualquats[i], dtype=np.float64) for i in range(k)])
+    if update_sigma2:  # filterreg.py:263-264
+        sigma2 = float(np.sum(nsum[:, 30])) / (3.0 * float(np.sum(nsum[:, 31])))
+    return new, sigma2, q, n_iter
+
+
+class DeformableKinematicFilterReg(FilterReg):
+    """FilterReg with the deformable kinematic model (reference filterreg.py:199-266): the source moves by
+    dual-quaternion skinning of ``skinning_weight.n_nodes`` nodes, two per point.
+
+    source          : (M, 3) array
+    skinning_weight : ``transformation.DeformableKinematicModel.SkinningWeight`` of length M
+    sigma2          : kernel variance (None = automatic)
+    update_sigma2   : re-estimate sigma2 in every M-step (an extension: the reference never does here)
+
+    With the identity ``feature_fn`` the EM loop stays on the device (skinning, lattice E-step, M-step sums); any other
+    callable takes the driver of the base class.  The M-step is the complete Gauss-Newton system of DESIGN.md section
+    3.10; ``_maximization_step(..., reference_form=True)`` is the reference's own.  The result's transformation carries
+    ``inner_iterations``, the Gauss-Newton iterations of the last M-step.
+    """
+
+    def __init__(self, source=None, skinning_weight=None, sigma2=None, update_sigma2=False):
+        super(DeformableKinematicFilterReg, self).__init__(source, sigma2=sigma2, update_sigma2=update_sigma2)
+        if skinning_weight is None:
+            raise ValueError("DeformableKinematicFilterReg needs skinning weights.")
+        self._tf_type = tf.DeformableKinematicModel
+        self._skinning_weight = skinning_weight
+        if self._source is not None:
+            self._check_source()
+        self._tf_result = self._tf_type(tf.dualquat_identity(self._skinning_weight.n_nodes), self._skinning_weight)
+
+    def _check_source(self):
+        if self._source.ndim != 2 or self._source.shape[1] != 3:
+            raise ValueError("dim must be 3.")  # filterreg.py:219
+        _kinematic_weights(self._skinning_weight, self._source.shape[0])
+        if int(np.min(self._skinning_weight["pair"])) < 0:
+            raise ValueError("skinning weights name a node outside [0, %d)." % self._skinning_weight.n_nodes)
+
+    def set_source(self, source):
+        super(DeformableKinematicFilterReg, self).set_source(source)
+        self._check_source()
+
+    @staticmethod
+    def _maximization_step(t_source, target, estep_res, trans_p, sigma2, w=0.0, objective_type="", maxiter=50, tol=1.0e-4,
+                           reference_form=False):
+        """Kinematic M-step from explicit arrays (reference filterreg.py:211-266).  The arrays go
+        to the device once; the inner loop exchanges increments and per-segment sums only.  sigma2 is re-estimated
+        when ``estep_res.m2`` is given."""
+        t_source = np.ascontiguousarray(_as_points(t_source))
+        target = _as_points(target)
+        if t_source.ndim != 2 or t_source.shape[1] != 3:
+            raise ValueError("dim must be 3.")
+        m = t_source.shape[0]
+        m0, m1, m2 = estep_res[0], estep_res[1], estep_res[2]
+        pairs, vals = _kinematic_weights(trans_p.weights, m)
+        dualquats = np.asarray(trans_p.dualquats, dtype=np.float64).reshape(-1, 8)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        plan = _Plan()
+        try:
+            plan.set_source(t_source)
+            plan.set_skinning(pairs, vals, dualquats.shape[0])
+            plan.kinematic_set_arrays(t_source, f32(m0), f32(m1), f32(m2), target.shape[0])
+            dq, sigma2_new, q, n_iter = _kinematic_solve(plan, dualquats, sigma2, w, m2 is not None, maxiter, tol,
+                                                        reference_form)
+        finally:
+            plan.close()
+        if q is None:
+            return MstepResult(trans_p, sigma2, None)
+        model = tf.DeformableKinematicModel(dq, trans_p.weights)
+        model.inner_iterations = n_iter
+        return MstepResult(model, sigma2_new, q)
+
+    def _registration_device(self, target, w, objective_type, maxiter, tol, min_sigma2):
+        """filterreg.py:120-147 with everything per point on the device: the source is skinned there, the lattice
+        E-step leaves m0, m1, m2 there and the M-step sums read them in place."""
+        if target.shape[1] != 3:
+            raise ValueError("dim must be 3.")
+        self._check_source()
+        q = None
+        if self._sigma2 is None:
+            self._sigma2 = max(mu.squared_kernel_sum(self._source, target), min_sigma2)
+        plan = self._ensure_plan(target)
+        pairs, vals = _kinematic_weights(self._skinning_weight, self._source.shape[0])
+        plan.set_skinning(pairs, vals, self._tf_result.dualquats.shape[0])
+        res = MstepResult(self._tf_result, self._sigma2, None)
+        for i in range(maxiter):
+            plan.set_dualquats(self._tf_result.dualquats)
+            plan.kinematic_estep(self._sigma2)
+            dq, sigma2, qn, n_iter = _kinematic_solve(plan, self._tf_result.dualquats, self._sigma2, w, self._update_sigma2,
+                                                     50, 1.0e-4, False)
+            if qn is None:  # every m0 == 0 (filterreg.py:136-138)
+                res = MstepResult(self._tf_result, self._sigma2, q)
+                break
+            model = tf.DeformableKinematicModel(dq, self._skinning_weight)
+            model.inner_iterations = n_iter
+            res = MstepResult(model, sigma2, qn)
+            self._tf_result = res.transformation
+            self._sigma2 = max(res.sigma2, min_sigma2)
+            for c in self._callbacks:
+                c(self._tf_result)
+            log.debug("Iteration: {}, Criteria: {}".format(i, res.q))
+            if q is not None and abs(res.q - q) < tol:
+                break
+            q = res.q
+        return res
+
+
+def kinematic_system(t_source, target_count, estep_res, weights, sigma2, w=0.0, reference_form=False):
+    """(A, b) of the kinematic M-step from the device sums: the 6K x 6K normal matrix and the
+    gradient at zero increments.  ``weights`` is a SkinningWeight, ``estep_res`` an EstepResult (or (m0, m1, ...))."""
+    t_source = np.ascontiguousarray(_as_points(t_source))
+    if t_source.ndim != 2 or t_source.shape[1] != 3:
+        raise ValueError("dim must be 3.")
+    m = t_source.shape[0]
+    pairs, vals = _kinematic_weights(weights, m)
+    k = int(pairs.max()) + 1
+    _lib.require_gpu()
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+    m0, m1 = f32(estep_res[0]), f32(estep_res[1])
+    m2 = f32(estep_res[2]) if len(estep_res) > 2 else None
+    keys = np.unique(pairs[:, 0].astype(np.int64) * k + pairs[:, 1])
+    seg_a, seg_b = keys // k, keys % k
+    nsum, gsum = np.empty((keys.shape[0], 34)), np.empty((keys.shape[0], 16))
+    dev, st = _current_device_and_stream()
+    check(lib.prg_fr_kinematic_sums_from_arrays(dev, ctypes.c_void_p(st), ptr(t_source), m, int(target_count), ptr(m0),
+                                                ptr(m1), None if m2 is None else ptr(m2), ptr(pairs), ptr(vals), k,
+                                                float(sigma2), float(w), 1 if reference_form else 0, None,
+                                                keys.shape[0], ptr(nsum), ptr(gsum)))
+    return (_assemble_normal(seg_a, seg_b, nsum, k, reference_form),
+            _assemble_gradient(seg_a, seg_b, gsum, k, reference_form)[0])
 
 
 def registration_filterreg(source, target, target_normals=None, sigma2=None, update_sigma2=False, w=0,

@@ -3,8 +3,10 @@
 These are small host-side value objects (a 3x3 matrix, a vector, an M x D weight matrix); the
 per-iteration transform of the *source cloud* inside the EM loop runs fused on the GPU
 (``k_transform_linear`` / ``k_gw`` in csrc/), not through these classes.
+``DeformableKinematicModel`` (transformation.py:163-212) skins its points on the GPU (``prg_dq_skin``).
 """
 import abc
+import itertools
 
 import numpy as np
 
@@ -160,3 +162,124 @@ class TPSTransformation(Transformation):
     def _transform(self, points):
         basis, _ = self.prepare(points)
         return self.transform_basis(basis)
+
+
+# ---- dual quaternions: 8 doubles (r_w, r_x, r_y, r_z, d_w, d_x, d_y, d_z) -------------------
+def _quat_mul(a, b):
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return np.array([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw])
+
+
+def dualquat_identity(k=None):
+    """The identity dual quaternion, or a (k, 8) array of them."""
+    one = np.array([1.0, 0, 0, 0, 0, 0, 0, 0])
+    return one if k is None else np.tile(one, (int(k), 1))
+
+
+def dualquat_from_rt(rot, t):
+    """Dual quaternion of x -> R x + t: ``rot`` a 3 x 3 rotation matrix or a unit quaternion (w, x, y, z); d = (0, t) r / 2."""
+    rot = np.asarray(rot, dtype=np.float64)
+    if rot.shape == (3, 3):
+        # Shepperd's method: the largest of (1 + tr, 1 + 2 R_ii - tr) picks the pivot
+        tr = np.trace(rot)
+        cand = np.array([tr, rot[0, 0], rot[1, 1], rot[2, 2]])
+        i = int(np.argmax(cand))
+        if i == 0:
+            r = np.array([1.0 + tr, rot[2, 1] - rot[1, 2], rot[0, 2] - rot[2, 0], rot[1, 0] - rot[0, 1]])
+        else:
+            a, b, c = i - 1, i % 3, (i + 1) % 3
+            r = np.zeros(4)
+            r[0] = rot[c, b] - rot[b, c]
+            r[1 + a] = 1.0 + 2.0 * rot[a, a] - tr
+            r[1 + b] = rot[b, a] + rot[a, b]
+            r[1 + c] = rot[c, a] + rot[a, c]
+        r = r / np.linalg.norm(r)
+    else:
+        r = rot.reshape(4)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    return np.r_[r, 0.5 * _quat_mul(np.r_[0.0, t], r)]
+
+
+def dualquat_from_twist(tw):
+    """Reference filterreg.py:38-42: rotation by ``|tw[:3]|`` about ``tw[:3]`` (the identity below float32 eps), translation ``tw[3:]``."""
+    tw = np.asarray(tw, dtype=np.float64)
+    ang = np.linalg.norm(tw[:3])
+    if ang < np.finfo(np.float32).eps:
+        return dualquat_from_rt(np.array([1.0, 0.0, 0.0, 0.0]), tw[3:])
+    return dualquat_from_rt(np.r_[np.cos(0.5 * ang), np.sin(0.5 * ang) * tw[:3] / ang], tw[3:])
+
+
+def dualquat_mul(a, b):
+    """``a * b`` (applies ``b`` first): r = a.r b.r, d = a.r b.d + a.d b.r."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.r_[_quat_mul(a[:4], b[:4]), _quat_mul(a[:4], b[4:]) + _quat_mul(a[4:], b[:4])]
+
+
+class DeformableKinematicModel(Transformation):
+    """Dual-quaternion skinning, two nodes per point (reference transformation.py:163-212).
+
+    dualquats : (K, 8) float64 array or a sequence of K length-8 arrays (r_w, r_x, r_y, r_z, d_w, d_x, d_y, d_z) -
+                NOT ``dq3d`` objects (known deviation; ``dualquat_from_rt`` / ``dualquat_from_twist`` build them)
+    weights   : ``DeformableKinematicModel.SkinningWeight`` (``make_weight(pairs, vals)``)
+
+    Point i moves by the blend ``val[0] * dualquats[pair[0]] + val[1] * dualquats[pair[1]]`` divided by the norm of
+    its rotation part (DLB, no antipodal sign correction); ``transform`` runs on the GPU.
+    """
+
+    class SkinningWeight(np.ndarray):
+        """Per point: two node indices ``['pair']`` (i4) and two weights ``['val']`` (f4)  (transformation.py:171-194)."""
+
+        def __new__(cls, n_points):
+            return super(DeformableKinematicModel.SkinningWeight, cls).__new__(
+                cls, n_points, dtype=[("pair", "i4", 2), ("val", "f4", 2)]
+            )
+
+        @property
+        def n_nodes(self):
+            return int(self["pair"].max()) + 1
+
+        def pairs_set(self):
+            return itertools.permutations(range(self.n_nodes), 2)
+
+        def in_pair(self, pair):
+            """Indices of the points whose pair equals the given ordered pair."""
+            return np.argwhere((self["pair"] == pair).all(1)).flatten()
+
+    @classmethod
+    def make_weight(cls, pairs, vals):
+        pairs = np.asarray(pairs)
+        weights = cls.SkinningWeight(pairs.shape[0])
+        weights["pair"] = pairs
+        weights["val"] = vals
+        return weights
+
+    def __init__(self, dualquats, weights):
+        super(DeformableKinematicModel, self).__init__()
+        self.weights = weights
+        self.dualquats = np.array([np.asarray(q, dtype=np.float64).reshape(8) for q in dualquats]).reshape(-1, 8)
+        pair = np.asarray(weights["pair"])
+        if pair.size and (pair.min() < 0 or pair.max() >= self.dualquats.shape[0]):
+            raise ValueError("skinning weights name a node outside [0, %d)." % self.dualquats.shape[0])
+
+    def _transform(self, points):
+        import ctypes
+
+        from . import _lib
+        from .engine import _current_device_and_stream
+
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError("DeformableKinematicModel moves (n, 3) points.")
+        if points.shape[0] != self.weights.shape[0]:
+            raise ValueError("%d points for %d skinning weights." % (points.shape[0], self.weights.shape[0]))
+        _lib.require_gpu()
+        dev, st = _current_device_and_stream()
+        pairs = np.ascontiguousarray(self.weights["pair"], dtype=np.int32)
+        vals = np.ascontiguousarray(self.weights["val"], dtype=np.float32)
+        dq = np.ascontiguousarray(self.dualquats, dtype=np.float64)
+        out = np.empty_like(points)
+        _lib.check(_lib.lib.prg_dq_skin(dev, ctypes.c_void_p(st), _lib.ptr(points), points.shape[0], _lib.ptr(pairs),
+                                        _lib.ptr(vals), _lib.ptr(dq), dq.shape[0], _lib.ptr(out)))
+        return out
