@@ -18,6 +18,8 @@ constexpr int kBlock = 256;
 // G[i][j] = exp(-|y_i - y_j|^2 / (2 beta)) in float32: squared distance in float32 without FMA
 // contraction (as the reference's Eigen expression), exponential in fp64 rounded once.
 // KIND 1: inverse multiquadric 1 / sqrt(d2 + c), all float32 (cc/math_utils.cc:32-34; BCPD's kernel, bcpd.py:107).
+// The square root is __builtin_sqrtf, which the compiler rounds correctly; __fsqrt_rn is the bare hardware estimate
+// (1 ulp) in this toolchain and left entries one float32 ulp from the reference's matrix.
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_build_g(const float4* __restrict__ src4, int64_t m, float two_beta,
                                                     float* __restrict__ g) {
@@ -32,7 +34,7 @@ __global__ __launch_bounds__(kBlock) void k_build_g(const float4* __restrict__ s
         if (KIND == 0)
             g[i * m + j] = (float)exp((double)__fdiv_rn(-d2, two_beta));
         else  // two_beta carries c
-            g[i * m + j] = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(d2, two_beta)));
+            g[i * m + j] = __fdiv_rn(1.f, __builtin_sqrtf(__fadd_rn(d2, two_beta)));
     }
 }
 

@@ -12,6 +12,13 @@
 // S is factored by a right-looking blocked Cholesky (NB = 128) whose trailing update and panel
 // solve are NT-GEMMs on v_mfma_f64_16x16x4_f64; everything is fp64 because cond(S) reaches 1e7-1e8
 // (c ~ 1e-3, lambda_max(G) ~ M) which rules out an fp32 factorisation at the 1e-4 parity target.
+//
+// Tests that hold each path to round-off level (8 x the disagreement of two float64 host solves; tests/test_dense_solve_gpu.py):
+//   dense M-step, every class of the look-ahead schedule     test_dense_mstep_per_schedule_class, test_rows_without_support
+//   correspondence priors and their two refinement steps      test_constrained_mstep_dense, test_constrained_mstep_lowrank
+//   prg_cpd_bcpd_solve (K-deep left update, second panel)     test_bcpd_solve
+//   non-positive pivots: immediate report / sticky flag       test_dense_path_reports_..., test_lowrank_path_reports_...
+//   low-rank M-step                                           tests/test_nonrigid_lowrank_gpu.py (1e-7 on the exact matrix)
 #include <math.h>
 
 #include <algorithm>
@@ -498,25 +505,47 @@ __global__ __launch_bounds__(kBlock) void k_tri_solve3(const double* __restrict_
 }
 
 // ---- block triangular solves with 3 right-hand sides ----------------------------------------------
-// x_k = Linv_k * v_k (TRANS = 0) or Linv_k^T * v_k (TRANS = 1); v, x are [mp][3] row-major.
+// L_k x = v_k (TRANS = 0) or L_k^T x = v_k (TRANS = 1) for the diagonal block at k0; v, x are [mp][3] row-major.
+// x0 = Linv_k v_k alone is only conditionally stable: its residual grows with cond(L_k) (~1e3 late in a registration),
+// where substitution's does not, and G W came out a digit further from LAPACK than W itself.  One step of refinement
+// against the factor, x = x0 + Linv_k (v_k - L_k x0), brings the block solve to substitution level at the price of two
+// more 128 x 128 products in a kernel that is bound by its launch.
 template <int TRANS>
-__global__ __launch_bounds__(384) void k_diag_solve(const double* __restrict__ linv, double* __restrict__ v,
-                                                    int64_t k0) {
-    __shared__ double vin[NB][3];
+__global__ __launch_bounds__(384) void k_diag_solve(const double* __restrict__ linv, const double* __restrict__ s,
+                                                    int64_t ld, double* __restrict__ v, int64_t k0) {
+    __shared__ double vin[NB][3], x0[NB][3];
     const int r = threadIdx.x / 3, c = threadIdx.x % 3;
-    vin[r][c] = v[(k0 + r) * 3 + c];
+    const double* __restrict__ lblk = s + k0 * ld + k0;  // L_k in the lower triangle (above it: what S held before)
+    const double vr = v[(k0 + r) * 3 + c];
+    vin[r][c] = vr;
     __syncthreads();
-    double s = 0.0;
-    // the upper triangle of linv is stored as explicit zeros, so both loops can run over all 128 terms
+    // the upper triangle of linv is stored as explicit zeros, so the loops can run over all 128 terms
     // with independent loads (unrolled, pipelined) instead of a data-dependent trip count
+    auto apply_inverse = [&]() {
+        double acc = 0.0;
+        if (TRANS == 0) {
+#pragma unroll 16
+            for (int k = 0; k < NB; ++k) acc += linv[r * NB + k] * vin[k][c];
+        } else {
+#pragma unroll 16
+            for (int k = 0; k < NB; ++k) acc += linv[k * NB + r] * vin[k][c];
+        }
+        return acc;
+    };
+    const double xr = apply_inverse();
+    x0[r][c] = xr;
+    __syncthreads();
+    double res = vr;
     if (TRANS == 0) {
 #pragma unroll 16
-        for (int k = 0; k < NB; ++k) s += linv[r * NB + k] * vin[k][c];
+        for (int k = 0; k < NB; ++k) res = fma(-(k <= r ? lblk[(int64_t)r * ld + k] : 0.0), x0[k][c], res);
     } else {
 #pragma unroll 16
-        for (int k = 0; k < NB; ++k) s += linv[k * NB + r] * vin[k][c];
+        for (int k = 0; k < NB; ++k) res = fma(-(k >= r ? lblk[(int64_t)k * ld + r] : 0.0), x0[k][c], res);
     }
-    v[(k0 + r) * 3 + c] = s;
+    vin[r][c] = res;  // (every thread read its own entry of vin only since the barrier)
+    __syncthreads();
+    v[(k0 + r) * 3 + c] = xr + apply_inverse();
 }
 
 // forward (right-looking): v[i] -= sum_c L[i][k0 + c] * x_k[c] for rows i >= k0 + 128.
@@ -896,13 +925,13 @@ int cholesky_solve3(prg_cpd* h, const double* S, int64_t mp, const double* linv,
     const int64_t nblk = mp / NB;
     for (int64_t kb = 0; kb < nblk; ++kb) {  // L u' = v
         const int64_t k0 = kb * NB;
-        k_diag_solve<0><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, v, k0);
+        k_diag_solve<0><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, S, mp, v, k0);
         const int64_t rows = mp - k0 - NB;
         if (rows > 0) k_fwd_update<<<(unsigned)prg::ceil_div(rows, 64), kBlock, 0, st>>>(S, mp, k0, mp, v);
     }
     for (int64_t kb = nblk - 1; kb >= 0; --kb) {  // L^T u = u'
         const int64_t k0 = kb * NB;
-        k_diag_solve<1><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, v, k0);
+        k_diag_solve<1><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, S, mp, v, k0);
         if (k0 > 0) k_bwd_update<<<grid1(k0), kBlock, 0, st>>>(S, mp, k0, v);
     }
     PRG_HIP(hipGetLastError());
@@ -1092,13 +1121,13 @@ extern "C" int prg_cpd_mstep_nonrigid(prg_cpd* h, double lmd) {
         if (mp > m) PRG_HIP(hipMemsetAsync(v + m * 3, 0, (size_t)(mp - m) * 3 * sizeof(double), st));
         for (int64_t kb = 0; kb < nblk; ++kb) {                   // L u' = v
             const int64_t k0 = kb * NB;
-            k_diag_solve<0><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, v, k0);
+            k_diag_solve<0><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, S, mp, v, k0);
             const int64_t rows = mp - k0 - NB;
             if (rows > 0) k_fwd_update<<<(unsigned)prg::ceil_div(rows, 64), kBlock, 0, st>>>(S, mp, k0, mp, v);
         }
         for (int64_t kb = nblk - 1; kb >= 0; --kb) {              // L^T u = u'
             const int64_t k0 = kb * NB;
-            k_diag_solve<1><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, v, k0);
+            k_diag_solve<1><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, S, mp, v, k0);
             if (k0 > 0) k_bwd_update<<<grid1(k0), kBlock, 0, st>>>(S, mp, k0, v);
         }
         k_form_w<<<grid1(m), kBlock, 0, st>>>(rhs, sp, v, m, h->params, lmd, wout);
@@ -1287,13 +1316,13 @@ extern "C" int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const dou
     if (mp > m) PRG_HIP(hipMemsetAsync(v + m * 3, 0, (size_t)(mp - m) * 3 * sizeof(double), st));
     for (int64_t kb = 0; kb < nblk; ++kb) {
         const int64_t k0 = kb * NB;
-        k_diag_solve<0><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, v, k0);
+        k_diag_solve<0><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, S, mp, v, k0);
         const int64_t rows = mp - k0 - NB;
         if (rows > 0) k_fwd_update<<<(unsigned)prg::ceil_div(rows, 64), kBlock, 0, st>>>(S, mp, k0, mp, v);
     }
     for (int64_t kb = nblk - 1; kb >= 0; --kb) {
         const int64_t k0 = kb * NB;
-        k_diag_solve<1><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, v, k0);
+        k_diag_solve<1><<<1, 384, 0, st>>>(linv + (size_t)kb * NB * NB, S, mp, v, k0);
         if (k0 > 0) k_bwd_update<<<grid1(k0), kBlock, 0, st>>>(S, mp, k0, v);
     }
     k_scale_rows<<<grid1(m), kBlock, 0, st>>>(sp, v, m, tv);

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_weighted(const float* __restric
     out[i] = v;
 }
 
-// K[i][j] = 1 / sqrt(|x_i - y_j|^2 + c), all float32 (cc/math_utils.cc:32-34)
+// K[i][j] = 1 / sqrt(|x_i - y_j|^2 + c), all float32 (cc/math_utils.cc:32-34); correctly rounded square root, see k_build_g
 __global__ __launch_bounds__(kBlock) void k_imq(const float* __restrict__ x, int64_t m, const float* __restrict__ y,
                                                 int64_t n, int dim, float c, float* __restrict__ out) {
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(kBlock) void k_imq(const float* __restrict__ x, int
         const float dx = __fsub_rn(x[i * dim], yx), dy = __fsub_rn(x[i * dim + 1], yy),
                     dz = dim > 2 ? __fsub_rn(x[i * dim + 2], yz) : 0.f;
         const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-        out[i * n + j] = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(d2, c)));
+        out[i * n + j] = __fdiv_rn(1.f, __builtin_sqrtf(__fadd_rn(d2, c)));
     }
 }
 

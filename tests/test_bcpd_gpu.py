@@ -169,6 +169,8 @@ def test_math_utils_helpers():
     k = mu.inverse_multiquadric_kernel(src[:300], tgt[:200], 0.7)
     assert k.dtype == np.float32 and k.shape == (300, 200)
     assert rel_err(k, bo.inverse_multiquadric_kernel(src[:300], tgt[:200], 0.7)) < 3e-7
+    # (every float32 operation of it is correctly rounded, the square root included: the oracle's bits)
+    assert np.array_equal(k, bo.inverse_multiquadric_kernel(src[:300], tgt[:200], 0.7))
     want = np.sum(cKDTree(tgt).query(src)[0]) / src.shape[0]
     assert abs(mu.compute_rmse(src, tgt) - want) < 1e-6 * want
     assert abs(mu.compute_rmse(src + 1000.0, cKDTree(tgt + 1000.0)) - want) < 1e-5 * want  # tree accepted, offsets centred
