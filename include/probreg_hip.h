@@ -341,6 +341,39 @@ int prg_inverse_multiquadric_kernel(int device, void* hip_stream, const float* x
 int prg_nn_mean_distance(int device, void* hip_stream, const float* a_hd, int64_t m, const float* b_hd, int64_t n,
                          int dim, double* out_host);
 
+/* ---- CPD batch plan: many small rigid / affine registrations per launch (csrc/cpd_batch.hip) ---- */
+/* Replaces a host loop over registration_cpd (cpd.py:407-456), i.e. B runs of the EM driver cpd.py:106-120, by one plan whose
+ * launch count per EM iteration does not depend on B; the reference has no batched interface.  Problem b keeps the semantics of
+ * its own registration: closed-form sigma2 initialiser and q0 (cpd.py:145-153 / 209-217), E-step cpd.py:71-88, M-step
+ * cpd.py:160-192 / 219-244, and the convergence test |q - q_prev| < tol_b of cpd.py:115-117, taken on the device. */
+typedef struct prg_cpd_batch prg_cpd_batch;
+/* Host only: the tile width (target columns per sweep workgroup) and the source-chunk length of the batch sweep. */
+int prg_cpd_batch_tile_shape(int* tile_columns, int* source_chunk);
+/* Host only: the sweep's tile table for problems of m[b] source and n[b] target points, as (problem, first column, column count)
+ * triples in launch order; *ntiles is their number, tiles_out (may be NULL) receives up to `capacity` of them.  A problem's tiles
+ * depend on its own sizes only. */
+int prg_cpd_batch_tile_table(int nb, const int64_t* m, const int64_t* n, int* tiles_out, int64_t capacity, int64_t* ntiles);
+/* nb problems in `dim` dimensions: problem b owns source points [source_offsets[b], source_offsets[b+1]) of the packed host array
+ * `sources` ([total][dim] doubles) and the same for the target.  The caller has centred every cloud on its own fp64 mean, as
+ * cpd.py of this project does for one problem (the points are stored as fp32). */
+int prg_cpd_batch_create(prg_cpd_batch** out, int device, void* hip_stream, int dim, int nb, const int64_t* source_offsets,
+                         const int64_t* target_offsets, const double* sources, const double* targets);
+int prg_cpd_batch_destroy(prg_cpd_batch* h);
+/* (Re)starts every registration: sigma2_0, q_0 (cpd.py:145-153) and the initial transform of every problem in one launch.
+ * init_params_host: NULL (identity) or [nb][16] doubles, per problem PARAMS[0..12] followed by delta = origin_target -
+ * origin_source (the layout prg_cpd_init_params takes for one problem; a rigid problem's linear part must be a rotation). */
+int prg_cpd_batch_init(prg_cpd_batch* h, const double* init_params_host);
+/* Up to n_iter EM iterations (cpd.py:110-117) of every problem still running, two launches per iteration for the whole batch.
+ * w[nb], tol[nb]: host arrays.  A problem stops after the M-step at which |q - q_prev| < tol[b] (the first comparison is against
+ * q_0) and is frozen from then on; tol[b] < 0 never stops.  With every tol[b] < 0 the call only enqueues; otherwise the host reads
+ * the number of running problems once every 8 iterations and stops enqueuing at 0. */
+int prg_cpd_batch_iterate(prg_cpd_batch* h, int kind, int update_scale, const double* w, const double* tol, int n_iter);
+/* Number of problems that have not stopped (synchronises). */
+int prg_cpd_batch_active(prg_cpd_batch* h, int* active);
+/* [nb][PRG_NPARAMS] parameter blocks (centred frames) and, if n_iter_host is not NULL, the EM iterations every problem ran
+ * (synchronises).  Replaces reading MstepResult cpd.py:18 of every registration. */
+int prg_cpd_batch_get_params(prg_cpd_batch* h, double* params_host, int* n_iter_host);
+
 /* ---- permutohedral lattice (Gaussian filtering) --------------------------------------------- */
 /* Replaces the pybind class probreg._permutohedral_lattice.Permutohedral
  * (cc/permutohedral_lattice_py.cc:13-21 over third_party/permutohedral/permutohedral.cpp) behind

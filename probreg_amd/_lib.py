@@ -88,6 +88,14 @@ SIGNATURES = {
     "prg_cpd_set_comm": [_vp, _vp],
     "prg_cpd_iterate": [_vp, _i, _i, _d, _i],
     "prg_cpd_set_moments_only": [_vp, _i],
+    "prg_cpd_batch_tile_shape": [_c.POINTER(_i), _c.POINTER(_i)],
+    "prg_cpd_batch_tile_table": [_i, _vp, _vp, _vp, _i64, _c.POINTER(_i64)],
+    "prg_cpd_batch_create": [_pp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "prg_cpd_batch_destroy": [_vp],
+    "prg_cpd_batch_init": [_vp, _vp],
+    "prg_cpd_batch_iterate": [_vp, _i, _i, _vp, _vp, _i],
+    "prg_cpd_batch_active": [_vp, _c.POINTER(_i)],
+    "prg_cpd_batch_get_params": [_vp, _vp, _vp],
     "prg_cpd_last_estep_fused": [_vp, _c.POINTER(_i)],
     "prg_cpd_set_fused_factor": [_vp, _d],
     "prg_cpd_set_resid_sweep": [_vp, _i],

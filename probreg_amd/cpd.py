@@ -3,7 +3,8 @@
 Same public surface as the reference: ``EstepResult`` / ``MstepResult`` (cpd.py:17-18),
 ``CoherentPointDrift`` with ``set_source`` / ``set_callbacks`` / ``expectation_step`` /
 ``maximization_step`` / ``registration`` (cpd.py:29-120), ``RigidCPD`` (:123-192), ``AffineCPD``
-(:195-244), ``NonRigidCPD`` (:247-303) and ``registration_cpd`` (:407-456).
+(:195-244), ``NonRigidCPD`` (:247-303) and ``registration_cpd`` (:407-456).  ``registration_cpd_batch`` has no counterpart there: many small
+rigid / affine registrations as one plan whose launch count does not depend on their number.
 
 What is different underneath: the E-step (M x N responsibilities, P1, Pt1, PX), the sigma2
 initialiser, the transform of the source and the M-step all run in ``libprobreg_hip.so`` on the
@@ -19,7 +20,7 @@ import numpy as np
 from . import _lib
 from . import dist as pdist
 from . import transformation as tf
-from .engine import CpdPlan
+from .engine import CpdBatchPlan, CpdPlan
 from .log import log
 
 EstepResult = namedtuple("EstepResult", ["pt1", "p1", "px", "n_p"])
@@ -585,3 +586,105 @@ def registration_cpd(source, target, tf_type_name="rigid", w=0.0, maxiter=50, to
         raise ValueError("Unknown transformation type %s" % tf_type_name)
     cpd.set_callbacks(callbacks)
     return cpd.registration(_as_points(target), w, maxiter, tol)
+
+
+def _batch_clouds(x, name):
+    """A sequence of clouds, or one (B, n, D) array, -> list of float64 (n_b, D) arrays."""
+    if isinstance(x, np.ndarray):
+        if x.ndim != 3:
+            raise ValueError("%s: one array for the whole batch must be (B, n, D); got shape %s." % (name, x.shape))
+        return [np.asarray(c, dtype=np.float64) for c in x]
+    try:
+        return [_as_points(c) for c in x]
+    except TypeError:
+        raise ValueError("%s must be a sequence of clouds or one (B, n, D) array." % name)
+
+
+def _per_problem(v, b, name):
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 0:
+        return np.full(b, float(a))
+    if a.shape != (b,):
+        raise ValueError("%s must be a scalar or hold one value per problem (%d); got shape %s." % (name, b, a.shape))
+    return a.copy()
+
+
+def registration_cpd_batch(sources, targets, tf_type_name="rigid", w=0.0, maxiter=50, tol=0.001, update_scale=True,
+                           tf_init_params=None, device=None, return_n_iter=False):
+    """Many small CPD registrations in one go: problem ``b`` gets what ``registration_cpd(sources[b], targets[b],
+    tf_type_name, w_b, maxiter, tol_b, update_scale=..., tf_init_params=...)`` defines, but the whole batch runs as one GPU plan -
+    one launch for every problem's initialisation, two per EM iteration, whatever the number of problems - and the convergence
+    test ``|q - q_prev| < tol_b`` is taken on the device.
+
+    sources, targets : sequences of (M_b, D) / (N_b, D) arrays or Open3D clouds, or one (B, M, D) array each; the clouds are
+                       ragged (every problem its own M_b, N_b >= 1), D is 2 or 3 and the same for the whole batch
+    tf_type_name     : 'rigid' | 'affine' (non-rigid needs an M x M solve per problem and is not batched)
+    w, tol           : a scalar, or one value per problem; a problem stops after the M-step at which |q - q_prev| < tol_b and
+                       is frozen while the others go on, tol_b < 0 never stops early
+    maxiter          : most EM iterations any problem runs
+    update_scale     : rigid only, as in ``RigidCPD``
+    tf_init_params   : None, one dict for all problems, or one dict per problem (keys of ``RigidCPD`` / ``AffineCPD``)
+    device           : GPU index; defaults to the calling process's current torch device
+    There are no callbacks.  Returns a list of ``MstepResult(transformation, sigma2, q)`` in input order; with
+    ``return_n_iter=True`` also an int64 array of the EM iterations every problem ran.  A problem whose affine system is singular
+    raises ``np.linalg.LinAlgError`` naming its index.  Under torchrun (torch.distributed initialised) nothing is sharded: every
+    rank runs the batch it was given.
+    """
+    if tf_type_name not in ("rigid", "affine"):
+        raise ValueError("registration_cpd_batch: tf_type_name must be 'rigid' or 'affine', got %r." % (tf_type_name,))
+    src = _batch_clouds(sources, "sources")
+    tgt = _batch_clouds(targets, "targets")
+    nb = len(src)
+    if nb == 0 or len(tgt) != nb:
+        raise ValueError("registration_cpd_batch: need as many targets as sources and at least one (got %d and %d)."
+                         % (nb, len(tgt)))
+    dim = src[0].shape[1] if src[0].ndim == 2 else -1
+    if dim not in (2, 3):
+        raise ValueError("registration_cpd_batch: clouds must be (n, 2) or (n, 3) arrays.")
+    for i, (s, t) in enumerate(zip(src, tgt)):
+        for name, c in (("source", s), ("target", t)):
+            if c.ndim != 2 or c.shape[1] != dim:
+                raise ValueError("registration_cpd_batch: %s %d has shape %s; every cloud of the batch must be (n, %d)."
+                                 % (name, i, c.shape, dim))
+            if c.shape[0] < 1:
+                raise ValueError("registration_cpd_batch: %s %d is empty." % (name, i))
+    wv = _per_problem(w, nb, "w")
+    tolv = _per_problem(tol, nb, "tol")
+    if np.any(~(wv >= 0.0)) or np.any(~(wv < 1.0)):
+        raise ValueError("registration_cpd_batch: w must lie in [0, 1).")
+    if tf_init_params is None or isinstance(tf_init_params, dict):
+        inits = [tf_init_params or {}] * nb
+    else:
+        inits = [ip or {} for ip in tf_init_params]
+        if len(inits) != nb:
+            raise ValueError("registration_cpd_batch: tf_init_params holds %d dicts for %d problems." % (len(inits), nb))
+    rigid = tf_type_name == "rigid"
+    maxiter = int(maxiter)
+    # centred frames, as for one problem: z - cx = s R (y - cy) + t'  with  t' = t + s R cy - cx
+    cys = [s.mean(axis=0) for s in src]
+    cxs = [t.mean(axis=0) for t in tgt]
+    blocks = np.empty((nb, 16))
+    for i, ip in enumerate(inits):
+        lin = np.asarray(ip.get("rot" if rigid else "b", np.identity(dim)), dtype=np.float64)
+        t = np.asarray(ip.get("t", np.zeros(dim)), dtype=np.float64)
+        scale = float(ip.get("scale", 1.0)) if rigid else 1.0
+        blocks[i] = _params_block(lin, t + scale * lin @ cys[i] - cxs[i], scale, dim, cxs[i] - cys[i])
+    _lib.require_gpu()
+    plan = CpdBatchPlan([s - c for s, c in zip(src, cys)], [t - c for t, c in zip(tgt, cxs)], device)
+    try:
+        plan.init(blocks)
+        if maxiter > 0:
+            plan.iterate(_lib.PRG_TF_RIGID if rigid else _lib.PRG_TF_AFFINE, update_scale, wv, tolv, maxiter)
+        params, n_iter = plan.get_params()
+    finally:
+        plan.close()
+    out = []
+    for i in range(nb):
+        if rigid:
+            out.append(_rigid_result(params[i], dim, cys[i], cxs[i]))
+        else:
+            try:
+                out.append(_affine_result(params[i], dim, cys[i], cxs[i]))
+            except np.linalg.LinAlgError:
+                raise np.linalg.LinAlgError("Singular matrix in problem %d of the batch" % i)
+    return (out, n_iter) if return_n_iter else out

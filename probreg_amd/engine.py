@@ -332,3 +332,88 @@ class CpdPlan(object):
     def synchronize(self):
         # a host read-back of the parameter block synchronises the plan's stream
         self.get_params()
+
+
+def batch_tile_shape():
+    """(target columns per tile, source points per chunk) of the batch sweep (prg_cpd_batch_tile_shape; host arithmetic)."""
+    a, b = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.prg_cpd_batch_tile_shape(ctypes.byref(a), ctypes.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def batch_tile_table(m, n):
+    """The batch sweep's tile table for problems of ``m[b]`` source and ``n[b]`` target points: an (ntiles, 3) int32 array of
+    (problem, first column, column count) in launch order (prg_cpd_batch_tile_table; host arithmetic, no GPU needed)."""
+    m = np.ascontiguousarray(m, dtype=np.int64)
+    n = np.ascontiguousarray(n, dtype=np.int64)
+    if m.ndim != 1 or m.shape != n.shape:
+        raise ValueError("batch_tile_table: m and n must be equally long 1-D size lists.")
+    count = ctypes.c_int64(0)
+    check(lib.prg_cpd_batch_tile_table(int(m.size), ptr(m), ptr(n), None, 0, ctypes.byref(count)))
+    out = np.empty((int(count.value), 3), dtype=np.int32)
+    check(lib.prg_cpd_batch_tile_table(int(m.size), ptr(m), ptr(n), ptr(out), int(count.value), ctypes.byref(count)))
+    return out
+
+
+class CpdBatchPlan(object):
+    """Owns one ``prg_cpd_batch`` handle: B rigid / affine registrations of ragged clouds on one GPU, one HIP stream.
+
+    sources, targets : lists of centred (M_b, D) / (N_b, D) float64 arrays (every cloud minus its own mean)
+    """
+
+    def __init__(self, sources, targets, device=None, stream=None):
+        _lib.require_gpu()
+        dev, st = _current_device_and_stream(device)
+        if stream is not None:
+            st = int(stream)
+        self.device = dev
+        self.stream = st
+        self.b = len(sources)
+        self.dim = int(sources[0].shape[1])
+        soff = np.zeros(self.b + 1, dtype=np.int64)
+        toff = np.zeros(self.b + 1, dtype=np.int64)
+        soff[1:] = np.cumsum([s.shape[0] for s in sources])
+        toff[1:] = np.cumsum([t.shape[0] for t in targets])
+        src = np.ascontiguousarray(np.concatenate(sources, axis=0), dtype=np.float64)
+        tgt = np.ascontiguousarray(np.concatenate(targets, axis=0), dtype=np.float64)
+        self._h = ctypes.c_void_p()
+        check(lib.prg_cpd_batch_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st), self.dim, self.b, ptr(soff), ptr(toff),
+                                       ptr(src), ptr(tgt)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib.prg_cpd_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+    def init(self, init16=None):
+        """Start (or restart) every registration; ``init16``: None or (B, 16) blocks as ``CpdPlan.init_params`` takes one."""
+        if init16 is not None:
+            init16 = np.ascontiguousarray(init16, dtype=np.float64)
+            assert init16.shape == (self.b, 16)
+        check(lib.prg_cpd_batch_init(self._h, ptr(init16)))
+
+    def iterate(self, kind, update_scale, w, tol, n_iter):
+        """Up to ``n_iter`` EM iterations of every running problem; ``w`` / ``tol``: (B,) arrays (prg_cpd_batch_iterate)."""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        tol = np.ascontiguousarray(tol, dtype=np.float64)
+        assert w.shape == (self.b,) and tol.shape == (self.b,)
+        check(lib.prg_cpd_batch_iterate(self._h, int(kind), 1 if update_scale else 0, ptr(w), ptr(tol), int(n_iter)))
+
+    def active(self):
+        """Number of problems that have not stopped (synchronises)."""
+        a = ctypes.c_int(0)
+        check(lib.prg_cpd_batch_active(self._h, ctypes.byref(a)))
+        return int(a.value)
+
+    def get_params(self):
+        """((B, PRG_NPARAMS) parameter blocks, (B,) int64 EM iterations run); synchronises."""
+        out = np.empty((self.b, _lib.PRG_NPARAMS), dtype=np.float64)
+        it = np.empty(self.b, dtype=np.int32)
+        check(lib.prg_cpd_batch_get_params(self._h, ptr(out), ptr(it)))
+        return out, it.astype(np.int64)
