@@ -160,18 +160,27 @@ def log_likelihood(points, nodes, pre, j0, jn):
 
 def build(points, tree_level, idx, lambda_s=0.001, lambda_d=1.0e-4, max_iter=1000, trace=False):
     """buildGmmTree (:98-123).  Returns (nodes, info) with per level: iterations, the q of every iteration, the minimum
-    top-two gamma gap of every E-step."""
+    top-two gamma gap of every E-step.  With ``trace`` also, per level and E-step, the m0 of all nodes ("m0") and the
+    assignment ``current`` ("cur")."""
     points = np.asarray(points, dtype=np.float64)
     nodes = init_nodes(points, tree_level, idx)
     parent = -np.ones(points.shape[0], dtype=np.int64)
     info = {"iters": [], "q": [], "gap": []}
+    if trace:
+        info["m0"], info["cur"] = [], []
     for l in range(tree_level):
         prev_q = 0.0
         qs, gaps = [], []
+        if trace:
+            info["m0"].append([])
+            info["cur"].append([])
         while True:
             pre = precompute(nodes)
             (m0, m1, m2), cur, gap = build_estep(points, nodes, pre, parent)
             lb, le = level(l), level(l + 1)
+            if trace:
+                info["m0"][l].append(m0.copy())
+                info["cur"][l].append(cur.copy())
             nodes[lb:le] = ml_estimator(m0[lb:le], m1[lb:le], m2[lb:le], points.shape[0], lambda_d)
             q = log_likelihood(points, nodes, precompute(nodes), lb, le)
             qs.append(q)
