@@ -299,12 +299,26 @@ int prg_cpd_set_source_weights(prg_cpd* h, const double* log_weights_hd, double 
  * bcpd.py:107) and BCPD mode: the transform becomes z = s R (y + v_hat) + t (CombinedTransformation) with the
  * v_hat of the last prg_cpd_bcpd_solve (0 before the first). */
 int prg_cpd_bcpd_build_g(prg_cpd* h, double c);
+/* How the next prg_cpd_bcpd_build_g holds the coherence kernel of bcpd.py:107 and how prg_cpd_bcpd_solve then evaluates
+ * bcpd.py:123-129 (no counterpart in the reference, which always forms the M x M matrix and inverts it twice):
+ *   mode 0 (default)  the dense float32 matrix and the M x M fp64 Cholesky below;
+ *   mode 1            the pivoted-Cholesky factor G = F F^T (fp64, M x r, every entry of G - F F^T <= tol) and an r x r
+ *                     solve, O(M r^2) per M-step and no M x M array at all; prg_cpd_bcpd_build_g fails with
+ *                     PRG_ERR_INVALID, naming the rank and the residual reached, when tol is not met within max_rank -
+ *                     a cloud much larger than the coherence length sqrt(c) has no such factor;
+ *   mode 2            the factor when it converges, the dense matrix otherwise.
+ * max_rank: 0 = min(2048, M / 2), otherwise at most 2048 (and M); tol: 0 = 1e-11.  prg_cpd_nonrigid_rank reports the
+ * rank of the factor a BCPD plan holds (0: dense).  The factor truncates G: the results move by about
+ * cfac * nu * tol / lmd relative, so tol has to stay small against lmd / (cfac * nu). */
+int prg_cpd_bcpd_set_solver(prg_cpd* h, int mode, int max_rank, double tol);
 /* Core of CombinedBCPD._maximization_step (bcpd.py:123-133) for nu = nu_hd ([m] float64, caller's order) or, when
  * nu_hd is NULL, the p1 of the last E-step:
  *   Sigma = (lmd G^-1 + cfac diag(nu))^-1,  v_hat = cfac * Sigma * diag(nu) * resid   (resid = T^-1(x_hat) - y),
  * returned as v_hat [m x dim] and diag(Sigma) [m] (float64, caller's point order); v_hat also stays on the
  * device for the next transform.  Woodbury form on S = (lmd/cfac) I + D^1/2 G D^1/2 - no G^-1, no M x M inverse:
- * fp64 Cholesky + a triangular solve with M right-hand sides on the matrix cores (4/3 M^3 flop). */
+ * fp64 Cholesky + a triangular solve with M right-hand sides on the matrix cores (4/3 M^3 flop).
+ * On a plan that holds the factor (prg_cpd_bcpd_set_solver): Sigma = F A^-1 F^T / lmd with the r x r matrix
+ * A = I + (cfac/lmd) F^T D F = L L^T, v_hat = (cfac/lmd) F A^-1 F^T D resid and Sigma_mm = |L^-1 f_m|^2 / lmd. */
 int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const double* nu_hd, const double* resid_hd,
                        double* vhat_hd, double* sigma_diag_hd);
 

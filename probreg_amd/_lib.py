@@ -124,6 +124,7 @@ SIGNATURES = {
     "prg_cpd_mstep_nonrigid": [_vp, _d],
     "prg_cpd_set_source_weights": [_vp, _vp, _d],
     "prg_cpd_bcpd_build_g": [_vp, _d],
+    "prg_cpd_bcpd_set_solver": [_vp, _i, _i, _d],
     "prg_cpd_bcpd_solve": [_vp, _d, _d, _vp, _vp, _vp, _vp],
     "prg_gauss_transform_direct": [_i, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _d, _vp],
     "prg_gauss_transform_direct_f64": [_i, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _d, _vp],

@@ -11,6 +11,12 @@ What runs where
     ``Sigma diag(nu) R``; both come from one fp64 Cholesky + triangular solve on the GPU (Woodbury form, no
     ``G^-1``, no M x M inverse, no (MD) x (MD) Kronecker matrices) - ``prg_cpd_bcpd_solve``.  The remaining O(M + N)
     algebra (digamma, D x D SVD, sigma2) is numpy on the host, as in the reference.
+    With ``solver="lowrank"`` the plan holds the kernel as its pivoted-Cholesky factor ``G = F F^T`` (M x r) and the
+    M-step solves an r x r system: O(M r^2) and no M x M array, which is what lets 1e5 - 1e6 points run at all.  The rank
+    follows the extent of the cloud in units of the kernel's coherence length (1, as the reference hard-codes), not M:
+    about 500 at an extent of 2, no usable factor at an extent of 20 - there ``"lowrank"`` raises and ``"auto"`` keeps
+    the dense matrix.  The factor truncates G by ``kernel_tol`` per entry, which moves the results by about
+    ``c nu kernel_tol / lmd`` (c = s^2 / sigma2^2): the default 1e-11 keeps that far below the float32 E-step.
   * Convergence criterion (bcpd.py:93): brute-force nearest neighbours on the GPU instead of a cKDTree.
 
 Differences a caller can see: ``MstepResult.sigma_mat`` is ``diag(Sigma)`` (length M) - ``expectation_step`` accepts
@@ -166,22 +172,49 @@ class CombinedBCPD(BayesianCoherentPointDrift):
     lmd   : weight of the motion-coherence prior (multiplies G^-1)
     k     : Dirichlet concentration of the mixing weights (1e20 = effectively uniform alpha)
     gamma : scale of the initial sigma2
+    solver     : "dense" (default) - the M x M kernel matrix; "lowrank" - its pivoted-Cholesky factor, ValueError when
+                 the kernel of this source is not low rank; "auto" - the factor when it converges, else the dense matrix
+    kernel_tol : largest entry of G - F F^T the factor may leave
+    max_rank   : rank at which the factor gives up (None: min(2048, M / 2); at most min(2048, M))
     """
 
-    def __init__(self, source=None, lmd=2.0, k=1.0e20, gamma=1.0, device=None):
+    _SOLVERS = {"dense": 0, "lowrank": 1, "auto": 2}
+
+    def __init__(self, source=None, lmd=2.0, k=1.0e20, gamma=1.0, device=None, solver="dense", kernel_tol=1e-11,
+                 max_rank=None):
         super(CombinedBCPD, self).__init__(source, device)
         self._tf_type = tf.CombinedTransformation
         self.lmd = lmd
         self.k = k
         self.gamma = gamma
+        if solver not in self._SOLVERS:
+            raise ValueError("solver must be 'dense', 'lowrank' or 'auto' (got %r)" % (solver,))
+        if not kernel_tol > 0.0:
+            raise ValueError("kernel_tol must be > 0 (got %r)" % (kernel_tol,))
+        if max_rank is not None and not 1 <= int(max_rank) <= 2048:
+            raise ValueError("max_rank must be None or in [1, 2048] (got %r)" % (max_rank,))
+        self.solver = solver
+        self.kernel_tol = float(kernel_tol)
+        self.max_rank = None if max_rank is None else int(max_rank)
+
+    @property
+    def kernel_rank(self):
+        """Rank of the kernel factor the plan holds; 0 when it holds the dense matrix."""
+        return self._ensure_plan().nonrigid_rank()
 
     def _ensure_plan(self):
         """Plan with the (centred) source and its inverse-multiquadric kernel on the GPU."""
         if self._plan is None:
             self._cy = self._source.mean(axis=0)
             plan = CpdPlan(self._device)
-            plan.set_source(self._source - self._cy)
-            plan.bcpd_build_g(1.0)  # bcpd.py:107 - mu.inverse_multiquadric_kernel(source, source), c = 1
+            try:
+                plan.set_source(self._source - self._cy)
+                if self.solver != "dense":
+                    plan.bcpd_set_solver(self._SOLVERS[self.solver], self.max_rank or 0, self.kernel_tol)
+                plan.bcpd_build_g(1.0)  # bcpd.py:107 - mu.inverse_multiquadric_kernel(source, source), c = 1
+            except Exception:
+                plan.close()
+                raise
             self._plan = plan
         return self._plan
 
@@ -243,7 +276,7 @@ def registration_bcpd(source, target, w=0.0, maxiter=50, tol=0.001, callbacks=()
 
     source, target : (n, 2|3) arrays or Open3D point clouds;  w : outlier mass in [0, 1)
     maxiter, tol   : stop after maxiter iterations or when the mean nearest-neighbour distance changes by < tol
-    **kwargs       : ``lmd``, ``k``, ``gamma`` of :class:`CombinedBCPD` (and ``device``)
+    **kwargs       : ``lmd``, ``k``, ``gamma``, ``solver``, ``kernel_tol``, ``max_rank`` of :class:`CombinedBCPD` (and ``device``)
     """
     bcpd = CombinedBCPD(_as_points(source), **kwargs)
     bcpd.set_callbacks(list(callbacks))

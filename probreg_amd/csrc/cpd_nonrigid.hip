@@ -130,6 +130,8 @@ __global__ __launch_bounds__(kBlock) void k_unsort4(const float4* __restrict__ i
 // cloud -> rank ~180 at 1e-14, whatever M).  Greedy pivoted Cholesky with the columns evaluated on the fly in fp64:
 //     step j: p = argmax_i d_i ;  F[j][i] = (G_ip - sum_{k<j} F[k][i] F[k][p]) / sqrt(d_p) ;  d_i -= F[j][i]^2
 // G - F F^T is positive semi-definite with diagonal d, so max d bounds every entry of the remainder and sum d its norm.
+// KIND 1: the inverse multiquadric kernel of BCPD, G_ij = 1 / sqrt(|y_i - y_j|^2 + c) in fp64 from the float32 coordinates
+// (diagonal 1 / sqrt(c)); its rank follows the extent of the cloud in units of sqrt(c).
 // One launch per step: every workgroup re-derives the pivot from the per-workgroup maxima the previous step left.
 struct PcholState {
     int rank;
@@ -167,23 +169,25 @@ __device__ __forceinline__ void block_argmax(double& v, int& i) {
     for (int k = 1; k < kBlock / 64; ++k) argmax_merge(v, i, sv[k], si[k]);
 }
 
-__global__ __launch_bounds__(kBlock) void k_pchol_init(int64_t m, int64_t mp, double* __restrict__ d,
+__global__ __launch_bounds__(kBlock) void k_pchol_init(int64_t m, int64_t mp, double g0, double* __restrict__ d,
                                                        double2* __restrict__ part, PcholState* __restrict__ state) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < mp) d[i] = i < m ? 1.0 : 0.0;  // G_ii = 1
+    if (i < mp) d[i] = i < m ? g0 : 0.0;  // G_ii = g0 (1 for the Gaussian, 1 / sqrt(c) for the inverse multiquadric)
     if (threadIdx.x == 0) {
         const int64_t first = (int64_t)blockIdx.x * kBlock;
-        part[blockIdx.x] = first < m ? make_double2(1.0, (double)first) : make_double2(-1.0, 0.0);
+        part[blockIdx.x] = first < m ? make_double2(g0, (double)first) : make_double2(-1.0, 0.0);
         if (blockIdx.x == 0) {
             state->rank = 0;
             state->done = 0;
-            state->dmax = 1.0;
+            state->dmax = g0;
         }
     }
 }
 
+// kparam: 1 / (2 beta) (KIND 0) or c (KIND 1)
+template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_pchol_step(const float4* __restrict__ src4, int64_t m, int64_t ld,
-                                                       double inv_two_beta, double* __restrict__ f,
+                                                       double kparam, double* __restrict__ f,
                                                        double* __restrict__ d, const double2* __restrict__ part_in,
                                                        double2* __restrict__ part_out, int nblk, int j, double tol,
                                                        PcholState* __restrict__ state, int* __restrict__ piv) {
@@ -207,7 +211,8 @@ __global__ __launch_bounds__(kBlock) void k_pchol_step(const float4* __restrict_
         if (i < m) {
             const float4 yi = src4[i], yp = src4[p];
             const double dx = (double)yi.x - (double)yp.x, dy = (double)yi.y - (double)yp.y, dz = (double)yi.z - (double)yp.z;
-            const double g = exp(-(dx * dx + dy * dy + dz * dz) * inv_two_beta);
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            const double g = KIND == 0 ? exp(-d2 * kparam) : 1.0 / sqrt(d2 + kparam);
             double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
             int k = 0;
             for (; k + 4 <= j; k += 4) {
@@ -332,9 +337,13 @@ int nonrigid_gw(prg_cpd* h, const double* w3, double* out3) {
 }
 
 // G = F F^T by pivoted Cholesky (see k_pchol_step).  On success h->F / f_rank are set; when the rank would exceed
-// max_rank the factor is dropped and *ok = false (the caller falls back to the dense matrix).
-static int build_lowrank_factor(prg_cpd* h, double beta, int max_rank, double tol, bool* ok) {
+// max_rank the factor is dropped and *ok = false (the caller falls back to the dense matrix, or reports the rank and the
+// largest remaining diagonal entry it is given in *reached_rank / *reached_resid).  kind 0: Gaussian, param = beta;
+// kind 1: inverse multiquadric, param = c.
+static int build_lowrank_factor(prg_cpd* h, int kind, double param, int max_rank, double tol, bool* ok,
+                                int* reached_rank = nullptr, double* reached_resid = nullptr) {
     *ok = false;
+    const double g0 = kind == 0 ? 1.0 : 1.0 / sqrt(param), kparam = kind == 0 ? 1.0 / (2.0 * param) : param;
     // rows of the factor are 256 bytes out of step with each other: kernels that walk many columns of F at the same
     // point offset (k_lr_gram's staging, k_lr_ft3, this file's k_pchol_step) would otherwise hit the same memory
     // channels with every row (row stride = a multiple of 8 KB)
@@ -359,8 +368,8 @@ static int build_lowrank_factor(prg_cpd* h, double beta, int max_rank, double to
         prg::set_error("non-rigid kernel factor: %s", what);
         return PRG_ERR_HIP;
     };
-    k_pchol_init<<<nblk, kBlock, 0, h->stream>>>(m, mp, d, part, state);
-    PcholState host = {0, 0, 1.0};
+    k_pchol_init<<<nblk, kBlock, 0, h->stream>>>(m, mp, g0, d, part, state);
+    PcholState host = {0, 0, g0};
     int j = 0;
     const int limit = (int)std::min<int64_t>(max_rank, m);
     cap = std::min(cap, limit);
@@ -380,9 +389,14 @@ static int build_lowrank_factor(prg_cpd* h, double beta, int max_rank, double to
             cap = ncap;
         }
         const int batch = std::min(32, cap - j);
-        for (int b = 0; b < batch; ++b, ++j)
-            k_pchol_step<<<nblk, kBlock, 0, h->stream>>>(h->src4, m, ld, 1.0 / (2.0 * beta), f, d, part + (size_t)(j & 1) * nblk,
-                                                         part + (size_t)((j + 1) & 1) * nblk, nblk, j, tol, state, piv);
+        for (int b = 0; b < batch; ++b, ++j) {
+            const double2* pin = part + (size_t)(j & 1) * nblk;
+            double2* pout = part + (size_t)((j + 1) & 1) * nblk;
+            if (kind == 0)
+                k_pchol_step<0><<<nblk, kBlock, 0, h->stream>>>(h->src4, m, ld, kparam, f, d, pin, pout, nblk, j, tol, state, piv);
+            else
+                k_pchol_step<1><<<nblk, kBlock, 0, h->stream>>>(h->src4, m, ld, kparam, f, d, pin, pout, nblk, j, tol, state, piv);
+        }
         if (hipMemcpyAsync(&host, state, sizeof(PcholState), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess)
             return fail("device error");
@@ -397,7 +411,9 @@ static int build_lowrank_factor(prg_cpd* h, double beta, int max_rank, double to
         double mx = -1.0;
         for (const double2& q : hp) mx = std::max(mx, q.x);
         host.done = mx <= tol;
+        if (reached_resid) *reached_resid = mx;
     }
+    if (reached_rank) *reached_rank = host.rank;
     (void)hipFree(work);
     if (!host.done) {
         (void)hipFree(f);
@@ -422,8 +438,25 @@ int build_kernel_matrix(prg_cpd* h, int kind, double param) {
         int max_rank = h->nr_max_rank > 0 ? h->nr_max_rank : (int)std::min<int64_t>(kMaxRank, m / 2);
         max_rank = std::min(max_rank, kMaxRank);
         bool ok = false;
-        if (max_rank >= 1) PRG_TRY(build_lowrank_factor(h, param, max_rank, h->nr_tol, &ok));
+        if (max_rank >= 1) PRG_TRY(build_lowrank_factor(h, 0, param, max_rank, h->nr_tol, &ok));
         if (ok) return PRG_OK;
+    }
+    if (kind == 1 && h->bcpd_solver != 0) {
+        int max_rank = h->bcpd_max_rank > 0 ? h->bcpd_max_rank : (int)std::min<int64_t>(kMaxRank, m / 2);
+        max_rank = (int)std::min<int64_t>(std::min(max_rank, kMaxRank), m);
+        bool ok = false;
+        int reached = 0;
+        double resid = 1.0 / sqrt(param);  // (nothing factored: the diagonal of G itself)
+        if (max_rank >= 1) PRG_TRY(build_lowrank_factor(h, 1, param, max_rank, h->bcpd_tol, &ok, &reached, &resid));
+        if (ok) return PRG_OK;
+        if (h->bcpd_solver == 1) {
+            nonrigid_free(h);
+            PRG_REQUIRE(false, PRG_ERR_INVALID,
+                        "prg_cpd_bcpd_build_g: the kernel is not low rank: at rank %d (max_rank %d) the largest entry of "
+                        "G - F F^T is still %.3g, above tol %.3g (cloud too large for the coherence length sqrt(c); use the "
+                        "dense solver or mode 2)",
+                        reached, max_rank, resid, h->bcpd_tol);
+        }
     }
     PRG_HIP(hipMalloc((void**)&h->G, (size_t)m * m * sizeof(float)));
     dim3 grid((unsigned)prg::ceil_div(m, kBlock), (unsigned)prg::ceil_div(m, 16));
@@ -491,6 +524,16 @@ int prg_cpd_nonrigid_set_solver(prg_cpd* h, int mode, int max_rank, double tol) 
 int prg_cpd_nonrigid_rank(prg_cpd* h, int* rank) {
     PRG_REQUIRE(h && rank && (h->G || h->F), PRG_ERR_STATE, "prg_cpd_nonrigid_rank: G has not been built");
     *rank = h->F ? h->f_rank : 0;
+    return PRG_OK;
+}
+
+int prg_cpd_bcpd_set_solver(prg_cpd* h, int mode, int max_rank, double tol) {
+    PRG_REQUIRE(h, PRG_ERR_INVALID, "prg_cpd_bcpd_set_solver: NULL plan");
+    PRG_REQUIRE(mode >= 0 && mode <= 2 && max_rank >= 0 && max_rank <= kMaxRank && tol >= 0.0, PRG_ERR_INVALID,
+                "prg_cpd_bcpd_set_solver: mode must be 0, 1 or 2, max_rank in [0, %d] and tol non-negative", kMaxRank);
+    h->bcpd_solver = mode;
+    h->bcpd_max_rank = max_rank;
+    h->bcpd_tol = tol > 0.0 ? tol : 1.0e-11;
     return PRG_OK;
 }
 

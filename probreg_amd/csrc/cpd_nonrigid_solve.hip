@@ -19,6 +19,7 @@
 //   prg_cpd_bcpd_solve (K-deep left update, second panel)     test_bcpd_solve
 //   non-positive pivots: immediate report / sticky flag       test_dense_path_reports_..., test_lowrank_path_reports_...
 //   low-rank M-step                                           tests/test_nonrigid_lowrank_gpu.py (1e-7 on the exact matrix)
+//   prg_cpd_bcpd_solve on the kernel factor, diag(Sigma)      tests/test_bcpd_lowrank_gpu.py::test_solve_on_the_factor
 #include <math.h>
 
 #include <algorithm>
@@ -703,8 +704,9 @@ constexpr int GLD = GT + 1;
 // u = F^T B with one more MFMA per k-step (B = [b | 0] as a 16-column operand), so the right-hand side of the reduced
 // system costs no pass of its own.
 __global__ __launch_bounds__(kBlock) void k_lr_gram(const double* __restrict__ f, int64_t ld, int64_t m, int rank,
-                                                    const double* __restrict__ sp, const double* __restrict__ b3,
-                                                    int64_t chunk, double* __restrict__ part, double* __restrict__ upart) {
+                                                    const double* __restrict__ sp, const double* __restrict__ dw,
+                                                    const double* __restrict__ b3, int64_t chunk,
+                                                    double* __restrict__ part, double* __restrict__ upart) {
     __shared__ double as[GS][GLD], bs[GS][GLD], xs[GS][16];
     // tile (ta >= tb) of the lower triangle from the linear index
     int ta = 0, rem = blockIdx.x;
@@ -734,7 +736,8 @@ __global__ __launch_bounds__(kBlock) void k_lr_gram(const double* __restrict__ f
     auto fetch = [&](int64_t i0) {
         const int64_t i = i0 + lk;
         const bool in = i < i_end;
-        const double pw = in ? sp[i] * sp[i] : 0.0;  // D_ii (k_rhs left sqrt(D) in sp)
+        // D_ii: k_rhs left sqrt(D) in sp; the BCPD M-step passes nu itself in dw (sqrt(nu)^2 is an ulp off)
+        const double pw = in ? (dw ? dw[i] : sp[i] * sp[i]) : 0.0;
 #pragma unroll
         for (int q = 0; q < GT / 8; ++q) {
             const int r = lr + 8 * q;
@@ -835,7 +838,7 @@ __global__ __launch_bounds__(kBlock) void k_lr_gram_reduce(const double* __restr
     if (e < rp * 3) u[e] = in_u ? uv : 0.0;  // zero rows in the pad
     if (!in_s) return;
     if (real) {
-        if (a == b) v += lmd * params[13];
+        if (a == b) v += params ? lmd * params[13] : lmd;  // params == nullptr: lmd carries the shift itself (BCPD)
     } else {
         v = a == b ? 1.0 : 0.0;
     }
@@ -1031,7 +1034,7 @@ int mstep_nonrigid_lowrank(prg_cpd* h, double lmd) {
     k_rhs<<<grid1(ld), kBlock, 0, st>>>(h->rowacc, h->Mcap, h->src4, m, ld, h->nr_alpha > 0.0 ? h->nr_prior : nullptr,
                                         h->nr_alpha, h->params, b3, sp);
     // S = c I + F^T D F and z = F^T B in one pass over the factor
-    k_lr_gram<<<ggrid, kBlock, 0, st>>>(h->F, ld, m, rank, sp, b3, chunk, part, upart);
+    k_lr_gram<<<ggrid, kBlock, 0, st>>>(h->F, ld, m, rank, sp, nullptr, b3, chunk, part, upart);
     k_lr_gram_reduce<<<rgrid, kBlock, 0, st>>>(part, upart, ntile, nsplit, rank, rp, h->params, lmd, S, z);
     const bool small = rp <= 1024;  // (beyond, the MFMA panel solves of the big factorisation pay for their inverses)
     // (one workgroup doing the whole r x r solve out of LDS was built in round 3: with the packed triangle's irregular LDS
@@ -1173,7 +1176,7 @@ namespace {
 __global__ __launch_bounds__(kBlock) void k_bcpd_rhs(const double* __restrict__ rowacc, const double* __restrict__ nu_ext,
                                                      const double* __restrict__ resid, const int* __restrict__ perm,
                                                      int64_t m, int64_t mp, int dim, double* __restrict__ b3,
-                                                     double* __restrict__ sp) {
+                                                     double* __restrict__ sp, double* __restrict__ nu_out = nullptr) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= mp) return;
     double nu = 0.0, r[3] = {0.0, 0.0, 0.0};
@@ -1186,6 +1189,7 @@ __global__ __launch_bounds__(kBlock) void k_bcpd_rhs(const double* __restrict__ 
     b3[i * 3 + 1] = nu * r[1];
     b3[i * 3 + 2] = nu * r[2];
     sp[i] = sqrt(nu);
+    if (nu_out) nu_out[i] = nu;
 }
 
 // Wt[c][j] = g[c][j] * sp[j]  (= (D^1/2 G)^T, G symmetric); zero in the pad
@@ -1229,16 +1233,196 @@ __global__ __launch_bounds__(kBlock) void k_unsort_rows(const double* __restrict
     for (int k = 0; k < dim; ++k) out[j * dim + k] = in[i * stride_in + k];
 }
 
+// ---- BCPD M-step on the kernel factor G = F F^T -------------------------------------------------------
+// With D = diag(nu), c = cfac and the r x r SPD matrix S = (lmd / c) I + F^T D F = L L^T (push-through identity: no G^-1 and
+// no division by nu, so nu_m = 0 is no special case):
+//     Sigma = (lmd G^-1 + c D)^-1 = (1 / c) F S^-1 F^T,    v_hat = c Sigma D R = F S^-1 (F^T D R),
+//     Sigma_mm = |L^-1 f_m|^2 / c                           (f_m = row m of F; a sum of squares, never negative).
+// S comes from k_lr_gram (which also forms F^T D R), the r x r Cholesky and the three-right-hand-side solves are the
+// low-rank non-rigid M-step's; new here is diag(Sigma): M r^2 flop, the only part whose cost grows with M r^2.
+
+// X = L^-1 (lower triangular, [rp][rp] row-major; the upper triangle and every row / column >= rank are written as zeros)
+// from the Cholesky factor in the lower triangle of s.  The columns of X are independent forward substitutions
+// L x = e_c: one workgroup per strip of 16 columns, walking down 16 rows at a time - the products with the rows
+// already finished are one dot product per thread (fixed order), the 16 x 16 diagonal block is substituted out of LDS.
+// (x is read back by the workgroup that wrote it, after a barrier: no __restrict__.)
+constexpr int TI = 16;
+__global__ __launch_bounds__(kBlock) void k_tri_inverse(const double* __restrict__ s, int64_t rp, int rank, double* x) {
+    __shared__ double lblk[TI][TI + 1], xb[TI][TI + 1];
+    const int c0 = blockIdx.x * TI;
+    const int ri = threadIdx.x >> 4, c = threadIdx.x & 15;
+    double* xcol = x + c0 + c;
+    for (int i0 = 0; i0 < (int)rp; i0 += TI) {
+        const int i = i0 + ri;
+        if (i0 < c0 || i0 >= rank || c0 >= rank) {  // (the same decision in every thread of the workgroup)
+            xcol[(int64_t)i * rp] = 0.0;
+            continue;
+        }
+        const double* __restrict__ lrow = s + (int64_t)i * rp;
+        double acc = (i == c0 + c) ? 1.0 : 0.0;
+#pragma unroll 8
+        for (int k = c0; k < i0; ++k) acc = fma(-lrow[k], xcol[(int64_t)k * rp], acc);
+        lblk[ri][c] = (c <= ri) ? lrow[i0 + c] : 0.0;
+        xb[ri][c] = acc;
+        __syncthreads();
+        if (ri == 0) {
+            for (int r = 0; r < TI; ++r) {
+                double t = xb[r][c];
+                for (int q = 0; q < r; ++q) t = fma(-lblk[r][q], xb[q][c], t);
+                xb[r][c] = t / lblk[r][r];
+            }
+        }
+        __syncthreads();
+        xcol[(int64_t)i * rp] = (i < rank && c0 + c < rank) ? xb[ri][c] : 0.0;
+        __syncthreads();  // the rows just written feed the products of the next 16
+    }
+}
+
+// out[i] = scale * sum_a (sum_{b <= a} X[a][b] F[b][i])^2 for the points i of this workgroup's slab of 64: the r x M product
+// X F is never stored.  Per block of 128 rows of X, wave w owns rows 32 w .. 32 w + 31 (two MFMA row tiles) times the
+// four 16-point tiles; the k loop stops at the wave's own diagonal (tiles above it are skipped), operands come straight
+// from global / L2 as in k_gemm_nt_f64 (A = X, row-major with k contiguous: two 16-byte loads per lane and tile, the k
+// index permuted the same way for both operands; B = F, point-contiguous: four 8-byte loads per tile, 128-byte runs per
+// 16 lanes).  Each lane squares and adds its accumulators block after block, the four lane groups and the four waves are
+// combined in a fixed order: no atomics, the same bytes on every run.
+// MFMA maps as above: lane l supplies A[row l & 15][k l >> 4], B[k l >> 4][col l & 15]; C/D col = l & 15, row = (l >> 4) + 4 reg.
+constexpr int SD_PTS = 64;
+__global__ __launch_bounds__(kBlock) void k_lr_sigma_diag(const double* __restrict__ x, int64_t rp, int rank,
+                                                          const double* __restrict__ f, int64_t ld, int64_t m,
+                                                          double scale, double* __restrict__ out) {
+    __shared__ double red[kBlock / 64][SD_PTS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, kq = lane >> 4;
+    const int64_t p0 = (int64_t)blockIdx.x * SD_PTS;  // p0 + 63 < round_up(m, 256) = ld - 32: inside every row of F
+    const int r16 = (rank + 15) & ~15;
+    double ssum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int a0 = 0; a0 < rank; a0 += NB) {
+        const int aw = a0 + 32 * wv;  // rows aw .. aw + 31 < rp (rp is a multiple of 128)
+        if (aw >= rank) continue;     // (wave-uniform; no barrier inside the loop)
+        d4 acc[2][4];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[t][j] = (d4){0.0, 0.0, 0.0, 0.0};
+        const int kend = aw + 32 < r16 ? aw + 32 : r16;
+        const double* __restrict__ xa = x + (int64_t)(aw + li) * rp + 4 * kq;
+        for (int kc = 0; kc < kend; kc += 16) {
+            d4 af[2];
+            double bf[4][4];
+            af[0] = *reinterpret_cast<const d4*>(xa + kc);
+            af[1] = *reinterpret_cast<const d4*>(xa + 16 * rp + kc);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int k = kc + 4 * kq + q;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bf[j][q] = k < rank ? f[(int64_t)k * ld + p0 + 16 * j + li] : 0.0;
+            }
+            const bool first = kc < aw + 16;  // the upper of the two row tiles ends one chunk earlier
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (first) acc[0][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[0][q], bf[j][q], acc[0][j], 0, 0, 0);
+                    acc[1][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[1][q], bf[j][q], acc[1][j], 0, 0, 0);
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ssum[j] = fma(acc[t][j][r], acc[t][j][r], ssum[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double v = ssum[j];
+        v += __shfl_xor(v, 16, 64);
+        v += __shfl_xor(v, 32, 64);
+        if (kq == 0) red[wv][16 * j + li] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < SD_PTS) {
+        const int64_t i = p0 + threadIdx.x;
+        if (i < m) out[i] = scale * ((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+    }
+}
+
+}  // namespace
+
+namespace {
+// prg_cpd_bcpd_solve for a plan that holds the factor; the caller has checked the arguments and set the device
+int bcpd_solve_lowrank(prg_cpd* h, double lmd, double cfac, const double* nu_hd, const double* resid_hd, double* vhat_hd,
+                       double* sigma_diag_hd) {
+    const int64_t m = h->M, ld = h->f_ld, mp = ld - 32;
+    const int rank = h->f_rank;
+    const int64_t rp = prg::round_up(rank, NB), nblk = rp / NB;
+    const int tiles1 = (int)prg::ceil_div(rank, GT), ntile = tiles1 * (tiles1 + 1) / 2;
+    int nsplit = (int)std::min<int64_t>(std::max(1, 512 / ntile), prg::ceil_div(m, 8 * GS));
+    const int64_t chunk = prg::round_up(prg::ceil_div(m, nsplit), GS);
+    nsplit = (int)prg::ceil_div(m, chunk);
+    const size_t n_s = (size_t)rp * rp, n_linv = (size_t)nblk * NB * NB, n_vec = (size_t)ld * 3,
+                 n_part = (size_t)nsplit * ntile * GT * GT + (size_t)nsplit * rank * 3;
+    // S | X = L^-1 | block inverses (look-ahead Cholesky only) | gram partials | b3, sp, nu, diag | z | info
+    PRG_TRY(ensure_solve_workspace(h, (2 * n_s + n_linv + n_part + 4 * n_vec + (size_t)rp * 3 + 16) * sizeof(double)));
+    double* S = h->nr_solve;
+    double* X = S + n_s;
+    double* linv = X + n_s;
+    double* part = linv + n_linv;
+    double* upart = part + (size_t)nsplit * ntile * GT * GT;
+    double* b3 = part + n_part;
+    double* sp = b3 + n_vec;
+    double* nu = sp + n_vec;
+    double* diag = nu + n_vec;
+    double* z = diag + n_vec;  // [rp][3]
+    int* info = reinterpret_cast<int*>(z + (size_t)rp * 3);
+    hipStream_t st = h->stream;
+
+    PRG_TRY(prg::ensure_stage(h, (size_t)m * 4 * sizeof(double)));
+    double* nu_dev = nullptr;
+    PRG_HIP(hipMemcpyAsync(h->stage, resid_hd, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
+    if (nu_hd) {
+        nu_dev = (double*)h->stage + (size_t)m * 3;
+        PRG_HIP(hipMemcpyAsync(nu_dev, nu_hd, (size_t)m * sizeof(double), hipMemcpyDefault, st));
+    }
+    PRG_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
+    k_bcpd_rhs<<<grid1(ld), kBlock, 0, st>>>(h->rowacc, nu_dev, (const double*)h->stage, h->perm_src, m, ld, h->D, b3, sp, nu);
+    // S = (lmd / c) I + F^T D F and z = F^T D R in one pass over the factor
+    k_lr_gram<<<dim3((unsigned)ntile, (unsigned)nsplit), kBlock, 0, st>>>(h->F, ld, m, rank, sp, nu, b3, chunk, part, upart);
+    k_lr_gram_reduce<<<grid1(4 * std::max<int64_t>((int64_t)rp * rp, rp * 3)), kBlock, 0, st>>>(part, upart, ntile, nsplit, rank,
+                                                                                              rp, nullptr, lmd / cfac, S, z);
+    if (rp <= 1024) {
+        PRG_TRY(cholesky_small(h, S, rp, info, rank));
+        PRG_TRY(cholesky_small_solve3(h, S, rp, z, rank));
+    } else {
+        PRG_TRY(cholesky_lookahead(h, S, rp, linv, info, rank));
+        PRG_TRY(cholesky_solve3(h, S, rp, linv, z));
+    }
+    PRG_TRY(prg::lowrank_apply(h, z, h->W));  // v_hat = F S^-1 F^T D R, kept for the next transform
+    k_tri_inverse<<<(unsigned)(rp / TI), kBlock, 0, st>>>(S, rp, rank, X);
+    k_lr_sigma_diag<<<(unsigned)(mp / SD_PTS), kBlock, 0, st>>>(X, rp, rank, h->F, ld, m, 1.0 / cfac, diag);
+
+    double* stage = (double*)h->stage;
+    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(h->W, 3, h->D, m, h->perm_src, stage);
+    PRG_HIP(hipMemcpyAsync(vhat_hd, stage, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
+    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(diag, 1, 1, m, h->perm_src, b3);
+    PRG_HIP(hipMemcpyAsync(sigma_diag_hd, b3, (size_t)m * sizeof(double), hipMemcpyDefault, st));
+    PRG_HIP(hipGetLastError());
+    int host_info = 0;
+    PRG_HIP(hipMemcpyAsync(&host_info, info, sizeof(int), hipMemcpyDeviceToHost, st));
+    PRG_HIP(hipStreamSynchronize(st));
+    PRG_REQUIRE(host_info == 0, PRG_ERR_STATE, "prg_cpd_bcpd_solve: S is not positive definite at pivot %d", host_info - 1);
+    return PRG_OK;
+}
 }  // namespace
 
 extern "C" int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const double* nu_hd, const double* resid_hd,
                                   double* vhat_hd, double* sigma_diag_hd) {
-    PRG_REQUIRE(h && h->bcpd && h->G && h->W, PRG_ERR_STATE, "prg_cpd_bcpd_solve: needs prg_cpd_bcpd_build_g first");
+    PRG_REQUIRE(h && h->bcpd && (h->G || h->F) && h->W, PRG_ERR_STATE, "prg_cpd_bcpd_solve: needs prg_cpd_bcpd_build_g first");
     PRG_REQUIRE(nu_hd || h->have_estep, PRG_ERR_STATE, "prg_cpd_bcpd_solve: no E-step has run and no nu was given");
     PRG_REQUIRE(resid_hd && vhat_hd && sigma_diag_hd, PRG_ERR_INVALID, "prg_cpd_bcpd_solve: NULL argument");
     PRG_REQUIRE(lmd > 0.0 && cfac > 0.0, PRG_ERR_INVALID, "prg_cpd_bcpd_solve: lmd and c must be > 0 (got %g, %g)", lmd,
                 cfac);
     prg::DeviceGuard g(h->device);
+    if (h->F) return bcpd_solve_lowrank(h, lmd, cfac, nu_hd, resid_hd, vhat_hd, sigma_diag_hd);
     const int64_t m = h->M, mp = prg::round_up(m, NB), nblk = mp / NB;
     const size_t n_s = (size_t)mp * mp, n_linv = (size_t)nblk * NB * NB, n_vec = (size_t)mp * 3;
     const size_t need = (2 * n_s + n_linv + 6 * n_vec + (size_t)mp + 16) * sizeof(double);

@@ -240,6 +240,10 @@ struct prg_cpd {
     float* srcw = nullptr;
     double uniform_ratio = 0.0;  // > 0: replaces M / N in the outlier constant of cpd.py:78-79
     bool bcpd = false;           // G is the inverse multiquadric kernel, W holds the displacement v_hat
+    // solver of the next prg_cpd_bcpd_build_g (prg_cpd_bcpd_set_solver)
+    int bcpd_solver = 0;         // 0: dense G (default), 1: factor G = F F^T or an error, 2: factor when it converges, else dense
+    int bcpd_max_rank = 0;       // 0: min(2048, M / 2)
+    double bcpd_tol = 1.0e-11;   // largest entry of G - F F^T the factor may leave
 
     double* pinned = nullptr;    // 64 doubles of pinned host memory for the per-iteration parameter read-back
 

@@ -317,6 +317,12 @@ class CpdPlan(object):
     def bcpd_build_g(self, c=1.0):
         check(lib.prg_cpd_bcpd_build_g(self._h, float(c)))
 
+    def bcpd_set_solver(self, mode=0, max_rank=0, tol=0.0):
+        """Before bcpd_build_g: 0 = dense G + M x M Cholesky (default), 1 = pivoted-Cholesky factor G = F F^T or a
+        ValueError when ``tol`` (0: 1e-11) is not reached within ``max_rank`` (0: min(2048, M / 2)), 2 = the factor when it
+        converges, else dense.  ``nonrigid_rank()`` then tells which one the plan holds (prg_cpd_bcpd_set_solver)."""
+        check(lib.prg_cpd_bcpd_set_solver(self._h, int(mode), int(max_rank), float(tol)))
+
     def bcpd_solve(self, lmd, cfac, resid, nu=None):
         """(v_hat [m x dim], diag(Sigma) [m]) for ``nu`` (default: the p1 of the last E-step) - prg_cpd_bcpd_solve."""
         r = np.ascontiguousarray(resid, dtype=np.float64)
