@@ -1,5 +1,5 @@
-// What the deformable kinematic M-step (filterreg_kinematic.hip) sees of a FilterReg plan (filterreg.hip): the plan's
-// buffers by pointer, and the lattice E-step over a moved source that the caller supplies.
+// What the deformable kinematic M-step (filterreg_kinematic.hip) sees of a FilterReg plan (filterreg.hip; its lattice: lattice.hip): the plan's
+// buffers by pointer (the plan owns them), and the lattice E-step over a moved source that the caller supplies.
 #pragma once
 #include "prg_common.h"
 

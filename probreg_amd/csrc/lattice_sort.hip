@@ -1,5 +1,5 @@
 // Stable LSD radix sort of (vertex id, incidence) pairs for the order-preserving splat of the permutohedral lattice
-// (filterreg.hip, lat_segments).  The sort itself is rocPRIM's device-wide radix sort - a plain library primitive, in a
+// (lattice.hip, lat_segments).  The sort itself is rocPRIM's device-wide radix sort - a plain library primitive, in a
 // translation unit of its own so that its templates are instantiated once.
 #include <rocprim/device/device_radix_sort.hpp>
 

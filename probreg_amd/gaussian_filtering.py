@@ -17,12 +17,17 @@ class Permutohedral(object):
 
     def __init__(self, p, with_blur=True):
         _lib.require_gpu()
-        p = np.ascontiguousarray(p, dtype=np.float32)
-        if p.ndim != 2:
-            raise ValueError("p must be a 2-D array (points x features).")
         dev, st = _current_device_and_stream()
         self._h = ctypes.c_void_p()
         check(lib.prg_ph_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        self.init(p, with_blur)
+
+    def init(self, p, with_blur=True):
+        """(Re)build the lattice over ``p`` on this handle, as the reference's ``_impl.init`` does; the handle's device
+        buffers are reused where they fit."""
+        p = np.ascontiguousarray(p, dtype=np.float32)
+        if p.ndim != 2:
+            raise ValueError("p must be a 2-D array (points x features).")
         self._n = p.shape[0]
         check(lib.prg_ph_init(self._h, ptr(p), p.shape[0], p.shape[1], 1 if with_blur else 0))
 
