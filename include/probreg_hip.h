@@ -355,6 +355,38 @@ int prg_inverse_multiquadric_kernel(int device, void* hip_stream, const float* x
 int prg_nn_mean_distance(int device, void* hip_stream, const float* a_hd, int64_t m, const float* b_hd, int64_t n,
                          int dim, double* out_host);
 
+/* ---- CPD correspondences: top-k posterior matches per point (csrc/cpd_correspond.hip) ---- */
+/* No reference counterpart: the reference hands back a transformation only; a user of it forms the dense M x N matrix P of
+ * cpd.py:84 on small clouds and takes an argmax.  Here P is never formed; the matches come from one sweep over all pairs in the
+ * log domain, s_mn = log2 P_mn = b_n - kappa (|x_n - z_m|^2 + q_m), kappa = log2(e) / (2 sigma2).
+ *
+ * The plan-free stage: for each of the n_o owned points ([n_o][dim] float32, dim 2 or 3) the k streamed points with the largest
+ *   score = owned_bias + streamed_bias - kappa |owned - streamed|^2      (float32; differences formed before squaring)
+ * in descending order; scores that are equal as float32 rank by the smaller streamed index.  Either bias ([n] float32) may be
+ * NULL, meaning 0: with both NULL this is an exact k-nearest-neighbour search.  1 <= k <= 8 and k <= n_s.  `segments` cuts the
+ * streamed cloud into that many pieces swept by separate workgroups (0: automatic, at most 4096); the result does not depend on
+ * it, bit for bit.  index_out / score_out: [n_o][k] int32 / float32.  All arrays host or device.  A pair whose score is NaN
+ * (a NaN coordinate or bias) is never listed; a row that fewer than k pairs can fill ends in index -1, score -inf. */
+int prg_topk_sweep(int device, void* hip_stream, const float* owned_hd, const float* owned_bias_hd, const float* streamed_hd,
+                   const float* streamed_bias_hd, int64_t n_o, int64_t n_s, int dim, double kappa, int k, int segments,
+                   int* index_out_hd, float* score_out_hd);
+/* On a plan, after prg_cpd_estep: side 0 - for every source point m the k target points n with the largest s_mn; side 1 - for
+ * every target point n the k source points m.  Rows and entries are in the caller's point order, equal scores rank by the smaller
+ * caller index (the plan's internal order never shows).  index_out [owned][k] int32, log2_prob_out [owned][k] float32 (the score as
+ * computed), prob_out [owned][k] float64 (exp2 of it; may underflow to 0 while the score stays finite) - host arrays, the last two
+ * may be NULL.  A column whose denominator underflowed takes den = float32 eps + c, as cpd.py:81-82.
+ * Reads what the E-step left: the transformed source with q_m (z4), b_n = -log2(den_n + c) (tgt4.w) and sigma2 in PARAMS.  Every
+ * form of the E-step - the two sweeps, the fused single sweep on the matrix cores and the residual-form single sweep - writes
+ * b_n, so any of them will do here (p1 for the source side's mass exists after the two sweeps only).  PRG_ERR_STATE when no E-step
+ * has run, or when the plan has moved on since (prg_cpd_mstep / _mstep_nonrigid / _iterate, prg_cpd_set_params / _init_params,
+ * prg_cpd_set_source_weights, prg_cpd_moments_from_estep, new clouds): b_n would belong to another sigma2.  PRG_ERR_STATE on a
+ * plan whose target is sharded over ranks (n_local != n_global).  A caller that writes PARAMS through prg_cpd_params_ptr is
+ * invisible to that check and has to run prg_cpd_estep again itself.  Pairs with a NaN score are never listed (index -1,
+ * score -inf fill such a row), as in prg_topk_sweep. */
+int prg_cpd_correspond(prg_cpd* h, int side, int k, int* index_out, float* log2_prob_out, double* prob_out);
+/* Host only: owned points per workgroup of the sweep (one per lane) and streamed points per trip of its loop. */
+int prg_cpd_correspond_tile_shape(int* owned_per_workgroup, int* streamed_per_tile);
+
 /* ---- CPD batch plan: many small rigid / affine registrations per launch (csrc/cpd_batch.hip) ---- */
 /* Replaces a host loop over registration_cpd (cpd.py:407-456), i.e. B runs of the EM driver cpd.py:106-120, by one plan whose
  * launch count per EM iteration does not depend on B; the reference has no batched interface.  Problem b keeps the semantics of

@@ -89,6 +89,9 @@ SIGNATURES = {
     "prg_cpd_iterate": [_vp, _i, _i, _d, _i],
     "prg_cpd_set_moments_only": [_vp, _i],
     "prg_cpd_batch_tile_shape": [_c.POINTER(_i), _c.POINTER(_i)],
+    "prg_topk_sweep": [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _i, _i, _vp, _vp],
+    "prg_cpd_correspond": [_vp, _i, _i, _vp, _vp, _vp],
+    "prg_cpd_correspond_tile_shape": [_c.POINTER(_i), _c.POINTER(_i)],
     "prg_cpd_batch_tile_table": [_i, _vp, _vp, _vp, _i64, _c.POINTER(_i64)],
     "prg_cpd_batch_create": [_pp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "prg_cpd_batch_destroy": [_vp],

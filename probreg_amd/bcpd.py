@@ -33,7 +33,7 @@ import scipy.special as spsp
 from . import _lib
 from . import math_utils as mu
 from . import transformation as tf
-from .cpd import _as_points, _params_block
+from .cpd import Correspondences, _as_points, _params_block
 from .engine import CpdPlan
 from .log import log
 
@@ -76,10 +76,12 @@ class BayesianCoherentPointDrift(abc.ABC):
         self._callbacks = []
         self._device = device
         self._plan = None
+        self._last = None  # (last M-step result, w, target size) of a finished registration
 
     def set_source(self, source):
         self._source = _as_points(source)
         self._close_plan()
+        self._last = None
 
     def set_callbacks(self, callbacks):
         self._callbacks.extend(callbacks)
@@ -136,6 +138,7 @@ class BayesianCoherentPointDrift(abc.ABC):
         assert source.ndim == 2 and target.ndim == 2, "source and target must have 2 dimensions."
         if source.shape[1] != target.shape[1] or source.shape[1] not in (2, 3):
             raise ValueError("source and target must both be (n, 2) or (n, 3) arrays.")
+        self._last = None  # (set again once this registration has finished)
         res = self._initialize(target)
         plan = self._plan
         dim = source.shape[1]
@@ -163,7 +166,38 @@ class BayesianCoherentPointDrift(abc.ABC):
                 if rmse is not None and abs(rmse - tmp_rmse) < tol:
                     break
                 rmse = tmp_rmse
+        self._last = (res, float(w), target.shape[0])  # (what correspondences() runs its E-step from)
         return res.transformation
+
+    def correspondences(self, k=1, side="source"):
+        """Top-``k`` posterior matches under the state ``registration`` ended with: the class's own weighted E-step
+        (alpha, diag(Sigma), sigma2 and the transformation of the last M-step, the ``w`` of that registration) on the
+        registration's plan, then the sweep of ``CpdPlan.correspondences``.  Returns
+        ``cpd.Correspondences(index, prob, log2_prob, mass)`` - mass is nu (source side) or nu' (target side)."""
+        if side not in ("source", "target"):
+            raise ValueError("side must be 'source' or 'target' (got %r)" % (side,))
+        if self._plan is None or self._last is None:
+            raise RuntimeError("correspondences() needs a finished registration(): there is no transformation yet.")
+        # (BCPD is never sharded over ranks, so there is no dist.world() guard as in cpd.py; a sharded plan would be refused by
+        # prg_cpd_correspond itself, n_local != n_global)
+        res, w, n_target = self._last
+        plan = self._plan
+        source = self._source
+        dim = source.shape[1]
+        rigid = res.transformation.rigid_trans
+        t_c = np.asarray(rigid.t) + rigid.scale * np.dot(rigid.rot, self._cy) - self._cx
+        p = np.zeros(_lib.PRG_NPARAMS)
+        p[:13] = _params_block(rigid.rot, t_c, rigid.scale, dim)[:13]
+        p[13] = res.sigma2
+        plan.set_params(p)
+        plan.set_moments_only(2)
+        try:
+            nu_d, nu, _px = _estep_on_plan(plan, n_target, dim, rigid.scale, res.alpha,
+                                           _sigma_diag(res.sigma_mat, source.shape[0]), res.sigma2, w)
+            index, log2_prob, prob = plan.correspondences(k, side)
+        finally:
+            plan.set_moments_only(0)
+        return Correspondences(index, prob, log2_prob, nu if side == "source" else nu_d)
 
 
 class CombinedBCPD(BayesianCoherentPointDrift):

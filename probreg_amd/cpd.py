@@ -31,6 +31,60 @@ MstepResult.__doc__ = """What an M-step (and ``registration``) hands back - same
     sigma2         : current isotropic variance of the GMM components
     q              : value of the objective the convergence test looks at
 """
+Correspondences = namedtuple("Correspondences", ["index", "prob", "log2_prob", "mass"])
+Correspondences.__doc__ = """The k best posterior matches of every owned point (no counterpart in the reference, which would
+    form the dense P of cpd.py:84 and sort it).  Arrays of shape (owned, k), rows and entries in the caller's point order.
+
+    index     : int32 - for ``side="source"`` the target points n of source point m with the largest P_mn, for
+                ``side="target"`` the source points m of target point n; descending, equal scores by the smaller index
+    prob      : float64 P_mn of those pairs (exp2 of ``log2_prob``; 0 where it underflows)
+    log2_prob : float32 log2 P_mn as the GPU sweep computed it - finite and ranked even where ``prob`` is 0
+    mass      : (owned,) float64 - p1 (source side) or pt1 (target side) of the same E-step; 1 - pt1_n is the probability
+                that target point n is an outlier
+"""
+
+
+def _plan_correspondences(plan, k, side):
+    """An E-step has just run on ``plan`` (two sweeps): its matches and the mass of the owned side."""
+    index, log2_prob, prob = plan.correspondences(k, side)
+    pt1, p1, _px = plan.get_estep()
+    return Correspondences(index, prob, log2_prob, p1 if side == "source" else pt1)
+
+
+def correspondences(t_source, target, sigma2, w=0.0, k=1, side="source", source_log_weights=None, uniform_ratio=0.0,
+                    device=None):
+    """Top-``k`` posterior matches of the CPD E-step (cpd.py:71-88) on explicit arrays, as ``expectation_step`` takes them:
+    ``t_source`` (M, D) is the transformed source, ``target`` (N, D), ``sigma2`` and ``w`` the E-step's parameters.
+
+    k      : 1 ... 8 matches per point (and at most the number of points on the other side)
+    side   : "source" - the best targets of every source point; "target" - the best sources of every target point
+    source_log_weights, uniform_ratio : the weighted (BCPD) E-step of ``CpdPlan.set_source_weights``: ln a_m <= 0 per source
+             point, and what replaces M / N in the outlier constant when > 0
+    Returns ``Correspondences(index, prob, log2_prob, mass)``.  Both clouds are centred on the target's fp64 mean before the
+    float32 upload; the M x N matrix is never formed.
+    """
+    if side not in ("source", "target"):
+        raise ValueError("side must be 'source' or 'target' (got %r)" % (side,))
+    t_source = _as_points(t_source)
+    target = _as_points(target)
+    assert t_source.ndim == 2 and target.ndim == 2, "source and target must have 2 dimensions."
+    dim = t_source.shape[1]
+    c = target.mean(axis=0)
+    plan = CpdPlan(device)
+    try:
+        plan.set_source(t_source - c)
+        plan.set_target(target - c)
+        plan.set_moments_only(2)  # never a single sweep: b_n, p1 and pt1 all exist afterwards
+        if source_log_weights is not None or uniform_ratio > 0.0:
+            plan.set_source_weights(source_log_weights, uniform_ratio)
+        p = np.zeros(_lib.PRG_NPARAMS)
+        p[:13] = _params_block(np.identity(dim), np.zeros(dim), 1.0, dim)[:13]
+        p[13] = sigma2
+        plan.set_params(p)
+        plan.estep(w)
+        return _plan_correspondences(plan, k, side)
+    finally:
+        plan.close()
 
 
 def _as_points(x):
@@ -69,11 +123,13 @@ class CoherentPointDrift(abc.ABC):
         self._callbacks = []
         self._device = device
         self._plan = None
+        self._reg_w = None  # outlier weight of the last registration (correspondences() runs its E-step with it)
         self.xp = np
 
     # -- reference API ------------------------------------------------------------------------
     def set_source(self, source):
         self._source = _as_points(source)
+        self._reg_w = None  # (correspondences() belongs to a registration of THIS source)
 
     def set_callbacks(self, callbacks):
         self._callbacks.extend(callbacks)
@@ -113,6 +169,30 @@ class CoherentPointDrift(abc.ABC):
     def _maximization_step(source, target, estep_res, sigma2_p=None, xp=np):
         """A static method in every subclass, with the reference's signature (cpd.py:95-104)."""
         return None
+
+    def correspondences(self, target=None, k=1, side="source"):
+        """Top-``k`` posterior matches under the transformation ``registration`` ended with (any flavour: rigid, affine,
+        non-rigid, constrained): one more E-step on the registration's own plan - two sweeps, current parameters, the ``w``
+        of that registration - then the sweep of ``CpdPlan.correspondences``.  ``target``: None, the registration's own
+        target (another cloud is not supported here: ``cpd.correspondences`` takes explicit arrays).  Returns
+        ``Correspondences(index, prob, log2_prob, mass)``."""
+        if side not in ("source", "target"):
+            raise ValueError("side must be 'source' or 'target' (got %r)" % (side,))
+        if self._plan is None or self._reg_w is None:
+            raise RuntimeError("correspondences() needs a finished registration(): there is no transformation yet.")
+        if pdist.world()[1] > 1:
+            raise NotImplementedError("correspondences: the target is sharded over %d ranks; run it in one process."
+                                      % pdist.world()[1])
+        plan = self._plan
+        if target is not None:
+            raise NotImplementedError("correspondences: only the registration's own target (target=None) is supported; for "
+                                      "another cloud use cpd.correspondences on explicit arrays.")
+        plan.set_moments_only(2)
+        try:
+            plan.estep(self._reg_w)
+            return _plan_correspondences(plan, k, side)
+        finally:
+            plan.set_moments_only(0)
 
     # -- plan handling ------------------------------------------------------------------------
     def _centres(self, source, target_full):
@@ -199,6 +279,12 @@ class CoherentPointDrift(abc.ABC):
         ``q``), otherwise once at the end.
         """
         assert self._tf_type is not None, "transformation type is None."
+        self._reg_w = None  # (set again once this registration has finished: correspondences() needs a whole one)
+        res = self._registration(target, w, maxiter, tol)
+        self._reg_w = float(w)
+        return res
+
+    def _registration(self, target, w, maxiter, tol):
         res = self._initialize(target)
         plan = self._plan
         q = res.q
@@ -397,6 +483,7 @@ class NonRigidCPD(CoherentPointDrift):
 
     def set_source(self, source):
         self._source = _as_points(source)
+        self._reg_w = None
         self._build()
 
     def _initialize(self, target):

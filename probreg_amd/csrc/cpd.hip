@@ -245,13 +245,14 @@ int free_plan_buffers(prg_cpd* h) {
     void** const owned[] = {(void**)&h->src4, (void**)&h->z4, (void**)&h->tgt4, (void**)&h->pt1, (void**)&h->colpart, (void**)&h->rowpart,
                             (void**)&h->rowacc, (void**)&h->mompart, &h->stage, (void**)&h->perm_src, (void**)&h->perm_tgt, (void**)&h->zmeta,
                             (void**)&h->tmeta, (void**)&h->colmin, (void**)&h->motion, (void**)&h->srcw, (void**)&h->wgcount, (void**)&h->rorig,
-                            (void**)&h->corig, (void**)&h->zchunk, (void**)&h->tchunk};
+                            (void**)&h->corig, (void**)&h->zchunk, (void**)&h->tchunk, &h->corr_buf};
     for (void** p : owned) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
     h->wg_cap = 0;
     h->stage_bytes = 0;
+    h->corr_bytes = 0;
     return PRG_OK;
 }
 
@@ -467,6 +468,7 @@ int prg_cpd_set_source_weights(prg_cpd* h, const double* log_weights_hd, double 
     PRG_REQUIRE(uniform_ratio >= 0.0, PRG_ERR_INVALID, "prg_cpd_set_source_weights: uniform_ratio must be >= 0");
     prg::DeviceGuard g(h->device);
     h->uniform_ratio = uniform_ratio;
+    h->estep_state_live = false;
     if (!log_weights_hd) {
         PRG_HIP(hipStreamSynchronize(h->stream));
         if (h->srcw) (void)hipFree(h->srcw);
@@ -719,6 +721,7 @@ int prg_cpd_init_params(prg_cpd* h, const double* init_params_host) {
     PRG_HIP(hipGetLastError());
     if (init_params_host) PRG_HIP(hipStreamSynchronize(h->stream));  // host buffer may be reused by the caller
     h->have_colmin = false;  // a new registration starts: its first column pass takes no seed from the previous one
+    h->estep_state_live = false;
     h->eng = EngineSwitch();  // ... and it starts in the dense regime, with nothing remembered
     // the fused single sweep maps its column-side sums back through s R: R has to be a rotation (the M-step's own results are)
     h->init_rot_orthonormal = !init_params_host || is_rotation(init_params_host);
@@ -812,6 +815,7 @@ int prg_cpd_mstep(prg_cpd* h, int kind, int update_scale) {
                 "moments do not hold Y^T diag(p1) Y, which the affine M-step needs");
     prg::DeviceGuard g(h->device);
     k_mstep<<<1, 64, 0, h->stream>>>(h->moments, h->params, kind, update_scale, h->D);
+    h->estep_state_live = false;  // sigma2 in PARAMS is the next E-step's now
     PRG_HIP(hipGetLastError());
     // the single sweeps map their column-side sums back through s R: only a rigid fit leaves a rotation in the parameter block
     h->init_rot_orthonormal = kind == PRG_TF_RIGID;
@@ -837,6 +841,7 @@ int prg_cpd_iterate(prg_cpd* h, int kind, int update_scale, double w, int n_iter
         }
     }
     h->moments_only = keep;
+    if (n_iter > 0) h->estep_state_live = false;  // (every iteration ends with an M-step)
     PRG_TRY(st);
     PRG_HIP(hipGetLastError());
     return PRG_OK;
@@ -866,6 +871,7 @@ int prg_cpd_get_params(prg_cpd* h, double* params_host) {
 int prg_cpd_set_params(prg_cpd* h, const double* params_host) {
     PRG_REQUIRE(h && params_host, PRG_ERR_INVALID, "prg_cpd_set_params: NULL argument");
     prg::DeviceGuard g(h->device);
+    h->estep_state_live = false;
     PRG_HIP(hipMemcpyAsync(h->params, params_host, PRG_NPARAMS * sizeof(double), hipMemcpyHostToDevice, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->init_rot_orthonormal = is_rotation(params_host);  // (a caller-set linear part that is no rotation keeps the two sweeps)
@@ -943,6 +949,7 @@ int prg_cpd_moments_from_estep(prg_cpd* h, const double* pt1_hd, const double* p
     h->have_estep = true;  // rowacc / MOMENTS now hold an E-step result (the caller's): all 24 moments and the per-point block
     h->last_estep_fused = false;
     h->rowacc_valid = true;
+    h->estep_state_live = false;  // (tgt4.w is not this result's b_n)
     return PRG_OK;
 }
 

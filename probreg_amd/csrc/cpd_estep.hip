@@ -1245,6 +1245,7 @@ int finish_estep(prg_cpd* h, double w, bool col_queue, bool row_queue, bool rowa
     h->qcol_live = col_queue;
     h->qrow_live = row_queue;
     h->have_estep = true;
+    h->estep_state_live = true;
     h->rowacc_valid = rowacc_valid;
     h->have_colmin = true;  // colmin now describes the z4 of this E-step (motion is measured against it)
     h->last_w = w;

@@ -1084,6 +1084,7 @@ extern "C" int prg_cpd_mstep_nonrigid(prg_cpd* h, double lmd) {
                 "prg_cpd_mstep_nonrigid: needs build_g and an E-step first");
     PRG_REQUIRE(lmd > 0.0, PRG_ERR_INVALID, "prg_cpd_mstep_nonrigid: lmd must be > 0 (got %g)", lmd);
     prg::DeviceGuard g(h->device);
+    h->estep_state_live = false;  // sigma2 in PARAMS is the next E-step's now
     if (h->F) return mstep_nonrigid_lowrank(h, lmd);
     const int64_t m = h->M, mp = prg::round_up(m, NB), nblk = mp / NB;
     // workspace: S [mp*mp] | Linv [nblk*128*128] | b3, gb, v, sp (each <= 3 mp) | trace partials | info

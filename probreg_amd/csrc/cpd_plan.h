@@ -249,6 +249,12 @@ struct prg_cpd {
 
     bool have_source = false, have_target = false, have_estep = false;
     double last_w = 0.0;
+    // z4, tgt4.w (b_n), the weights and sigma2 in PARAMS are still those of ONE E-step: set by every prg_cpd_estep, cleared by
+    // whatever writes PARAMS, the weights or an E-step result of the caller's (what prg_cpd_correspond reads, cpd_correspond.hip)
+    bool estep_state_live = false;
+    // workspace of prg_cpd_correspond (packed clouds, partial lists, results): grows, never shrinks, freed with the plan
+    void* corr_buf = nullptr;
+    size_t corr_bytes = 0;
 
     // multi-GPU: when set, prg_cpd_estep / prg_cpd_init_sums end with the SUM all-reduce of the moment block (and, for a
     // non-rigid plan, of the per-point block) on the plan's stream; not owned by the plan

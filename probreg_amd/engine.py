@@ -335,9 +335,58 @@ class CpdPlan(object):
                                      ptr(v), ptr(d)))
         return v, d
 
+    # -- correspondences ------------------------------------------------------------------------
+    def correspondences(self, k=1, side="source"):
+        """The ``k`` best posterior matches of every point after an E-step (prg_cpd_correspond): for ``side="source"`` the
+        targets n of every source point m with the largest P_mn, for ``side="target"`` the sources of every target point,
+        in descending order, ties by the smaller index.  Returns ``(index int32, log2_prob float32, prob float64)``, each
+        ``(owned, k)`` in the caller's point order."""
+        if side not in ("source", "target"):
+            raise ValueError("side must be 'source' or 'target' (got %r)" % (side,))
+        k = int(k)
+        owned = self.m if side == "source" else self.n
+        shape = (owned, max(k, 0))
+        index = np.empty(shape, dtype=np.int32)
+        log2_prob = np.empty(shape, dtype=np.float32)
+        prob = np.empty(shape, dtype=np.float64)
+        check(lib.prg_cpd_correspond(self._h, 0 if side == "source" else 1, k, ptr(index), ptr(log2_prob), ptr(prob)))
+        return index, log2_prob, prob
+
     def synchronize(self):
         # a host read-back of the parameter block synchronises the plan's stream
         self.get_params()
+
+
+def correspond_tile_shape():
+    """(owned points per workgroup, streamed points per loop trip) of the correspondence sweep (prg_cpd_correspond_tile_shape;
+    host arithmetic)."""
+    a, b = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.prg_cpd_correspond_tile_shape(ctypes.byref(a), ctypes.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def topk_sweep(owned, streamed, kappa, k=1, owned_bias=None, streamed_bias=None, segments=0, device=None):
+    """For every row of ``owned`` (n_o, 2|3) the ``k`` rows of ``streamed`` with the largest float32 score
+    ``owned_bias + streamed_bias - kappa |owned - streamed|^2``, descending, ties by the smaller index (prg_topk_sweep: the
+    correspondence sweep on explicit arrays; zero biases make it an exact k-nearest-neighbour search).  ``segments``: pieces the
+    streamed cloud is cut into (0: automatic) - the result does not depend on it.  Returns ``(index int32, score float32)``,
+    each ``(n_o, k)``."""
+    _lib.require_gpu()
+    dev, st = _current_device_and_stream(device)
+    a = np.ascontiguousarray(owned, dtype=np.float32)
+    b = np.ascontiguousarray(streamed, dtype=np.float32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("topk_sweep: owned and streamed must be (n, 2) or (n, 3) arrays of one dimension.")
+    ab = None if owned_bias is None else np.ascontiguousarray(owned_bias, dtype=np.float32)
+    bb = None if streamed_bias is None else np.ascontiguousarray(streamed_bias, dtype=np.float32)
+    if (ab is not None and ab.shape != (a.shape[0],)) or (bb is not None and bb.shape != (b.shape[0],)):
+        raise ValueError("topk_sweep: a bias holds one value per point.")
+    k = int(k)
+    index = np.empty((a.shape[0], max(k, 0)), dtype=np.int32)
+    score = np.empty((a.shape[0], max(k, 0)), dtype=np.float32)
+    check(lib.prg_topk_sweep(dev, ctypes.c_void_p(st), ptr(a), ptr(ab), ptr(b), ptr(bb), int(a.shape[0]), int(b.shape[0]),
+                             int(a.shape[1]), float(kappa), k, int(segments), ptr(index), ptr(score)))
+    return index, score
 
 
 def batch_tile_shape():
