@@ -232,37 +232,21 @@ __global__ __launch_bounds__(kBlock) void k_unpack_points(const float4* __restri
     if (dim > 2) out[j * dim + 2] = v.z;
 }
 
-static void free_queue(SweepQueue& q) {
-    for (void* p : {(void*)q.masks, (void*)q.chunk, (void*)q.units, (void*)q.ctrl, (void*)q.ucount})
-        if (p) (void)hipFree(p);
-    q = SweepQueue();
-}
-
-// every device buffer the plan owns for its clouds and E-steps (the non-rigid state: prg::nonrigid_free)
-int free_plan_buffers(prg_cpd* h) {
-    free_queue(h->qcol);
-    free_queue(h->qrow);
-    void** const owned[] = {(void**)&h->src4, (void**)&h->z4, (void**)&h->tgt4, (void**)&h->pt1, (void**)&h->colpart, (void**)&h->rowpart,
-                            (void**)&h->rowacc, (void**)&h->mompart, &h->stage, (void**)&h->perm_src, (void**)&h->perm_tgt, (void**)&h->zmeta,
-                            (void**)&h->tmeta, (void**)&h->colmin, (void**)&h->motion, (void**)&h->srcw, (void**)&h->wgcount, (void**)&h->rorig,
-                            (void**)&h->corig, (void**)&h->zchunk, (void**)&h->tchunk, &h->corr_buf};
-    for (void** p : owned) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    h->wg_cap = 0;
-    h->stage_bytes = 0;
-    h->corr_bytes = 0;
-    return PRG_OK;
-}
-
 // capacity: the cloud + room for the segments' rounding to 256-point multiples + prefetch slack
 int cap_for(int64_t n) { return (int)prg::round_up(n + 64 * prg::kSuper + 1024, 1024); }
+
+// the motion slots, allocated once and zeroed (whichever cloud is set first)
+int ensure_motion(prg_cpd* h) {
+    if (h->motion.p) return PRG_OK;
+    PRG_HIP(h->motion.reset(16));
+    PRG_HIP(hipMemsetAsync(h->motion.p, 0, 16 * sizeof(unsigned), h->stream));
+    return PRG_OK;
+}
 
 // Spatial order of a cloud: sorted position -> original index, as the plan's device permutation.  [r6] The kd-tree order of
 // morton.h, built on the device (spatial_order.hip: ~2 ms per 100k points; PRG_SPATIAL_ORDER=kd_host: the host build, 17 ms;
 // =morton: the Z-curve of rounds 1 - 5).
-int morton_permutation(prg_cpd* h, const float* pts_hd, int64_t n, int dim, int** perm_dev, double* ext2 = nullptr,
+int morton_permutation(prg_cpd* h, const float* pts_hd, int64_t n, int dim, prg::DevBuf<int>* perm_dev, double* ext2 = nullptr,
                        float* box = nullptr) {
     std::vector<float> host((size_t)n * dim);
     PRG_HIP(hipMemcpy(host.data(), pts_hd, host.size() * sizeof(float), hipMemcpyDefault));
@@ -282,26 +266,16 @@ int morton_permutation(prg_cpd* h, const float* pts_hd, int64_t n, int dim, int*
             }
         }
     }
-    if (*perm_dev) (void)hipFree(*perm_dev);
-    *perm_dev = nullptr;
-    PRG_HIP(hipMalloc((void**)perm_dev, (size_t)n * sizeof(int)));
+    PRG_HIP(perm_dev->reset(n));
     const std::string& order = prg::cpd_env().spatial_order;
     if (order != "morton" && order != "kd_host") {
         // the caller's layout, [n][dim] floats, goes to the staging buffer (where k_pack_cloud reads it anyway) and is ordered there
         PRG_TRY(prg::ensure_stage(h, (size_t)n * dim * sizeof(float)));
-        PRG_HIP(hipMemcpyAsync(h->stage, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        return prg::device_kd_order((const float*)h->stage, n, dim, *perm_dev, h->stream);
+        PRG_HIP(hipMemcpyAsync(h->stage.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        return prg::device_kd_order((const float*)h->stage.p, n, dim, perm_dev->p, h->stream);
     }
     const std::vector<int> perm = order == "morton" ? prg::morton_order(host.data(), n, dim) : prg::kd_order(host.data(), n, dim);
-    PRG_HIP(hipMemcpy(*perm_dev, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    return PRG_OK;
-}
-
-template <typename T>
-int ensure_exact(T** p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    PRG_HIP(hipMalloc((void**)p, count * sizeof(T)));
+    PRG_HIP(hipMemcpy(perm_dev->p, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
     return PRG_OK;
 }
 
@@ -309,15 +283,9 @@ int ensure_exact(T** p, size_t count) {
 
 namespace prg {
 int ensure_stage(prg_cpd* h, size_t bytes) {
-    if (h->stage && h->stage_bytes >= bytes) return PRG_OK;
-    if (h->stage) {
-        PRG_HIP(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->stage);
-    }
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    PRG_HIP(hipMalloc(&h->stage, bytes));
-    h->stage_bytes = bytes;
+    if (h->stage.cap >= (int64_t)bytes) return PRG_OK;
+    if (h->stage.p) PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(h->stage.reset((int64_t)bytes));
     return PRG_OK;
 }
 
@@ -342,18 +310,15 @@ const CpdEnv& cpd_env() {
     return env;
 }
 
-// Device / mapped-host state of the engine decision: the decision itself, the matrix-core sweeps' tile counters and the LOCAL
-// target's sum |x|^2 (prg_cpd_init_sums keeps a copy here: the caller all-reduces the moments block it also writes it to).
+// Device / mapped-host state of the engine decision (EngineState, cpd_plan.h), allocated once
 int ensure_engine_state(prg_cpd* h) {
-    if (h->eng_host) return PRG_OK;
-    PRG_HIP(hipHostMalloc((void**)&h->eng_host, sizeof(EngineDecision), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h->eng_host, 0, sizeof(EngineDecision));
-    PRG_HIP(hipHostGetDevicePointer((void**)&h->eng_host_dev, h->eng_host, 0));
-    const size_t bytes = sizeof(EngineDecision) + 2 * sizeof(unsigned long long) + 4 * sizeof(double);
-    PRG_HIP(hipMalloc((void**)&h->eng_dev, bytes));
-    PRG_HIP(hipMemsetAsync(h->eng_dev, 0, bytes, h->stream));
-    h->eng_work = reinterpret_cast<unsigned long long*>(h->eng_dev + 1);
-    h->tsum_local = reinterpret_cast<double*>(h->eng_work + 2);
+    if (h->eng_dev.p) return PRG_OK;
+    PRG_HIP(h->eng_host.ensure(1, kMailboxFlags));
+    h->eng_host_dev = h->eng_host.dev;
+    PRG_HIP(h->eng_dev.reset(1));
+    PRG_HIP(hipMemsetAsync(h->eng_dev.p, 0, sizeof(EngineState), h->stream));
+    h->eng_work = h->eng_dev.p->work;
+    h->tsum_local = h->eng_dev.p->tsum;
     return PRG_OK;
 }
 }  // namespace prg
@@ -379,15 +344,15 @@ int prg_cpd_create(prg_cpd** out, int device, void* hip_stream) {
     if (const char* eng = getenv("PRG_DENSE_ENGINE")) h->dense_engine = std::max(0, std::min(2, atoi(eng)));
     if (const char* eng = getenv("PRG_SPARSE_ENGINE")) h->sparse_engine = std::max(0, std::min(2, atoi(eng)));
     if (const char* eng = getenv("PRG_RESID_SWEEP")) h->resid_sweep = atoi(eng) != 0;  // (A/B runs of the two-sweep sparse regime)
-    hipError_t e = hipMalloc((void**)&h->state, (PRG_NMOMENTS + PRG_NPARAMS) * sizeof(double));
+    const hipError_t e = h->state.reset(PRG_NMOMENTS + PRG_NPARAMS);
     if (e != hipSuccess) {
         delete h;
-        prg::set_error("prg_cpd_create: hipMalloc failed: %s", hipGetErrorString(e));
+        prg::set_error("prg_cpd_create: device allocation failed: %s", hipGetErrorString(e));
         return PRG_ERR_HIP;
     }
-    h->moments = h->state;
-    h->params = h->state + PRG_NMOMENTS;
-    k_zero_doubles<<<1, 64, 0, h->stream>>>(h->state, PRG_NMOMENTS + PRG_NPARAMS);
+    h->moments = h->state.p;
+    h->params = h->state.p + PRG_NMOMENTS;
+    k_zero_doubles<<<1, 64, 0, h->stream>>>(h->state.p, PRG_NMOMENTS + PRG_NPARAMS);
     *out = h;
     return PRG_OK;
 }
@@ -396,13 +361,8 @@ int prg_cpd_destroy(prg_cpd* h) {
     if (!h) return PRG_OK;
     prg::DeviceGuard g(h->device);
     (void)hipStreamSynchronize(h->stream);
-    free_plan_buffers(h);
     prg::nonrigid_free(h);
-    if (h->state) (void)hipFree(h->state);
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->eng_host) (void)hipHostFree(h->eng_host);
-    if (h->eng_dev) (void)hipFree(h->eng_dev);
-    delete h;
+    delete h;  // (its buffers go with it, on the plan's device)
     return PRG_OK;
 }
 
@@ -414,52 +374,32 @@ int prg_cpd_set_source(prg_cpd* h, const float* source_hd, int64_t m, int dim) {
                 "prg_cpd_set_source: dim %d does not match target dim %d", dim, h->D);
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
+    // no source until this one is complete: a failure below leaves a plan that says so, whatever the arrays hold by then
+    h->have_source = h->have_estep = h->estep_state_live = false;
+    prg::nonrigid_free(h);  // ... and nothing that belongs to the previous source: its kernel matrix, W, priors and weights
+    h->srcw.release();
+    h->uniform_ratio = 0.0;
     const int64_t cap = cap_for(m);
-    if (cap != h->Mcap) {
-        if (h->src4) (void)hipFree(h->src4);
-        if (h->z4) (void)hipFree(h->z4);
-        if (h->rowacc) (void)hipFree(h->rowacc);
-        h->src4 = h->z4 = nullptr;
-        h->rowacc = nullptr;
-        PRG_HIP(hipMalloc((void**)&h->src4, cap * sizeof(float4)));
-        PRG_HIP(hipMalloc((void**)&h->z4, cap * sizeof(float4)));
-        PRG_HIP(hipMalloc((void**)&h->rowacc, 4 * cap * sizeof(double)));
-    }
-    if (cap != h->Mcap || !h->zmeta) {
-        PRG_TRY(ensure_exact(&h->zmeta, (size_t)(cap / prg::kGroup) * 8));
-        if (!h->motion) {
-            PRG_TRY(ensure_exact(&h->motion, 16));
-            PRG_HIP(hipMemsetAsync(h->motion, 0, 16 * sizeof(unsigned), h->stream));
-        }
-        PRG_TRY(ensure_exact(&h->rorig, (size_t)(cap / prg::kMfmaWgPoints) + 4));
-        PRG_TRY(ensure_exact(&h->zchunk, (size_t)(cap / prg::kSuper) * 8));
-    }
-    h->M = m;
-    h->D = dim;
-    h->Mcap = cap;
-    if (h->opt_sort_src) {
+    PRG_HIP(h->size_source(cap));  // (all of the group or none of it, Mcap with it)
+    PRG_TRY(ensure_motion(h));
+    if (h->opt_sort_src)
         PRG_TRY(morton_permutation(h, source_hd, m, dim, &h->perm_src, &h->sext2));
-    } else if (h->perm_src) {
-        (void)hipFree(h->perm_src);
-        h->perm_src = nullptr;
-    }
+    else
+        h->perm_src.release();
     PRG_TRY(prg::ensure_stage(h, (size_t)m * dim * sizeof(float)));
-    PRG_HIP(hipMemcpyAsync(h->stage, source_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, h->stream));
-    k_pack_cloud<<<grid1(cap), kBlock, 0, h->stream>>>((const float*)h->stage, m, dim, h->src4, cap, prg::kSrcPad,
-                                                       0.f, h->perm_src);
-    k_pack_cloud<<<grid1(cap), kBlock, 0, h->stream>>>((const float*)h->stage, m, dim, h->z4, cap, prg::kSrcPad, 0.f,
-                                                       h->perm_src);
+    PRG_HIP(hipMemcpyAsync(h->stage.p, source_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, h->stream));
+    k_pack_cloud<<<grid1(cap), kBlock, 0, h->stream>>>((const float*)h->stage.p, m, dim, h->src4.p, cap, prg::kSrcPad,
+                                                       0.f, h->perm_src.p);
+    k_pack_cloud<<<grid1(cap), kBlock, 0, h->stream>>>((const float*)h->stage.p, m, dim, h->z4.p, cap, prg::kSrcPad, 0.f,
+                                                       h->perm_src.p);
     // boxes of the whole padded array once; the per-iteration transform kernel refreshes the blocks with real points
-    k_group_meta<<<grid1(cap / prg::kGroup), kBlock, 0, h->stream>>>(h->z4, cap / prg::kGroup, h->zmeta);
+    k_group_meta<<<grid1(cap / prg::kGroup), kBlock, 0, h->stream>>>(h->z4.p, cap / prg::kGroup, h->zmeta.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));  // the caller's buffer may be pageable host memory
+    h->M = m;
+    h->D = dim;
     h->have_colmin = false;
     h->have_source = true;
-    h->have_estep = false;
-    prg::nonrigid_free(h);
-    if (h->srcw) (void)hipFree(h->srcw);  // weights belong to the previous source
-    h->srcw = nullptr;
-    h->uniform_ratio = 0.0;
     return PRG_OK;
 }
 
@@ -471,8 +411,7 @@ int prg_cpd_set_source_weights(prg_cpd* h, const double* log_weights_hd, double 
     h->estep_state_live = false;
     if (!log_weights_hd) {
         PRG_HIP(hipStreamSynchronize(h->stream));
-        if (h->srcw) (void)hipFree(h->srcw);
-        h->srcw = nullptr;
+        h->srcw.release();
         return PRG_OK;
     }
     hipPointerAttribute_t attr;
@@ -483,10 +422,10 @@ int prg_cpd_set_source_weights(prg_cpd* h, const double* log_weights_hd, double 
             PRG_REQUIRE(log_weights_hd[i] <= 0.0, PRG_ERR_INVALID,
                         "prg_cpd_set_source_weights: log-weight %lld is %g, must be <= 0 (and not NaN)", (long long)i,
                         log_weights_hd[i]);
-    if (!h->srcw) PRG_HIP(hipMalloc((void**)&h->srcw, (size_t)h->Mcap * sizeof(float)));
+    if (!h->srcw.p) PRG_HIP(h->srcw.reset(h->Mcap));
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * sizeof(double)));
-    PRG_HIP(hipMemcpyAsync(h->stage, log_weights_hd, (size_t)h->M * sizeof(double), hipMemcpyDefault, h->stream));
-    k_gather_weights<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage, h->M, h->perm_src, h->srcw);
+    PRG_HIP(hipMemcpyAsync(h->stage.p, log_weights_hd, (size_t)h->M * sizeof(double), hipMemcpyDefault, h->stream));
+    k_gather_weights<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage.p, h->M, h->perm_src.p, h->srcw.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_colmin = false;
@@ -501,55 +440,37 @@ int prg_cpd_set_target(prg_cpd* h, const float* target_hd, int64_t n_local, int 
                 "prg_cpd_set_target: dim %d does not match source dim %d", dim, h->D);
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
+    h->have_target = h->have_estep = h->estep_state_live = false;  // (as in prg_cpd_set_source)
     // (the sums of the previous target no longer describe this one: no lean row pass until prg_cpd_init_sums has run)
     if (h->tsum_local) PRG_HIP(hipMemsetAsync(h->tsum_local, 0, 4 * sizeof(double), h->stream));
     const int64_t cap = cap_for(n_local);
-    if (cap != h->Ncap) {
-        if (h->tgt4) (void)hipFree(h->tgt4);
-        if (h->pt1) (void)hipFree(h->pt1);
-        h->tgt4 = nullptr;
-        h->pt1 = nullptr;
-        PRG_HIP(hipMalloc((void**)&h->tgt4, cap * sizeof(float4)));
-        PRG_HIP(hipMalloc((void**)&h->pt1, cap * sizeof(float)));
-    }
-    if (cap != h->Ncap || !h->tmeta) {
-        PRG_TRY(ensure_exact(&h->tmeta, (size_t)(cap / prg::kGroup) * 8));
-        PRG_TRY(ensure_exact(&h->tchunk, (size_t)(cap / prg::kSuper) * 8));
-        PRG_TRY(ensure_exact(&h->corig, (size_t)(cap / prg::kMfmaWgPoints) + 4));
-        PRG_TRY(ensure_exact(&h->colmin, (size_t)cap + (size_t)cap / prg::kGroup));  // + per-group maxima
-        PRG_HIP(hipMemsetAsync(h->colmin, 0, ((size_t)cap + (size_t)cap / prg::kGroup) * sizeof(float), h->stream));
-    }
-    if (!h->motion) {
-        PRG_TRY(ensure_exact(&h->motion, 16));
-        PRG_HIP(hipMemsetAsync(h->motion, 0, 16 * sizeof(unsigned), h->stream));
-    }
+    bool fresh = false;
+    PRG_HIP(h->size_target(cap, &fresh));
+    if (fresh) PRG_HIP(hipMemsetAsync(h->colmin.p, 0, (size_t)h->colmin.cap * sizeof(float), h->stream));
+    PRG_TRY(ensure_motion(h));
+    if (h->opt_sort_tgt)
+        PRG_TRY(morton_permutation(h, target_hd, n_local, dim, &h->perm_tgt, &h->text2, h->tbox));
+    else
+        h->perm_tgt.release();
+    PRG_TRY(prg::ensure_stage(h, (size_t)n_local * dim * sizeof(float)));
+    PRG_HIP(hipMemcpyAsync(h->stage.p, target_hd, (size_t)n_local * dim * sizeof(float), hipMemcpyDefault, h->stream));
+    k_pack_cloud<<<grid1(cap), kBlock, 0, h->stream>>>((const float*)h->stage.p, n_local, dim, h->tgt4.p, cap,
+                                                       prg::kTgtPad, 0.f, h->perm_tgt.p);
+    // the target never moves: its group boxes are written once (k_colfinal refreshes the b_n range)
+    k_group_meta<<<grid1(cap / prg::kGroup), kBlock, 0, h->stream>>>(h->tgt4.p, cap / prg::kGroup, h->tmeta.p);
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipStreamSynchronize(h->stream));
     h->N = n_local;
     h->Nglobal = n_global;
     h->D = dim;
-    h->Ncap = cap;
-    if (h->opt_sort_tgt) {
-        PRG_TRY(morton_permutation(h, target_hd, n_local, dim, &h->perm_tgt, &h->text2, h->tbox));
-    } else if (h->perm_tgt) {
-        (void)hipFree(h->perm_tgt);
-        h->perm_tgt = nullptr;
-    }
-    PRG_TRY(prg::ensure_stage(h, (size_t)n_local * dim * sizeof(float)));
-    PRG_HIP(hipMemcpyAsync(h->stage, target_hd, (size_t)n_local * dim * sizeof(float), hipMemcpyDefault, h->stream));
-    k_pack_cloud<<<grid1(cap), kBlock, 0, h->stream>>>((const float*)h->stage, n_local, dim, h->tgt4, cap,
-                                                       prg::kTgtPad, 0.f, h->perm_tgt);
-    // the target never moves: its group boxes are written once (k_colfinal refreshes the b_n range)
-    k_group_meta<<<grid1(cap / prg::kGroup), kBlock, 0, h->stream>>>(h->tgt4, cap / prg::kGroup, h->tmeta);
-    PRG_HIP(hipGetLastError());
-    PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_colmin = false;
     h->have_target = true;
-    h->have_estep = false;
     return PRG_OK;
 }
 
 int prg_cpd_bind_moments(prg_cpd* h, double* moments_dev) {
     PRG_REQUIRE(h, PRG_ERR_INVALID, "prg_cpd_bind_moments: NULL handle");
-    h->moments = moments_dev ? moments_dev : h->state;
+    h->moments = moments_dev ? moments_dev : h->state.p;
     return PRG_OK;
 }
 
@@ -675,8 +596,8 @@ int prg_cpd_init_sums(prg_cpd* h) {
     PRG_TRY(ensure_mompart(h));
     const int nblk = (int)prg::ceil_div(h->N, kBlock);
     k_zero_doubles<<<1, 64, 0, h->stream>>>(h->moments, PRG_NMOMENTS);
-    k_cloud_sums<<<nblk, kBlock, 0, h->stream>>>(h->tgt4, h->N, h->mompart);
-    prg::reduce_partials(h, h->mompart, nblk, 4, h->moments, 24);
+    k_cloud_sums<<<nblk, kBlock, 0, h->stream>>>(h->tgt4.p, h->N, h->mompart.p);
+    prg::reduce_partials(h, h->mompart.p, nblk, 4, h->moments, 24);
     PRG_HIP(hipGetLastError());
     PRG_TRY(prg::ensure_engine_state(h));
     PRG_HIP(hipMemcpyAsync(h->tsum_local, h->moments + 24, 4 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -708,14 +629,14 @@ int prg_cpd_init_params(prg_cpd* h, const double* init_params_host) {
     prg::DeviceGuard g(h->device);
     PRG_TRY(ensure_mompart(h));
     const int nblk = (int)prg::ceil_div(h->M, kBlock);
-    double* srcsum = h->mompart + (h->mompart_elems - 64);
+    double* srcsum = prg::mom_scratch(*h);
     double* init_dev = nullptr;
     if (init_params_host) {
         init_dev = srcsum + 8;
         PRG_HIP(hipMemcpyAsync(init_dev, init_params_host, 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    k_cloud_sums<<<nblk, kBlock, 0, h->stream>>>(h->src4, h->M, h->mompart);
-    prg::reduce_partials(h, h->mompart, nblk, 4, srcsum, 0);
+    k_cloud_sums<<<nblk, kBlock, 0, h->stream>>>(h->src4.p, h->M, h->mompart.p);
+    prg::reduce_partials(h, h->mompart.p, nblk, 4, srcsum, 0);
     k_init_params<<<1, 64, 0, h->stream>>>(h->moments, srcsum, h->params, (double)h->M, (double)h->Nglobal, h->D,
                                            init_dev);
     PRG_HIP(hipGetLastError());
@@ -768,13 +689,13 @@ int prg_cpd_pair_counts(prg_cpd* h, double* col_pairs, double* row_pairs) {
         const SweepQueue& q = pass ? h->qrow : h->qcol;
         if ((pass ? h->wg_row : h->wg_col) != -1) continue;
         int nu[2] = {0, 0};  // fine units [0, nu[0]), coarse units [cap_soft, cap_soft + nu[1])
-        PRG_HIP(hipMemcpyAsync(nu, q.ctrl + 8, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(nu, q.ctrl.p + 8, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
         double sum = 0.0;
         for (int part = 0; part < 2; ++part) {
             if (nu[part] <= 0) continue;
             std::vector<unsigned> host((size_t)nu[part]);
-            PRG_HIP(hipMemcpyAsync(host.data(), q.ucount + (part ? q.cap_soft : 0), (size_t)nu[part] * sizeof(unsigned),
+            PRG_HIP(hipMemcpyAsync(host.data(), q.ucount.p + (part ? q.cap_soft : 0), (size_t)nu[part] * sizeof(unsigned),
                                    hipMemcpyDeviceToHost, h->stream));
             PRG_HIP(hipStreamSynchronize(h->stream));
             for (int i = 0; i < nu[part]; ++i) sum += host[(size_t)i];
@@ -782,8 +703,8 @@ int prg_cpd_pair_counts(prg_cpd* h, double* col_pairs, double* row_pairs) {
         *(pass ? row_pairs : col_pairs) = sum * 128.0 * prg::kGroup;
     }
     if (h->wg_col > 0 || h->wg_row > 0) {
-        std::vector<unsigned> host((size_t)h->wg_cap * 2);
-        PRG_HIP(hipMemcpyAsync(host.data(), h->wgcount, host.size() * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        std::vector<unsigned> host((size_t)h->wg_cap() * 2);
+        PRG_HIP(hipMemcpyAsync(host.data(), h->wgcount.p, host.size() * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
         if (h->wg_col > 0) {
             double s = 0.0;
@@ -792,7 +713,7 @@ int prg_cpd_pair_counts(prg_cpd* h, double* col_pairs, double* row_pairs) {
         }
         if (h->wg_row > 0) {
             double s = 0.0;
-            for (int64_t i = 0; i < h->wg_row; ++i) s += host[(size_t)(h->wg_cap + i)];
+            for (int64_t i = 0; i < h->wg_row; ++i) s += host[(size_t)(h->wg_cap() + i)];
             *row_pairs = s * h->wg_row_pairs;
         }
     }
@@ -852,13 +773,13 @@ int prg_cpd_get_params(prg_cpd* h, double* params_host) {
     prg::DeviceGuard g(h->device);
     // through pinned memory: a device->host copy into pageable memory pays ~100 us of staging, and the EM driver
     // reads the parameter block every iteration when it has a tolerance to test
-    if (!h->pinned) PRG_HIP(hipHostMalloc((void**)&h->pinned, 64 * sizeof(double), hipHostMallocDefault));
-    PRG_HIP(hipMemcpyAsync(h->pinned, h->params, PRG_NPARAMS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    int* host_info = reinterpret_cast<int*>(h->pinned + 48);
+    PRG_HIP(h->pinned.ensure(64));
+    PRG_HIP(hipMemcpyAsync(h->pinned.p, h->params, PRG_NPARAMS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    int* host_info = reinterpret_cast<int*>(h->pinned.p + 48);
     *host_info = 0;
     if (h->nr_info) PRG_HIP(hipMemcpyAsync(host_info, h->nr_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < PRG_NPARAMS; ++i) params_host[i] = h->pinned[i];
+    for (int i = 0; i < PRG_NPARAMS; ++i) params_host[i] = h->pinned.p[i];
     if (*host_info != 0) {  // a non-rigid M-step since the last read-back hit a non-positive pivot (it does not stall to say so)
         const int pivot = *host_info - 1;
         PRG_HIP(hipMemsetAsync(h->nr_info, 0, sizeof(int), h->stream));
@@ -896,18 +817,18 @@ int prg_cpd_get_estep(prg_cpd* h, double* pt1_hd, double* p1_hd, double* px_hd) 
     const size_t need = (size_t)(h->N > h->M * h->D ? h->N : h->M * h->D) * sizeof(double);
     PRG_TRY(prg::ensure_stage(h, need));
     if (pt1_hd) {
-        k_float_to_double<<<grid1(h->N), kBlock, 0, h->stream>>>(h->pt1, (double*)h->stage, h->N, h->perm_tgt);
-        PRG_HIP(hipMemcpyAsync(pt1_hd, h->stage, h->N * sizeof(double), hipMemcpyDefault, h->stream));
+        k_float_to_double<<<grid1(h->N), kBlock, 0, h->stream>>>(h->pt1.p, (double*)h->stage.p, h->N, h->perm_tgt.p);
+        PRG_HIP(hipMemcpyAsync(pt1_hd, h->stage.p, h->N * sizeof(double), hipMemcpyDefault, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
     }
     if (p1_hd) {
-        k_scatter_double<<<grid1(h->M), kBlock, 0, h->stream>>>(h->rowacc, (double*)h->stage, h->M, h->perm_src);
-        PRG_HIP(hipMemcpyAsync(p1_hd, h->stage, h->M * sizeof(double), hipMemcpyDefault, h->stream));
+        k_scatter_double<<<grid1(h->M), kBlock, 0, h->stream>>>(h->rowacc.p, (double*)h->stage.p, h->M, h->perm_src.p);
+        PRG_HIP(hipMemcpyAsync(p1_hd, h->stage.p, h->M * sizeof(double), hipMemcpyDefault, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
     }
     if (px_hd) {
-        k_pack_px<<<grid1(h->M), kBlock, 0, h->stream>>>(h->rowacc, h->Mcap, h->M, h->D, (double*)h->stage, h->perm_src);
-        PRG_HIP(hipMemcpyAsync(px_hd, h->stage, h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
+        k_pack_px<<<grid1(h->M), kBlock, 0, h->stream>>>(h->rowacc.p, h->Mcap, h->M, h->D, (double*)h->stage.p, h->perm_src.p);
+        PRG_HIP(hipMemcpyAsync(px_hd, h->stage.p, h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
     }
     PRG_HIP(hipGetLastError());
@@ -918,8 +839,8 @@ int prg_cpd_get_tsource(prg_cpd* h, float* tsource_hd) {
     PRG_REQUIRE(h && h->have_source && tsource_hd, PRG_ERR_STATE, "prg_cpd_get_tsource: source not set");
     prg::DeviceGuard g(h->device);
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(float)));
-    k_unpack_points<<<grid1(h->M), kBlock, 0, h->stream>>>(h->z4, h->M, h->D, (float*)h->stage, h->perm_src);
-    PRG_HIP(hipMemcpyAsync(tsource_hd, h->stage, h->M * h->D * sizeof(float), hipMemcpyDefault, h->stream));
+    k_unpack_points<<<grid1(h->M), kBlock, 0, h->stream>>>(h->z4.p, h->M, h->D, (float*)h->stage.p, h->perm_src.p);
+    PRG_HIP(hipMemcpyAsync(tsource_hd, h->stage.p, h->M * h->D * sizeof(float), hipMemcpyDefault, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }
@@ -932,18 +853,18 @@ int prg_cpd_moments_from_estep(prg_cpd* h, const double* pt1_hd, const double* p
                  nb_px = (size_t)h->M * h->D * sizeof(double);
     PRG_TRY(prg::ensure_stage(h, nb_pt1 + nb_p1 + nb_px));
     PRG_TRY(ensure_mompart(h));
-    double* d_pt1 = (double*)h->stage;
+    double* d_pt1 = (double*)h->stage.p;
     double* d_p1 = d_pt1 + h->N;
     double* d_px = d_p1 + h->M;
     PRG_HIP(hipMemcpyAsync(d_pt1, pt1_hd, nb_pt1, hipMemcpyDefault, h->stream));
     PRG_HIP(hipMemcpyAsync(d_p1, p1_hd, nb_p1, hipMemcpyDefault, h->stream));
     PRG_HIP(hipMemcpyAsync(d_px, px_hd, nb_px, hipMemcpyDefault, h->stream));
     const int nblk = prg::mom_blocks(*h);
-    k_moments_from_arrays<<<nblk, kBlock, 0, h->stream>>>(d_pt1, d_p1, d_px, h->D, h->M, h->N, h->src4, h->tgt4,
-                                                          h->perm_src, h->perm_tgt, h->mompart);
-    prg::reduce_partials(h, h->mompart, nblk, kMomComp, h->moments, 0);
-    k_rowacc_from_arrays<<<nblk, kBlock, 0, h->stream>>>(d_pt1, d_p1, d_px, h->D, h->M, h->N, h->Mcap, h->perm_src,
-                                                         h->perm_tgt, h->rowacc, h->pt1);
+    k_moments_from_arrays<<<nblk, kBlock, 0, h->stream>>>(d_pt1, d_p1, d_px, h->D, h->M, h->N, h->src4.p, h->tgt4.p,
+                                                          h->perm_src.p, h->perm_tgt.p, h->mompart.p);
+    prg::reduce_partials(h, h->mompart.p, nblk, kMomComp, h->moments, 0);
+    k_rowacc_from_arrays<<<nblk, kBlock, 0, h->stream>>>(d_pt1, d_p1, d_px, h->D, h->M, h->N, h->Mcap, h->perm_src.p,
+                                                         h->perm_tgt.p, h->rowacc.p, h->pt1.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_estep = true;  // rowacc / MOMENTS now hold an E-step result (the caller's): all 24 moments and the per-point block

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -31,18 +32,18 @@ struct prg_cpd_batch {
     hipStream_t stream = nullptr;
     int dim = 3, B = 0, ntiles = 0;
     int64_t Mtot = 0, Ntot = 0;
-    float4* src4 = nullptr;     // [Mtot] centred source points (fp32, as the single plan uploads them)
-    float4* tgt4 = nullptr;     // [Ntot]
-    int64_t* soff = nullptr;    // [B + 1] first source point of every problem
-    int64_t* toff = nullptr;    // [B + 1]
-    int4* tiles = nullptr;      // [ntiles] (problem, first column, column count, 0)
-    int* tile_first = nullptr;  // [B + 1] first tile of every problem
-    double* params = nullptr;   // [B][PRG_NPARAMS]
-    double* part = nullptr;     // [ntiles][kBatchComp]
-    double* init = nullptr;     // [B][16]
-    double* wtol = nullptr;     // [2][B]: w, tol
-    int* flags = nullptr;       // done[B], n_iter[B], active
-    void* pinned = nullptr;     // host staging: 2 B doubles (w, tol), then one int (active)
+    prg::DevBuf<float4> src4;     // [Mtot] centred source points (fp32, as the single plan uploads them)
+    prg::DevBuf<float4> tgt4;     // [Ntot]
+    prg::DevBuf<int64_t> soff;    // [B + 1] first source point of every problem
+    prg::DevBuf<int64_t> toff;    // [B + 1]
+    prg::DevBuf<int4> tiles;      // [ntiles] (problem, first column, column count, 0)
+    prg::DevBuf<int> tile_first;  // [B + 1] first tile of every problem
+    prg::DevBuf<double> params;   // [B][PRG_NPARAMS]
+    prg::DevBuf<double> part;     // [ntiles][kBatchComp]
+    prg::DevBuf<double> init;     // [B][16]
+    prg::DevBuf<double> wtol;     // [2][B]: w, tol
+    prg::DevBuf<int> flags;       // done[B], n_iter[B], active
+    prg::HostBuf<double> pinned;  // host staging: 2 B doubles (w, tol), then one int (active) in 8 more
     std::vector<double> wtol_host;  // what wtol holds (w, tol of the last prg_cpd_batch_iterate)
     bool initialised = false;
 };
@@ -354,22 +355,6 @@ __global__ __launch_bounds__(64) void k_batch_mstep(const double* __restrict__ p
     }
 }
 
-void free_batch(prg_cpd_batch* h) {
-    void* const owned[] = {h->src4, h->tgt4, h->soff, h->toff, h->tiles, h->tile_first, h->params,
-                           h->part, h->init, h->wtol, h->flags};
-    for (void* p : owned)
-        if (p) (void)hipFree(p);
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    delete h;
-}
-
-template <typename T>
-int upload(T** dev, const T* host, size_t count, hipStream_t st) {
-    PRG_HIP(hipMalloc((void**)dev, count * sizeof(T)));
-    PRG_HIP(hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, st));
-    return PRG_OK;
-}
-
 int check_sizes(const char* who, int nb, const int64_t* m, const int64_t* n) {
     PRG_REQUIRE(nb > 0 && m && n, PRG_ERR_INVALID, "%s: need B > 0 and both size tables", who);
     for (int b = 0; b < nb; ++b)
@@ -425,20 +410,12 @@ int prg_cpd_batch_create(prg_cpd_batch** out, int device, void* hip_stream, int 
                 count);
     prg::DeviceGuard g(device);
     PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_cpd_batch_create: hipSetDevice(%d) failed", device);
-    prg_cpd_batch* h = new (std::nothrow) prg_cpd_batch();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_cpd_batch_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    h->dim = dim;
-    h->B = nb;
-    h->ntiles = (int)nt;
-    h->Mtot = source_offsets[nb];
-    h->Ntot = target_offsets[nb];
     // host side of the layout: fp32 points (what the single plan uploads), the tile table and every problem's first tile
-    std::vector<float4> s4((size_t)h->Mtot), t4((size_t)h->Ntot);
-    for (int64_t i = 0; i < h->Mtot; ++i)
+    const int64_t mtot = source_offsets[nb], ntot = target_offsets[nb];
+    std::vector<float4> s4((size_t)mtot), t4((size_t)ntot);
+    for (int64_t i = 0; i < mtot; ++i)
         s4[(size_t)i] = make_float4((float)sources[i * dim], (float)sources[i * dim + 1], dim > 2 ? (float)sources[i * dim + 2] : 0.f, 0.f);
-    for (int64_t i = 0; i < h->Ntot; ++i)
+    for (int64_t i = 0; i < ntot; ++i)
         t4[(size_t)i] = make_float4((float)targets[i * dim], (float)targets[i * dim + 1], dim > 2 ? (float)targets[i * dim + 2] : 0.f, 0.f);
     std::vector<int> t3((size_t)nt * 3);
     int64_t again = 0;
@@ -449,37 +426,41 @@ int prg_cpd_batch_create(prg_cpd_batch** out, int device, void* hip_stream, int 
         tiles[(size_t)i] = make_int4(t3[3 * i], t3[3 * i + 1], t3[3 * i + 2], 0);
         first[(size_t)t3[3 * i] + 1] = (int)i + 1;
     }
-    int st = PRG_OK;
-    auto step = [&](int s) { if (st == PRG_OK) st = s; };
-    step(upload(&h->src4, s4.data(), s4.size(), h->stream));
-    step(upload(&h->tgt4, t4.data(), t4.size(), h->stream));
-    step(upload(&h->soff, source_offsets, (size_t)nb + 1, h->stream));
-    step(upload(&h->toff, target_offsets, (size_t)nb + 1, h->stream));
-    step(upload(&h->tiles, tiles.data(), tiles.size(), h->stream));
-    step(upload(&h->tile_first, first.data(), first.size(), h->stream));
-    auto alloc = [&](void** p, size_t bytes) -> int {
-        PRG_HIP(hipMalloc(p, bytes));
-        PRG_HIP(hipMemsetAsync(*p, 0, bytes, h->stream));
+    // the handle comes AFTER the host vectors: on a failure below its buffers are freed - which drains the stream and the uploads
+    // still queued from those vectors - before the vectors go
+    std::unique_ptr<prg_cpd_batch> h(new (std::nothrow) prg_cpd_batch());  // (a failure below frees what it holds by then)
+    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_cpd_batch_create: out of host memory");
+    h->device = device;
+    h->stream = (hipStream_t)hip_stream;
+    h->dim = dim;
+    h->B = nb;
+    h->ntiles = (int)nt;
+    h->Mtot = mtot;
+    h->Ntot = ntot;
+    auto put = [&h](auto& buf, const auto* host, size_t count) -> int {
+        PRG_HIP(buf.reset((int64_t)count));
+        PRG_HIP(hipMemcpyAsync(buf.p, host, count * sizeof(*host), hipMemcpyHostToDevice, h->stream));
         return PRG_OK;
     };
-    step(alloc((void**)&h->params, (size_t)nb * PRG_NPARAMS * sizeof(double)));
-    step(alloc((void**)&h->part, (size_t)nt * kBatchComp * sizeof(double)));
-    step(alloc((void**)&h->init, (size_t)nb * 16 * sizeof(double)));
-    step(alloc((void**)&h->wtol, (size_t)nb * 2 * sizeof(double)));
-    step(alloc((void**)&h->flags, ((size_t)nb * 2 + 1) * sizeof(int)));
-    if (st == PRG_OK && hipHostMalloc(&h->pinned, (size_t)nb * 2 * sizeof(double) + 64, hipHostMallocDefault) != hipSuccess) {
-        prg::set_error("prg_cpd_batch_create: hipHostMalloc failed");
-        st = PRG_ERR_HIP;
-    }
-    if (st == PRG_OK && hipStreamSynchronize(h->stream) != hipSuccess) {  // (the uploads read this call's own host vectors)
-        prg::set_error("prg_cpd_batch_create: upload failed");
-        st = PRG_ERR_HIP;
-    }
-    if (st != PRG_OK) {
-        free_batch(h);
-        return st;
-    }
-    *out = h;
+    auto zeroed = [&h](auto& buf, size_t count) -> int {
+        PRG_HIP(buf.reset((int64_t)count));
+        PRG_HIP(hipMemsetAsync(buf.p, 0, count * sizeof(*buf.p), h->stream));
+        return PRG_OK;
+    };
+    PRG_TRY(put(h->src4, s4.data(), s4.size()));
+    PRG_TRY(put(h->tgt4, t4.data(), t4.size()));
+    PRG_TRY(put(h->soff, source_offsets, (size_t)nb + 1));
+    PRG_TRY(put(h->toff, target_offsets, (size_t)nb + 1));
+    PRG_TRY(put(h->tiles, tiles.data(), tiles.size()));
+    PRG_TRY(put(h->tile_first, first.data(), first.size()));
+    PRG_TRY(zeroed(h->params, (size_t)nb * PRG_NPARAMS));
+    PRG_TRY(zeroed(h->part, (size_t)nt * kBatchComp));
+    PRG_TRY(zeroed(h->init, (size_t)nb * 16));
+    PRG_TRY(zeroed(h->wtol, (size_t)nb * 2));
+    PRG_TRY(zeroed(h->flags, (size_t)nb * 2 + 1));
+    PRG_HIP(h->pinned.ensure((int64_t)nb * 2 + 8));
+    PRG_HIP(hipStreamSynchronize(h->stream));  // (the uploads read this call's own host vectors)
+    *out = h.release();
     return PRG_OK;
 }
 
@@ -487,7 +468,7 @@ int prg_cpd_batch_destroy(prg_cpd_batch* h) {
     if (!h) return PRG_OK;
     prg::DeviceGuard g(h->device);
     (void)hipStreamSynchronize(h->stream);
-    free_batch(h);
+    delete h;
     return PRG_OK;
 }
 
@@ -495,9 +476,9 @@ int prg_cpd_batch_init(prg_cpd_batch* h, const double* init_params_host) {
     PRG_REQUIRE(h, PRG_ERR_INVALID, "prg_cpd_batch_init: NULL handle");
     prg::DeviceGuard g(h->device);
     if (init_params_host)
-        PRG_HIP(hipMemcpyAsync(h->init, init_params_host, (size_t)h->B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    k_batch_init<<<h->B, 256, 0, h->stream>>>(h->src4, h->tgt4, h->soff, h->toff, init_params_host ? h->init : nullptr, h->params,
-                                              h->flags, h->B, h->dim);
+        PRG_HIP(hipMemcpyAsync(h->init.p, init_params_host, (size_t)h->B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    k_batch_init<<<h->B, 256, 0, h->stream>>>(h->src4.p, h->tgt4.p, h->soff.p, h->toff.p, init_params_host ? h->init.p : nullptr, h->params.p,
+                                              h->flags.p, h->B, h->dim);
     PRG_HIP(hipGetLastError());
     if (init_params_host) PRG_HIP(hipStreamSynchronize(h->stream));  // the caller may reuse its buffer
     h->initialised = true;
@@ -505,8 +486,8 @@ int prg_cpd_batch_init(prg_cpd_batch* h, const double* init_params_host) {
 }
 
 static int read_active(prg_cpd_batch* h, int* active) {
-    int* slot = reinterpret_cast<int*>(static_cast<double*>(h->pinned) + (size_t)h->B * 2);
-    PRG_HIP(hipMemcpyAsync(slot, h->flags + 2 * h->B, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    int* slot = reinterpret_cast<int*>(h->pinned.p + (size_t)h->B * 2);
+    PRG_HIP(hipMemcpyAsync(slot, h->flags.p + 2 * h->B, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     *active = *slot;
     return PRG_OK;
@@ -530,8 +511,8 @@ int prg_cpd_batch_iterate(prg_cpd_batch* h, int kind, int update_scale, const do
     now.insert(now.end(), tol, tol + h->B);
     if (now != h->wtol_host) {
         PRG_HIP(hipStreamSynchronize(h->stream));
-        memcpy(h->pinned, now.data(), now.size() * sizeof(double));
-        PRG_HIP(hipMemcpyAsync(h->wtol, h->pinned, now.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        memcpy(h->pinned.p, now.data(), now.size() * sizeof(double));
+        PRG_HIP(hipMemcpyAsync(h->wtol.p, h->pinned.p, now.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         h->wtol_host.swap(now);
     }
     for (int it = 0; it < n_iter; ++it) {
@@ -541,12 +522,12 @@ int prg_cpd_batch_iterate(prg_cpd_batch* h, int kind, int update_scale, const do
             if (active == 0) break;
         }
         if (kind == PRG_TF_AFFINE)
-            k_batch_sweep<true><<<h->ntiles, kBatchTile, 0, h->stream>>>(h->tiles, h->src4, h->tgt4, h->soff, h->toff, h->params,
-                                                                        h->flags, h->wtol, h->part, h->dim);
+            k_batch_sweep<true><<<h->ntiles, kBatchTile, 0, h->stream>>>(h->tiles.p, h->src4.p, h->tgt4.p, h->soff.p, h->toff.p, h->params.p,
+                                                                        h->flags.p, h->wtol.p, h->part.p, h->dim);
         else
-            k_batch_sweep<false><<<h->ntiles, kBatchTile, 0, h->stream>>>(h->tiles, h->src4, h->tgt4, h->soff, h->toff, h->params,
-                                                                         h->flags, h->wtol, h->part, h->dim);
-        k_batch_mstep<<<h->B, 64, 0, h->stream>>>(h->part, h->tile_first, h->params, h->flags, h->wtol + h->B, h->B, kind,
+            k_batch_sweep<false><<<h->ntiles, kBatchTile, 0, h->stream>>>(h->tiles.p, h->src4.p, h->tgt4.p, h->soff.p, h->toff.p, h->params.p,
+                                                                         h->flags.p, h->wtol.p, h->part.p, h->dim);
+        k_batch_mstep<<<h->B, 64, 0, h->stream>>>(h->part.p, h->tile_first.p, h->params.p, h->flags.p, h->wtol.p + h->B, h->B, kind,
                                                   update_scale, h->dim);
     }
     PRG_HIP(hipGetLastError());
@@ -564,9 +545,9 @@ int prg_cpd_batch_get_params(prg_cpd_batch* h, double* params_host, int* n_iter_
     PRG_REQUIRE(h && params_host, PRG_ERR_INVALID, "prg_cpd_batch_get_params: NULL argument");
     PRG_REQUIRE(h->initialised, PRG_ERR_STATE, "prg_cpd_batch_get_params: prg_cpd_batch_init has not run");
     prg::DeviceGuard g(h->device);
-    PRG_HIP(hipMemcpyAsync(params_host, h->params, (size_t)h->B * PRG_NPARAMS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipMemcpyAsync(params_host, h->params.p, (size_t)h->B * PRG_NPARAMS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (n_iter_host)
-        PRG_HIP(hipMemcpyAsync(n_iter_host, h->flags + h->B, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(n_iter_host, h->flags.p + h->B, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }

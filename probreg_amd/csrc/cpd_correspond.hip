@@ -205,20 +205,6 @@ int run_topk(hipStream_t st, const float4* own4, int64_t n_o, const float4* str4
     return PRG_OK;
 }
 
-// The plan's correspondence workspace: one block that grows and is never shrunk (freed with the plan, cpd.hip), so that a call
-// on a plan allocates nothing once it has run at its largest k: hipFree drains the device and a fresh 16 MB allocation costs
-// more than the sweep.
-int ensure_corr_workspace(prg_cpd* h, size_t bytes) {
-    if (h->corr_bytes >= bytes) return PRG_OK;
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    if (h->corr_buf) (void)hipFree(h->corr_buf);
-    h->corr_buf = nullptr;
-    h->corr_bytes = 0;
-    PRG_HIP(hipMalloc(&h->corr_buf, bytes));
-    h->corr_bytes = bytes;
-    return PRG_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -307,8 +293,11 @@ int prg_cpd_correspond(prg_cpd* h, int side, int k, int* index_out, float* log2_
                              (size_t)cut.part_elems * sizeof(int), (size_t)n_o * k * sizeof(double)};
     size_t off[8] = {0};
     for (int i = 0; i < 7; ++i) off[i + 1] = off[i] + (size_t)prg::round_up((int64_t)sizes[i], 256);
-    PRG_TRY(ensure_corr_workspace(h, off[7]));
-    char* const base = static_cast<char*>(h->corr_buf);
+    // ... one block that grows and is never shrunk, so that a call on a plan allocates nothing once it has run at its largest k:
+    // a free drains the device and a fresh 16 MB allocation costs more than the sweep
+    if (h->corr_buf.cap < (int64_t)off[7]) PRG_HIP(hipStreamSynchronize(st));
+    PRG_HIP(h->corr_buf.ensure((int64_t)off[7], (int64_t)off[7]));
+    char* const base = h->corr_buf.p;
     float4* const z4 = reinterpret_cast<float4*>(base + off[0]);
     float4* const x4 = reinterpret_cast<float4*>(base + off[1]);
     int* const bi = reinterpret_cast<int*>(base + off[2]);
@@ -316,13 +305,13 @@ int prg_cpd_correspond(prg_cpd* h, int side, int k, int* index_out, float* log2_
     float* const ps = reinterpret_cast<float*>(base + off[4]);
     int* const pi = reinterpret_cast<int*>(base + off[5]);
     double* const bp = reinterpret_cast<double*>(base + off[6]);
-    k_corr_pack_plan<true><<<(unsigned)prg::ceil_div(h->M, kOwned), kOwned, 0, st>>>(h->z4, h->M, -kappa, 0.f, z4);
-    k_corr_pack_plan<false><<<(unsigned)prg::ceil_div(h->N, kOwned), kOwned, 0, st>>>(h->tgt4, h->N, 0.f, dead_bias, x4);
+    k_corr_pack_plan<true><<<(unsigned)prg::ceil_div(h->M, kOwned), kOwned, 0, st>>>(h->z4.p, h->M, -kappa, 0.f, z4);
+    k_corr_pack_plan<false><<<(unsigned)prg::ceil_div(h->N, kOwned), kOwned, 0, st>>>(h->tgt4.p, h->N, 0.f, dead_bias, x4);
     PRG_HIP(hipGetLastError());
     const float4* const own4 = side == 0 ? z4 : x4;
     const float4* const str4 = side == 0 ? x4 : z4;
-    PRG_TRY(run_topk(st, own4, n_o, str4, n_s, kappa, k, cut, side == 0 ? h->perm_src : h->perm_tgt,
-                     side == 0 ? h->perm_tgt : h->perm_src, ps, pi, bi, bs, prob_out ? bp : nullptr));
+    PRG_TRY(run_topk(st, own4, n_o, str4, n_s, kappa, k, cut, side == 0 ? h->perm_src.p : h->perm_tgt.p,
+                     side == 0 ? h->perm_tgt.p : h->perm_src.p, ps, pi, bi, bs, prob_out ? bp : nullptr));
     PRG_HIP(hipMemcpyAsync(index_out, bi, (size_t)n_o * k * sizeof(int), hipMemcpyDeviceToHost, st));
     if (log2_prob_out) PRG_HIP(hipMemcpyAsync(log2_prob_out, bs, (size_t)n_o * k * sizeof(float), hipMemcpyDeviceToHost, st));
     if (prob_out) PRG_HIP(hipMemcpyAsync(prob_out, bp, (size_t)n_o * k * sizeof(double), hipMemcpyDeviceToHost, st));

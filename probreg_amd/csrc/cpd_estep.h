@@ -41,6 +41,9 @@ int ensure_engine_state(prg_cpd* h);  // (cpd.hip)
 inline int mom_blocks(const prg_cpd& h) { return (int)ceil_div(std::max(h.M, h.N), kBlock); }
 inline int64_t mompart_elems(const prg_cpd& h) { return (int64_t)mom_blocks(h) * (kMomComp + 2) + 64; }
 int ensure_mompart(prg_cpd* h);
+// ... of the ALLOCATION (mompart grows and never shrinks: the end of the block a larger cloud pair left is the one place every
+// reader and writer agrees on)
+inline double* mom_scratch(const prg_cpd& h) { return h.mompart.p + (h.mompart.cap - 64); }
 // out[off + c] = sum_b part[b][ncomp] (k_reduce_partials, one workgroup), on the plan's stream
 void reduce_partials(prg_cpd* h, const double* part, int nblk, int ncomp, double* out, int off);
 

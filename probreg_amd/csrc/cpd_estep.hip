@@ -815,23 +815,12 @@ __global__ __launch_bounds__(kBlock) void k_xpx_columns(const double* __restrict
 
 static QueueView queue_view(const SweepQueue& q, bool active) {
     QueueView v;
-    v.chunk = active ? q.chunk : nullptr;
+    v.chunk = active ? q.chunk.p : nullptr;
     v.nchunk = q.nchunk;
-    v.ctrl = q.ctrl;
+    v.ctrl = q.ctrl.p;
     v.pop_start = prg::kQueueWorkgroups * (prg::kSweepBlock / 64);
     v.cap_soft = q.cap_soft;
     return v;
-}
-
-template <typename T>
-int ensure_buffer(T** p, int64_t* have, int64_t need) {
-    if (*p && *have >= need) return PRG_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    PRG_HIP(hipMalloc((void**)p, (size_t)need * sizeof(T)));
-    *have = need;
-    return PRG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -962,7 +951,11 @@ double engine_row_bound(int64_t m, int64_t n_local, bool lean) {
     return lean ? engine_leave_below(m, n_local, 14.5e-6, -20.0e-6, 0.250e-12) : engine_leave_below(m, n_local, 19.2e-6, 8.0e-6, 0.233e-12);
 }
 
-int ensure_mompart(prg_cpd* h) { return ensure_buffer(&h->mompart, &h->mompart_elems, mompart_elems(*h)); }
+int ensure_mompart(prg_cpd* h) {
+    const int64_t need = mompart_elems(*h);
+    PRG_HIP(h->mompart.ensure(need, need));
+    return PRG_OK;
+}
 
 void reduce_partials(prg_cpd* h, const double* part, int nblk, int ncomp, double* out, int off) {
     k_reduce_partials<<<1, kRedBlock, 0, h->stream>>>(part, nblk, ncomp, out, off);
@@ -976,7 +969,7 @@ int estep_layout(const prg_cpd& h, EstepLayout* out) {
     L.RA = L.ra < 0 ? -L.ra : L.ra;
     L.RB = L.rb < 0 ? -L.rb : L.rb;
     // Culled sweeps need both clouds Morton-sorted (compact waves / groups); they walk the stream in groups of 32.
-    L.use_cull = h.opt_cull && h.perm_src && h.perm_tgt && h.r_col == 0 && h.r_row == 0;  // (segment counts stay tunable)
+    L.use_cull = h.opt_cull && h.perm_src.p && h.perm_tgt.p && h.r_col == 0 && h.r_row == 0;  // (segment counts stay tunable)
     // segment lengths are multiples of the loop trip (8 points, or 256 points = 8 groups); the pads absorb the
     // overshoot and the prefetch over-read of the last segment
     const int quantum = L.use_cull ? kSuper : 8;
@@ -1005,7 +998,7 @@ int estep_layout(const prg_cpd& h, EstepLayout* out) {
     // matrix-core sweeps (dense regime, decided per E-step): segments of whole 512-point chunks, one plane each
     // ... for clouds large enough that the sweeps are worth it: below ~8k points an E-step is launch bound whatever the
     // engine, and a 512-point patch of a small cloud spans most of it (the patch-local origin buys no precision)
-    L.mfma_possible = L.use_cull && h.dense_engine > 0 && !h.srcw && (h.dense_engine >= 2 || (h.M >= 8192 && h.N >= 8192));
+    L.mfma_possible = L.use_cull && h.dense_engine > 0 && !h.srcw.p && (h.dense_engine >= 2 || (h.M >= 8192 && h.N >= 8192));
     // ... cut to fill the chip once (PRG_MFMA_SEG = 0) and, once the previous sweep skipped a tenth of its pairs, in >= 3 rounds
     // of shorter segments (mfma_fine_segments)
     L.seg_col_fine = L.mfma_possible ? mfma_fine_segments(h.N, h.M, 256) : 0;
@@ -1025,7 +1018,7 @@ int estep_layout(const prg_cpd& h, EstepLayout* out) {
     L.allow_fused = L.mfma_possible && single_ok;
     // the residual-form single sweep on the vector pipe: the same callers as the fused sweep, any sigma2, no
     // matrix cores needed
-    L.allow_resid = L.use_cull && h.resid_sweep && single_ok && !h.srcw;
+    L.allow_resid = L.use_cull && h.resid_sweep && single_ok && !h.srcw.p;
     // ... which the column block's owner runs ([r6] cpd_sweeps_owner.hip: the stream dealt out over PO parts x 8 waves per 128-column
     // block, cells found through the chunk / group hierarchy; prg_cpd_set_sparse_engine(0 / 2 / 3): round 5's grid / queue instead)
     L.use_owner = L.allow_resid && h.sparse_engine == 1 && !env.owner_off;
@@ -1059,19 +1052,13 @@ namespace {
 // the driver's steps
 // ---------------------------------------------------------------------------------------------
 int ensure_estep_buffers(prg_cpd* h, const EstepLayout& L) {
-    PRG_TRY(ensure_buffer(&h->colpart, &h->colpart_elems, L.colpart_elems));
-    PRG_TRY(ensure_buffer(&h->rowpart, &h->rowpart_elems, L.rowpart_elems));
-    PRG_TRY(ensure_buffer(&h->mompart, &h->mompart_elems, L.mompart_elems));
+    PRG_HIP(h->colpart.ensure(L.colpart_elems, L.colpart_elems));
+    PRG_HIP(h->rowpart.ensure(L.rowpart_elems, L.rowpart_elems));
+    PRG_HIP(h->mompart.ensure(L.mompart_elems, L.mompart_elems));
     if (L.use_queue) PRG_TRY(prg::prepare_queues(h));
-    if (L.wgcount_elems > h->wg_cap) {  // ([0, wg_cap) column pass, [wg_cap, 2 wg_cap) row pass)
-        if (h->wgcount) {
-            PRG_HIP(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->wgcount);
-        }
-        h->wgcount = nullptr;
-        h->wg_cap = 0;
-        PRG_HIP(hipMalloc((void**)&h->wgcount, (size_t)L.wgcount_elems * 2 * sizeof(unsigned)));
-        h->wg_cap = L.wgcount_elems;
+    if (L.wgcount_elems > h->wg_cap()) {  // ([0, wg_cap) column pass, [wg_cap, 2 wg_cap) row pass)
+        if (h->wgcount.p) PRG_HIP(hipStreamSynchronize(h->stream));
+        PRG_HIP(h->wgcount.reset(2 * L.wgcount_elems));
     }
     return PRG_OK;
 }
@@ -1079,10 +1066,10 @@ int ensure_estep_buffers(prg_cpd* h, const EstepLayout& L) {
 // one fused kernel: transform, source motion, group boxes of the transformed cloud.  Non-rigid: z = y + G W with the
 // parameter block's identity linear part (the fp64 sum is rounded once, transformation.py:101-102)
 int transform_source(prg_cpd* h, int slot) {
-    const double* disp = h->bcpd ? h->W : nullptr;
+    const double* disp = h->bcpd ? h->W.p : nullptr;
     if (h->nonrigid) PRG_TRY(prg::nonrigid_displacement(h, &disp));
     k_transform_linear<<<(unsigned)prg::ceil_div(h->M, kBlock), kBlock, 0, h->stream>>>(
-        h->src4, h->z4, h->M, h->params, h->motion, slot, h->zmeta, h->srcw, disp, h->zchunk);  // pad-only blocks are static
+        h->src4.p, h->z4.p, h->M, h->params, h->motion.p, slot, h->zmeta.p, h->srcw.p, disp, h->zchunk.p);  // pad-only blocks are static
     return PRG_OK;
 }
 
@@ -1126,7 +1113,7 @@ void fill_engine_args(prg_cpd* h, const EstepLayout& L, int slot, EngineArgs* ou
     ea.have_colmin = h->have_colmin ? 1 : 0;
     ea.forced = h->dense_engine >= 2 ? 1 : 0;
     ea.seq = (unsigned)h->estep_count;  // (already incremented: never 0, the mailbox's initial value)
-    ea.dev = h->eng_dev;
+    ea.dev = &h->eng_dev.p->decision;
     ea.host = h->eng_host_dev;
     *out = ea;
 }
@@ -1158,16 +1145,16 @@ int decide_engines(prg_cpd* h, const EstepLayout& L, int slot, bool cull_seed, h
     const bool pred = h->eng.pred_col != 0, pred_fused = L.allow_fused && h->eng.pred_fused != 0;
     const bool vector_grid = !L.use_queue && !L.use_owner;  // the vector pipe's column pass would be the grid of culled waves
     if (pred_fused)  // (the single sweep of a rigid iteration, if the previous E-step ran it)
-        prg::launch_fused_mfma(h, seg_col(), !h->have_colmin, false, h->eng_dev);
+        prg::launch_fused_mfma(h, seg_col(), !h->have_colmin, false, ea.dev);
     else if (pred)  // (stream mode if the previous decision found nothing to skip: the dense regime)
-        prg::launch_colpass_mfma(h, seg_col(), !h->have_colmin, false, h->eng_dev, h->mfma_stream && h->eng.pred_fine == 0 && !h->eng.grid_fine);
+        prg::launch_colpass_mfma(h, seg_col(), !h->have_colmin, false, ea.dev, h->mfma_stream && h->eng.pred_fine == 0 && !h->eng.grid_fine);
     else if (vector_grid)
-        prg::launch_colpass_cull(h, L.SA, L.segA, cull_seed, h->eng_dev, L.allow_resid);
+        prg::launch_colpass_cull(h, L.SA, L.segA, cull_seed, ea.dev, L.allow_resid);
     // (pred == vector pipe with the work queue / the owner sweep: nothing goes out ahead - inside the dense regime that engine only
     // runs when the bracket of the column minima is too wide for the matrix-core offsets, a handful of E-steps at most)
     PRG_HIP(hipGetLastError());
     // the answer: a few microseconds after the transform has finished, long before the column pass has
-    volatile EngineDecision* mb = h->eng_host;
+    volatile EngineDecision* mb = h->eng_host.p;
     hipError_t werr;
     const bool got = prg::wait_mailbox(&mb->seq, ea.seq, h->stream, &werr);
     PRG_HIP(werr);
@@ -1200,10 +1187,10 @@ int decide_engines(prg_cpd* h, const EstepLayout& L, int slot, bool cull_seed, h
     h->eng.pred_fine = d.fine ? 1 : 0;
     h->eng.pred_fused = d.fused ? 1 : 0;
     if (!d.col_launched && d.fused) {  // (the guarded launch has returned at once; rare: the engine changes a few times per registration)
-        prg::launch_fused_mfma(h, seg_col(), d.first, d.fine, h->eng_dev);
+        prg::launch_fused_mfma(h, seg_col(), d.first, d.fine, ea.dev);
         d.col_launched = true;
     } else if (!d.col_launched && d.use_mfma) {
-        prg::launch_colpass_mfma(h, seg_col(), d.first, d.fine, h->eng_dev, h->mfma_stream && !d.fine && !h->eng.grid_fine);
+        prg::launch_colpass_mfma(h, seg_col(), d.first, d.fine, ea.dev, h->mfma_stream && !d.fine && !h->eng.grid_fine);
         d.col_launched = true;
     }
     *out = d;
@@ -1240,7 +1227,7 @@ int finish_estep(prg_cpd* h, double w, bool col_queue, bool row_queue, bool rowa
     if (h->comm) {
         // (the E-step's 24 sums only: [24..27] hold the target sums prg_cpd_init_sums has already made global)
         PRG_TRY(prg::comm_all_reduce_f64(h->comm, h->moments, kMomComp, h->stream));
-        if (h->nonrigid && rowacc_valid) PRG_TRY(prg::comm_all_reduce_f64(h->comm, h->rowacc, 4 * h->Mcap, h->stream));
+        if (h->nonrigid && rowacc_valid) PRG_TRY(prg::comm_all_reduce_f64(h->comm, h->rowacc.p, 4 * h->Mcap, h->stream));
     }
     h->qcol_live = col_queue;
     h->qrow_live = row_queue;
@@ -1257,28 +1244,28 @@ int finish_estep(prg_cpd* h, double w, bool col_queue, bool row_queue, bool rowa
 int single_sweep_tail(prg_cpd* h, const EstepLayout& L, const EstepEngines& d, const ColumnPass& cp, bool resid, double w, int slot,
                       hipEvent_t* ev) {
     const int nblk = (int)prg::ceil_div(h->N, kBlock);
-    float* const colmin_g = h->colmin + h->Ncap;
-    const float* part = reinterpret_cast<const float*>(h->colpart);
+    float* const colmin_g = h->colmin.p + h->Ncap;
+    const float* part = reinterpret_cast<const float*>(h->colpart.p);
     if (!resid) {  // fused: per-column (A, B, E) relative to the block origins
-        k_colfinal_fused<<<nblk, kBlock, 0, h->stream>>>(h->tgt4, part, h->mfma_col_planes, h->Ncap, h->N, h->pt1, h->params, w, m_over_n(h),
-                                                         h->D, h->colmin, colmin_g, h->tmeta, d.first ? 2 : 1, h->motion, slot, h->corig,
-                                                         h->mompart);
+        k_colfinal_fused<<<nblk, kBlock, 0, h->stream>>>(h->tgt4.p, part, h->mfma_col_planes, h->Ncap, h->N, h->pt1.p, h->params, w, m_over_n(h),
+                                                         h->D, h->colmin.p, colmin_g, h->tmeta.p, d.first ? 2 : 1, h->motion.p, slot, h->corig.p,
+                                                         h->mompart.p);
     } else if (cp.queue) {  // per-column (A, U, R), residuals against the column's own x_n: in the slots of the queue's units
-        k_colfinal_resid<true><<<nblk, kBlock, 0, h->stream>>>(h->tgt4, part, 0, h->Ncap, h->N, h->pt1, h->params, w, m_over_n(h), h->D,
-                                                               h->colmin, colmin_g, h->tmeta, h->motion, slot, nullptr,
-                                                               queue_view(h->qcol, true), h->mompart, 7);
+        k_colfinal_resid<true><<<nblk, kBlock, 0, h->stream>>>(h->tgt4.p, part, 0, h->Ncap, h->N, h->pt1.p, h->params, w, m_over_n(h), h->D,
+                                                               h->colmin.p, colmin_g, h->tmeta.p, h->motion.p, slot, nullptr,
+                                                               queue_view(h->qcol, true), h->mompart.p, 7);
     } else {  // ... in planes with their touched flags; a flag stands for 128 columns, or for 64 when the owner sweep ran one per lane
         const int planes = cp.owner ? L.PO : L.PA;
-        k_colfinal_resid<false><<<nblk, kBlock, 0, h->stream>>>(h->tgt4, part, planes, h->Ncap, h->N, h->pt1, h->params, w, m_over_n(h), h->D,
-                                                                h->colmin, colmin_g, h->tmeta, h->motion, slot, prg::resid_flags(h, planes),
-                                                                queue_view(h->qcol, false), h->mompart,
+        k_colfinal_resid<false><<<nblk, kBlock, 0, h->stream>>>(h->tgt4.p, part, planes, h->Ncap, h->N, h->pt1.p, h->params, w, m_over_n(h), h->D,
+                                                                h->colmin.p, colmin_g, h->tmeta.p, h->motion.p, slot, prg::resid_flags(h, planes),
+                                                                queue_view(h->qcol, false), h->mompart.p,
                                                                 cp.owner && prg::owner_cols_per_lane() == 1 ? 6 : 7);
     }
     if (ev) {
         PRG_HIP(hipEventRecord(ev[3], h->stream));
         PRG_HIP(hipEventRecord(ev[4], h->stream));
     }
-    k_fused_final<<<1, kRedBlock, 0, h->stream>>>(h->mompart, nblk, h->params, h->moments);
+    k_fused_final<<<1, kRedBlock, 0, h->stream>>>(h->mompart.p, nblk, h->params, h->moments);
     if (ev) PRG_HIP(hipEventRecord(ev[5], h->stream));
     h->wg_row = 0;
     h->dense_pairs_row = 0.0;
@@ -1288,10 +1275,10 @@ int single_sweep_tail(prg_cpd* h, const EstepLayout& L, const EstepEngines& d, c
 int two_sweep_tail(prg_cpd* h, const EstepLayout& L, const EstepEngines& d, const ColumnPass& cp, double w, int slot, hipEvent_t* ev) {
     const int mfma_seg = prg::cpd_env().mfma_seg;
     // (lean matrix-core row pass: no residual sums - sum pt1 |x|^2 goes from k_colfinal's partials to k_xpx_columns)
-    double* xpart = h->mompart + (int64_t)prg::mom_blocks(*h) * kMomComp;
-    k_colfinal<<<grid1(h->N), kBlock, 0, h->stream>>>(h->tgt4, h->colpart, d.use_mfma ? h->mfma_col_planes : L.PA, h->Ncap, h->N, h->pt1, h->params, w,
-                                                      m_over_n(h), h->D, h->colmin, h->colmin + h->Ncap,
-                                                      L.use_cull ? h->tmeta : nullptr, d.use_mfma ? (d.first ? 2 : 1) : 0, h->motion, slot,
+    double* xpart = h->mompart.p + (int64_t)prg::mom_blocks(*h) * kMomComp;
+    k_colfinal<<<grid1(h->N), kBlock, 0, h->stream>>>(h->tgt4.p, h->colpart.p, d.use_mfma ? h->mfma_col_planes : L.PA, h->Ncap, h->N, h->pt1.p, h->params, w,
+                                                      m_over_n(h), h->D, h->colmin.p, h->colmin.p + h->Ncap,
+                                                      L.use_cull ? h->tmeta.p : nullptr, d.use_mfma ? (d.first ? 2 : 1) : 0, h->motion.p, slot,
                                                       queue_view(h->qcol, cp.queue), d.row_lean ? xpart : nullptr);
     if (ev) PRG_HIP(hipEventRecord(ev[3], h->stream));
     const bool row_queue = !d.row_mfma && L.use_queue;
@@ -1308,15 +1295,15 @@ int two_sweep_tail(prg_cpd* h, const EstepLayout& L, const EstepEngines& d, cons
     if (ev) PRG_HIP(hipEventRecord(ev[4], h->stream));
     const int nblk = (int)std::min<int64_t>(prg::ceil_div(h->M, kBlock), 1024);
     const int row_planes = d.row_mfma ? h->mfma_row_planes : L.PB;
-    k_row_moments<<<nblk, kBlock, 0, h->stream>>>(h->rowpart, row_planes, h->Mcap, h->M, h->src4, h->z4, h->rowacc,
-                                                  h->mompart,
-                                                  L.use_cull ? reinterpret_cast<const unsigned char*>(h->rowpart + (int64_t)row_planes * 5 * h->Mcap)
+    k_row_moments<<<nblk, kBlock, 0, h->stream>>>(h->rowpart.p, row_planes, h->Mcap, h->M, h->src4.p, h->z4.p, h->rowacc.p,
+                                                  h->mompart.p,
+                                                  L.use_cull ? reinterpret_cast<const unsigned char*>(h->rowpart.p + (int64_t)row_planes * 5 * h->Mcap)
                                                              : nullptr,
-                                                  d.row_mfma ? h->rorig : nullptr, queue_view(h->qrow, row_queue), d.row_lean ? 1 : 0);
+                                                  d.row_mfma ? h->rorig.p : nullptr, queue_view(h->qrow, row_queue), d.row_lean ? 1 : 0);
     // (folding this single-block reduction into the last-finishing workgroup of k_row_moments was measured in round 3:
     // +25 us - that workgroup's 256 threads read the ~400 partial rows through L2 in a few dependent rounds, the 1024
     // threads of this launch do it in 5 us including the launch)
-    k_reduce_partials<<<1, kRedBlock, 0, h->stream>>>(h->mompart, nblk, kMomComp, h->moments, 0);
+    k_reduce_partials<<<1, kRedBlock, 0, h->stream>>>(h->mompart.p, nblk, kMomComp, h->moments, 0);
     if (d.row_lean) k_xpx_columns<<<1, kBlock, 0, h->stream>>>(xpart, (int)prg::ceil_div(h->N, kBlock), h->moments);
     if (ev) PRG_HIP(hipEventRecord(ev[5], h->stream));
     return finish_estep(h, w, cp.queue, row_queue, true);
@@ -1337,7 +1324,7 @@ int prg::estep_impl(prg_cpd* h, double w, hipEvent_t* ev) {
     const int slot = (int)(h->estep_count & 1);
     ++h->estep_count;
     PRG_TRY(transform_source(h, slot));
-    const bool cull_seed = h->have_colmin && !h->srcw;  // the seed bound assumes unweighted distances
+    const bool cull_seed = h->have_colmin && !h->srcw.p;  // the seed bound assumes unweighted distances
     h->wg_col_pairs = h->wg_row_pairs = 128.0 * prg::kGroup;  // a (wave, group) block of the culled vector-pipe sweeps
     EstepEngines d;
     PRG_TRY(decide_engines(h, L, slot, cull_seed, ev, &d));

@@ -303,35 +303,35 @@ namespace prg {
 // workspace layout inside h->nr_work (doubles): [0, 3M) GW / scratch
 // displacement field G W of the current W -> nr_work[0, 3M); the E-step's transform kernel adds it to the source
 int nonrigid_displacement(prg_cpd* h, const double** gw_out) {
-    PRG_REQUIRE((h->G || h->F) && h->W, PRG_ERR_STATE, "non-rigid transform: G has not been built");
+    PRG_REQUIRE((h->G.p || h->F.p) && h->W.p, PRG_ERR_STATE, "non-rigid transform: G has not been built");
     if (!h->gw_valid) {
-        PRG_TRY(nonrigid_gw(h, h->W, h->nr_work));
+        PRG_TRY(nonrigid_gw(h, h->W.p, h->nr_work.p));
         h->gw_valid = true;
     }
-    *gw_out = h->nr_work;
+    *gw_out = h->nr_work.p;
     return PRG_OK;
 }
 
 int lowrank_ft3(prg_cpd* h, const double* x3, double* out) {
-    k_lr_ft3<<<(unsigned)h->f_rank, kBlock, 0, h->stream>>>(h->F, h->f_ld, h->M, x3, out);
+    k_lr_ft3<<<(unsigned)h->f_rank, kBlock, 0, h->stream>>>(h->F.p, h->f_ld, h->M, x3, out);
     PRG_HIP(hipGetLastError());
     return PRG_OK;
 }
 
 int lowrank_apply(prg_cpd* h, const double* v, double* out3) {
-    k_lr_apply<<<grid1(h->M), kBlock, 0, h->stream>>>(h->F, h->f_ld, h->M, h->f_rank, v, out3);
+    k_lr_apply<<<grid1(h->M), kBlock, 0, h->stream>>>(h->F.p, h->f_ld, h->M, h->f_rank, v, out3);
     PRG_HIP(hipGetLastError());
     return PRG_OK;
 }
 
 int nonrigid_gw(prg_cpd* h, const double* w3, double* out3) {
-    PRG_REQUIRE(h->G || h->F, PRG_ERR_STATE, "non-rigid: G has not been built");
-    if (h->F) {  // G w = F (F^T w)
-        double* v = h->nr_work + (size_t)h->M * 3;  // [rank][3] behind the GW block of the workspace
+    PRG_REQUIRE(h->G.p || h->F.p, PRG_ERR_STATE, "non-rigid: G has not been built");
+    if (h->F.p) {  // G w = F (F^T w)
+        double* v = h->nr_work.p + (size_t)h->M * 3;  // [rank][3] behind the GW block of the workspace
         PRG_TRY(lowrank_ft3(h, w3, v));
         return lowrank_apply(h, v, out3);
     }
-    k_gw<<<(unsigned)prg::ceil_div(h->M, kGwRows), kBlock, 0, h->stream>>>(h->G, h->M, w3, out3);
+    k_gw<<<(unsigned)prg::ceil_div(h->M, kGwRows), kBlock, 0, h->stream>>>(h->G.p, h->M, w3, out3);
     PRG_HIP(hipGetLastError());
     return PRG_OK;
 }
@@ -350,24 +350,16 @@ static int build_lowrank_factor(prg_cpd* h, int kind, double param, int max_rank
     const int64_t m = h->M, mp = round_up(m, kBlock), ld = mp + 32;
     const int nblk = (int)(mp / kBlock);
     int cap = std::min(max_rank, 256);
-    double* f = nullptr;
-    double* work = nullptr;  // d [ld] | part [2][nblk] double2 | state | piv [kMaxRank]
-    const size_t work_bytes = (size_t)ld * 8 + (size_t)nblk * 2 * 16 + 64 + (size_t)kMaxRank * 4;
-    PRG_HIP(hipMalloc((void**)&f, (size_t)cap * ld * sizeof(double)));
-    if (hipMalloc((void**)&work, work_bytes) != hipSuccess) {
-        (void)hipFree(f);
-        PRG_REQUIRE(false, PRG_ERR_HIP, "non-rigid: out of device memory for the kernel factor");
-    }
-    double* d = work;
-    double2* part = reinterpret_cast<double2*>(work + ld);
+    prg::DevBuf<double> fbuf;  // the factor while it grows: freed on every way out but the last, which hands it to the plan
+    prg::DevBuf<char> work;    // d [ld] | part [2][nblk] double2 | state | piv [kMaxRank]
+    PRG_HIP(fbuf.reset(cap * ld));
+    PRG_REQUIRE(work.reset(ld * 8 + (int64_t)nblk * 2 * 16 + 64 + (int64_t)kMaxRank * 4) == hipSuccess, PRG_ERR_HIP,
+                "non-rigid: out of device memory for the kernel factor");
+    double* f = fbuf.p;
+    double* d = reinterpret_cast<double*>(work.p);
+    double2* part = reinterpret_cast<double2*>(d + ld);
     PcholState* state = reinterpret_cast<PcholState*>(part + 2 * (size_t)nblk);
     int* piv = reinterpret_cast<int*>(reinterpret_cast<char*>(state) + 64);
-    auto fail = [&](const char* what) {
-        (void)hipFree(f);
-        (void)hipFree(work);
-        prg::set_error("non-rigid kernel factor: %s", what);
-        return PRG_ERR_HIP;
-    };
     k_pchol_init<<<nblk, kBlock, 0, h->stream>>>(m, mp, g0, d, part, state);
     PcholState host = {0, 0, g0};
     int j = 0;
@@ -377,15 +369,13 @@ static int build_lowrank_factor(prg_cpd* h, int kind, double param, int max_rank
         if (j == cap) {  // grow the factor
             if (cap >= limit) break;  // not low rank enough
             const int ncap = std::min(limit, cap * 2);
-            double* nf = nullptr;
-            if (hipMalloc((void**)&nf, (size_t)ncap * ld * sizeof(double)) != hipSuccess) return fail("out of device memory");
-            if (hipMemcpyAsync(nf, f, (size_t)cap * ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-                hipStreamSynchronize(h->stream) != hipSuccess) {
-                (void)hipFree(nf);
-                return fail("copy failed");
-            }
-            (void)hipFree(f);
-            f = nf;
+            prg::DevBuf<double> nf;
+            PRG_REQUIRE(nf.reset(ncap * ld) == hipSuccess, PRG_ERR_HIP, "non-rigid kernel factor: out of device memory");
+            PRG_REQUIRE(hipMemcpyAsync(nf.p, f, (size_t)cap * ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+                            hipStreamSynchronize(h->stream) == hipSuccess,
+                        PRG_ERR_HIP, "non-rigid kernel factor: copy failed");
+            fbuf.swap(nf);  // (nf takes the old block away with it)
+            f = fbuf.p;
             cap = ncap;
         }
         const int batch = std::min(32, cap - j);
@@ -393,33 +383,29 @@ static int build_lowrank_factor(prg_cpd* h, int kind, double param, int max_rank
             const double2* pin = part + (size_t)(j & 1) * nblk;
             double2* pout = part + (size_t)((j + 1) & 1) * nblk;
             if (kind == 0)
-                k_pchol_step<0><<<nblk, kBlock, 0, h->stream>>>(h->src4, m, ld, kparam, f, d, pin, pout, nblk, j, tol, state, piv);
+                k_pchol_step<0><<<nblk, kBlock, 0, h->stream>>>(h->src4.p, m, ld, kparam, f, d, pin, pout, nblk, j, tol, state, piv);
             else
-                k_pchol_step<1><<<nblk, kBlock, 0, h->stream>>>(h->src4, m, ld, kparam, f, d, pin, pout, nblk, j, tol, state, piv);
+                k_pchol_step<1><<<nblk, kBlock, 0, h->stream>>>(h->src4.p, m, ld, kparam, f, d, pin, pout, nblk, j, tol, state, piv);
         }
-        if (hipMemcpyAsync(&host, state, sizeof(PcholState), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess)
-            return fail("device error");
+        PRG_REQUIRE(hipMemcpyAsync(&host, state, sizeof(PcholState), hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
+                        hipStreamSynchronize(h->stream) == hipSuccess && hipGetLastError() == hipSuccess,
+                    PRG_ERR_HIP, "non-rigid kernel factor: device error");
         if (host.done) break;  // a step of this batch found the remaining diagonal below tol
     }
     if (!host.done) {  // out of rank: converged only if the very last step reached the tolerance
         std::vector<double2> hp((size_t)nblk);
-        if (hipMemcpyAsync(hp.data(), part + (size_t)(j & 1) * nblk, (size_t)nblk * sizeof(double2), hipMemcpyDeviceToHost,
-                           h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess)
-            return fail("device error");
+        PRG_REQUIRE(hipMemcpyAsync(hp.data(), part + (size_t)(j & 1) * nblk, (size_t)nblk * sizeof(double2), hipMemcpyDeviceToHost,
+                                   h->stream) == hipSuccess &&
+                        hipStreamSynchronize(h->stream) == hipSuccess,
+                    PRG_ERR_HIP, "non-rigid kernel factor: device error");
         double mx = -1.0;
         for (const double2& q : hp) mx = std::max(mx, q.x);
         host.done = mx <= tol;
         if (reached_resid) *reached_resid = mx;
     }
     if (reached_rank) *reached_rank = host.rank;
-    (void)hipFree(work);
-    if (!host.done) {
-        (void)hipFree(f);
-        return PRG_OK;
-    }
-    h->F = f;
+    if (!host.done) return PRG_OK;
+    h->F.swap(fbuf);  // (h->F was empty: build_kernel_matrix starts from nonrigid_free)
     h->f_ld = ld;
     h->f_rank = host.rank;
     h->f_cap = cap;
@@ -430,10 +416,9 @@ static int build_lowrank_factor(prg_cpd* h, int kind, double param, int max_rank
 int build_kernel_matrix(prg_cpd* h, int kind, double param) {
     nonrigid_free(h);
     const int64_t m = h->M;
-    PRG_HIP(hipMalloc((void**)&h->W, (size_t)m * 3 * sizeof(double)));
-    h->nr_work_bytes = ((size_t)m * 16 + (size_t)kMaxRank * 3) * sizeof(double);
-    PRG_HIP(hipMalloc((void**)&h->nr_work, h->nr_work_bytes));
-    PRG_HIP(hipMemsetAsync(h->W, 0, (size_t)m * 3 * sizeof(double), h->stream));
+    PRG_HIP(h->W.reset(m * 3));
+    PRG_HIP(h->nr_work.reset(m * 16 + (int64_t)kMaxRank * 3));
+    PRG_HIP(hipMemsetAsync(h->W.p, 0, (size_t)m * 3 * sizeof(double), h->stream));
     if (kind == 0 && h->nr_solver == 1) {
         int max_rank = h->nr_max_rank > 0 ? h->nr_max_rank : (int)std::min<int64_t>(kMaxRank, m / 2);
         max_rank = std::min(max_rank, kMaxRank);
@@ -458,12 +443,12 @@ int build_kernel_matrix(prg_cpd* h, int kind, double param) {
                         reached, max_rank, resid, h->bcpd_tol);
         }
     }
-    PRG_HIP(hipMalloc((void**)&h->G, (size_t)m * m * sizeof(float)));
+    PRG_HIP(h->G.reset(m * m));
     dim3 grid((unsigned)prg::ceil_div(m, kBlock), (unsigned)prg::ceil_div(m, 16));
     if (kind == 0)
-        k_build_g<0><<<grid, kBlock, 0, h->stream>>>(h->src4, m, (float)(2.0 * param), h->G);
+        k_build_g<0><<<grid, kBlock, 0, h->stream>>>(h->src4.p, m, (float)(2.0 * param), h->G.p);
     else
-        k_build_g<1><<<grid, kBlock, 0, h->stream>>>(h->src4, m, (float)param, h->G);
+        k_build_g<1><<<grid, kBlock, 0, h->stream>>>(h->src4.p, m, (float)param, h->G.p);
     PRG_HIP(hipGetLastError());
     return PRG_OK;
 }
@@ -473,24 +458,16 @@ int nonrigid_free(prg_cpd* h) {
     h->nr_events.clear();
     if (h->nr_stream2) (void)hipStreamDestroy(h->nr_stream2);
     h->nr_stream2 = nullptr;
-    if (h->nr_prior) (void)hipFree(h->nr_prior);
-    h->nr_prior = nullptr;
+    h->nr_prior.release();
     h->nr_alpha = 0.0;
-    if (h->nr_solve) (void)hipFree(h->nr_solve);
-    h->nr_solve = nullptr;
-    h->nr_solve_bytes = 0;
+    h->nr_solve.release();
     h->nr_info = nullptr;  // the sticky pivot flag lives at the end of nr_solve: it goes with it
-    if (h->G) (void)hipFree(h->G);
-    if (h->F) (void)hipFree(h->F);
-    h->F = nullptr;
+    h->G.release();
+    h->F.release();
     h->f_rank = h->f_cap = 0;
     h->f_ld = 0;
-    if (h->W) (void)hipFree(h->W);
-    if (h->nr_work) (void)hipFree(h->nr_work);
-    h->G = nullptr;
-    h->W = nullptr;
-    h->nr_work = nullptr;
-    h->nr_work_bytes = 0;
+    h->W.release();
+    h->nr_work.release();
     h->nonrigid = false;
     h->bcpd = false;
     h->gw_valid = false;
@@ -522,8 +499,8 @@ int prg_cpd_nonrigid_set_solver(prg_cpd* h, int mode, int max_rank, double tol) 
 }
 
 int prg_cpd_nonrigid_rank(prg_cpd* h, int* rank) {
-    PRG_REQUIRE(h && rank && (h->G || h->F), PRG_ERR_STATE, "prg_cpd_nonrigid_rank: G has not been built");
-    *rank = h->F ? h->f_rank : 0;
+    PRG_REQUIRE(h && rank && (h->G.p || h->F.p), PRG_ERR_STATE, "prg_cpd_nonrigid_rank: G has not been built");
+    *rank = h->F.p ? h->f_rank : 0;
     return PRG_OK;
 }
 
@@ -548,40 +525,34 @@ int prg_cpd_bcpd_build_g(prg_cpd* h, double c) {
 }
 
 int prg_cpd_nonrigid_get_g(prg_cpd* h, float* g_hd) {
-    PRG_REQUIRE(h && (h->G || h->F) && !h->bcpd && g_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_get_g: G has not been built");
+    PRG_REQUIRE(h && (h->G.p || h->F.p) && !h->bcpd && g_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_get_g: G has not been built");
     prg::DeviceGuard g(h->device);
     const size_t bytes = (size_t)h->M * h->M * sizeof(float);
-    if (h->G && !h->perm_src) {
-        PRG_HIP(hipMemcpyAsync(g_hd, h->G, bytes, hipMemcpyDefault, h->stream));
+    if (h->G.p && !h->perm_src.p) {
+        PRG_HIP(hipMemcpyAsync(g_hd, h->G.p, bytes, hipMemcpyDefault, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
         return PRG_OK;
     }
     // the plan keeps the factor only, or the matrix of the SORTED source: evaluate the float32 matrix of the caller's
     // order on the spot (entry (i, j) depends on the two points alone, so this is the same matrix)
-    float* tmp = nullptr;
-    float4* pts = nullptr;
-    PRG_HIP(hipMalloc((void**)&tmp, bytes));
-    if (hipMalloc((void**)&pts, (size_t)h->M * sizeof(float4)) != hipSuccess) {
-        (void)hipFree(tmp);
-        PRG_REQUIRE(false, PRG_ERR_HIP, "prg_cpd_nonrigid_get_g: out of device memory");
-    }
-    k_unsort4<<<grid1(h->M), kBlock, 0, h->stream>>>(h->src4, h->M, h->perm_src, pts);
+    prg::DevBuf<float> tmp;
+    prg::DevBuf<float4> pts;
+    PRG_HIP(tmp.reset(h->M * h->M));
+    PRG_REQUIRE(pts.reset(h->M) == hipSuccess, PRG_ERR_HIP, "prg_cpd_nonrigid_get_g: out of device memory");
+    k_unsort4<<<grid1(h->M), kBlock, 0, h->stream>>>(h->src4.p, h->M, h->perm_src.p, pts.p);
     dim3 grid((unsigned)prg::ceil_div(h->M, kBlock), (unsigned)prg::ceil_div(h->M, 16));
-    k_build_g<0><<<grid, kBlock, 0, h->stream>>>(pts, h->M, (float)(2.0 * h->beta), tmp);
-    hipError_t e = hipMemcpyAsync(g_hd, tmp, bytes, hipMemcpyDefault, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(tmp);
-    (void)hipFree(pts);
-    PRG_HIP(e);
+    k_build_g<0><<<grid, kBlock, 0, h->stream>>>(pts.p, h->M, (float)(2.0 * h->beta), tmp.p);
+    PRG_HIP(hipMemcpyAsync(g_hd, tmp.p, bytes, hipMemcpyDefault, h->stream));
+    PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }
 
 int prg_cpd_nonrigid_set_w(prg_cpd* h, const double* w_hd) {
-    PRG_REQUIRE(h && h->W && w_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_set_w: G has not been built");
+    PRG_REQUIRE(h && h->W.p && w_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_set_w: G has not been built");
     prg::DeviceGuard g(h->device);
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(double)));
-    PRG_HIP(hipMemcpyAsync(h->stage, w_hd, (size_t)h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
-    k_pack_w<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage, h->M, h->D, h->W, 1, h->perm_src);
+    PRG_HIP(hipMemcpyAsync(h->stage.p, w_hd, (size_t)h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
+    k_pack_w<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage.p, h->M, h->D, h->W.p, 1, h->perm_src.p);
     h->gw_valid = false;
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
@@ -589,18 +560,18 @@ int prg_cpd_nonrigid_set_w(prg_cpd* h, const double* w_hd) {
 }
 
 int prg_cpd_nonrigid_get_w(prg_cpd* h, double* w_hd) {
-    PRG_REQUIRE(h && h->W && w_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_get_w: G has not been built");
+    PRG_REQUIRE(h && h->W.p && w_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_get_w: G has not been built");
     prg::DeviceGuard g(h->device);
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(double)));
-    k_pack_w<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage, h->M, h->D, h->W, 0, h->perm_src);
+    k_pack_w<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage.p, h->M, h->D, h->W.p, 0, h->perm_src.p);
     PRG_HIP(hipGetLastError());
-    PRG_HIP(hipMemcpyAsync(w_hd, h->stage, (size_t)h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
+    PRG_HIP(hipMemcpyAsync(w_hd, h->stage.p, (size_t)h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }
 
 int prg_cpd_nonrigid_set_priors(prg_cpd* h, const double* p1_tilde_hd, const double* px_tilde_hd, double alpha) {
-    PRG_REQUIRE(h && (h->G || h->F), PRG_ERR_STATE, "prg_cpd_nonrigid_set_priors: G has not been built");
+    PRG_REQUIRE(h && (h->G.p || h->F.p), PRG_ERR_STATE, "prg_cpd_nonrigid_set_priors: G has not been built");
     prg::DeviceGuard g(h->device);
     if (!p1_tilde_hd || !px_tilde_hd) {  // clear
         h->nr_alpha = 0.0;
@@ -608,13 +579,13 @@ int prg_cpd_nonrigid_set_priors(prg_cpd* h, const double* p1_tilde_hd, const dou
     }
     PRG_REQUIRE(alpha > 0.0, PRG_ERR_INVALID, "prg_cpd_nonrigid_set_priors: alpha must be > 0 (got %g)", alpha);
     const int64_t m = h->M;
-    if (!h->nr_prior) PRG_HIP(hipMalloc((void**)&h->nr_prior, (size_t)m * 4 * sizeof(double)));
+    if (!h->nr_prior.p) PRG_HIP(h->nr_prior.reset(m * 4));
     PRG_TRY(prg::ensure_stage(h, (size_t)m * (h->D + 1) * sizeof(double)));
-    double* st_p1 = (double*)h->stage;
+    double* st_p1 = (double*)h->stage.p;
     double* st_px = st_p1 + m;
     PRG_HIP(hipMemcpyAsync(st_p1, p1_tilde_hd, (size_t)m * sizeof(double), hipMemcpyDefault, h->stream));
     PRG_HIP(hipMemcpyAsync(st_px, px_tilde_hd, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, h->stream));
-    k_unpack_planes<<<grid1(m), kBlock, 0, h->stream>>>(st_p1, st_px, m, h->D, h->nr_prior, h->perm_src);
+    k_unpack_planes<<<grid1(m), kBlock, 0, h->stream>>>(st_p1, st_px, m, h->D, h->nr_prior.p, h->perm_src.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->nr_alpha = alpha;
@@ -623,7 +594,7 @@ int prg_cpd_nonrigid_set_priors(prg_cpd* h, const double* p1_tilde_hd, const dou
 
 int prg_cpd_rowacc_ptr(prg_cpd* h, double** rowacc_dev, int64_t* count) {
     PRG_REQUIRE(h && h->have_source && rowacc_dev && count, PRG_ERR_STATE, "prg_cpd_rowacc_ptr: source not set");
-    *rowacc_dev = h->rowacc;
+    *rowacc_dev = h->rowacc.p;
     *count = 4 * h->Mcap;
     return PRG_OK;
 }
@@ -644,14 +615,14 @@ __global__ __launch_bounds__(kBlock) void k_apply_out(const float4* __restrict__
 }  // namespace
 
 extern "C" int prg_cpd_nonrigid_apply(prg_cpd* h, double* t_hd) {
-    PRG_REQUIRE(h && (h->G || h->F) && h->W && t_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_apply: G has not been built");
+    PRG_REQUIRE(h && (h->G.p || h->F.p) && h->W.p && t_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_apply: G has not been built");
     prg::DeviceGuard g(h->device);
-    double* gw = h->nr_work;
-    PRG_TRY(prg::nonrigid_gw(h, h->W, gw));
+    double* gw = h->nr_work.p;
+    PRG_TRY(prg::nonrigid_gw(h, h->W.p, gw));
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(double)));
-    k_apply_out<<<grid1(h->M), kBlock, 0, h->stream>>>(h->src4, gw, h->M, h->D, (double*)h->stage, h->perm_src);
+    k_apply_out<<<grid1(h->M), kBlock, 0, h->stream>>>(h->src4.p, gw, h->M, h->D, (double*)h->stage.p, h->perm_src.p);
     PRG_HIP(hipGetLastError());
-    PRG_HIP(hipMemcpyAsync(t_hd, h->stage, (size_t)h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
+    PRG_HIP(hipMemcpyAsync(t_hd, h->stage.p, (size_t)h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }

@@ -981,22 +981,22 @@ int cholesky_small_solve3(prg_cpd* h, const double* S, int64_t mp, double* v, in
     return PRG_OK;
 }
 
-int ensure_solve_workspace(prg_cpd* h, size_t need) {
-    // kernels that keep a 128 x 129 fp64 block in LDS need the opt-in above 64 KB (once per process and device context)
-    for (const void* fn : {reinterpret_cast<const void*>(k_potrf_inv), reinterpret_cast<const void*>(k_trsm_rows),
-                           reinterpret_cast<const void*>(k_tri_solve3<0>), reinterpret_cast<const void*>(k_tri_solve3<1>)})
-        PRG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, NB * LDP * (int)sizeof(double)));
-    if (h->nr_solve_bytes >= need) return PRG_OK;
-    if (h->nr_solve) {
-        PRG_HIP(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->nr_solve);
+// The M-step / BCPD solve workspace of `need` doubles: grows, never shrinks.  A new block takes the sticky pivot flag with it
+// (nr_info points into the block); `lowrank`: ... and starts zeroed, for the low-rank solves, whose flag lives at its end.
+int ensure_solve_workspace(prg_cpd* h, size_t need, bool lowrank) {
+    const bool fresh = h->nr_solve.cap < (int64_t)need;
+    if (fresh) {
+        if (h->nr_solve.p) PRG_HIP(hipStreamSynchronize(h->stream));
+        h->nr_info = nullptr;
+        PRG_HIP(h->nr_solve.reset((int64_t)need));
+        if (lowrank) PRG_HIP(hipMemsetAsync(h->nr_solve.p, 0, need * sizeof(double), h->stream));
     }
-    h->nr_solve = nullptr;
-    h->nr_solve_bytes = 0;
-    PRG_HIP(hipMalloc((void**)&h->nr_solve, need));
-    PRG_HIP(hipMemsetAsync(h->nr_solve, 0, need, h->stream));  // (the sticky pivot flag of the low-rank M-step lives at its end)
-    h->nr_solve_bytes = need;
-    h->nr_info = nullptr;
+    // kernels that keep a 128 x 129 fp64 block in LDS need the opt-in above 64 KB: the low-rank solves ask on every call, as
+    // they always have, the dense ones with a new block
+    if (lowrank || fresh)
+        for (const void* fn : {reinterpret_cast<const void*>(k_potrf_inv), reinterpret_cast<const void*>(k_trsm_rows),
+                               reinterpret_cast<const void*>(k_tri_solve3<0>), reinterpret_cast<const void*>(k_tri_solve3<1>)})
+            PRG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, NB * LDP * (int)sizeof(double)));
     return PRG_OK;
 }
 
@@ -1012,8 +1012,8 @@ int mstep_nonrigid_lowrank(prg_cpd* h, double lmd) {
     const size_t n_s = (size_t)rp * rp, n_linv = (size_t)nblk * NB * NB, n_vec = (size_t)ld * 3,
                  n_part = (size_t)nsplit * ntile * GT * GT + (size_t)nsplit * rank * 3;
     const int tr_blk = (int)prg::ceil_div(m, kBlock);
-    PRG_TRY(ensure_solve_workspace(h, (n_s + n_linv + n_part + 6 * n_vec + (size_t)rp * 3 + 2 * (size_t)tr_blk + 16) * sizeof(double)));
-    double* S = h->nr_solve;
+    PRG_TRY(ensure_solve_workspace(h, n_s + n_linv + n_part + 6 * n_vec + (size_t)rp * 3 + 2 * (size_t)tr_blk + 16, true));
+    double* S = h->nr_solve.p;
     double* linv = S + n_s;
     double* part = linv + n_linv;
     double* upart = part + (size_t)nsplit * ntile * GT * GT;
@@ -1031,10 +1031,10 @@ int mstep_nonrigid_lowrank(prg_cpd* h, double lmd) {
     const dim3 rgrid = grid1(4 * std::max<int64_t>((int64_t)rp * rp, rp * 3));  // four lanes per element
 
     // (info is sticky: cleared when the workspace is allocated and when prg_cpd_get_params has reported it)
-    k_rhs<<<grid1(ld), kBlock, 0, st>>>(h->rowacc, h->Mcap, h->src4, m, ld, h->nr_alpha > 0.0 ? h->nr_prior : nullptr,
+    k_rhs<<<grid1(ld), kBlock, 0, st>>>(h->rowacc.p, h->Mcap, h->src4.p, m, ld, h->nr_alpha > 0.0 ? h->nr_prior.p : nullptr,
                                         h->nr_alpha, h->params, b3, sp);
     // S = c I + F^T D F and z = F^T B in one pass over the factor
-    k_lr_gram<<<ggrid, kBlock, 0, st>>>(h->F, ld, m, rank, sp, nullptr, b3, chunk, part, upart);
+    k_lr_gram<<<ggrid, kBlock, 0, st>>>(h->F.p, ld, m, rank, sp, nullptr, b3, chunk, part, upart);
     k_lr_gram_reduce<<<rgrid, kBlock, 0, st>>>(part, upart, ntile, nsplit, rank, rp, h->params, lmd, S, z);
     const bool small = rp <= 1024;  // (beyond, the MFMA panel solves of the big factorisation pay for their inverses)
     // (one workgroup doing the whole r x r solve out of LDS was built in round 3: with the packed triangle's irregular LDS
@@ -1046,16 +1046,16 @@ int mstep_nonrigid_lowrank(prg_cpd* h, double lmd) {
         PRG_TRY(cholesky_lookahead(h, S, rp, linv, info, rank));
         PRG_TRY(cholesky_solve3(h, S, rp, linv, z));
     }
-    double* gw = h->nr_work;                      // [M][3]: G W, kept for the next E-step's transform
+    double* gw = h->nr_work.p;                      // [M][3]: G W, kept for the next E-step's transform
     // W = (B - D F z) / c ... and G W = F (F^T W) = F z exactly: F^T W = (F^T B - F^T D F z) / c = (S z - (S - c I) z) / c
     PRG_TRY(prg::lowrank_apply(h, z, gw));
-    k_lr_form_w<<<grid1(m), kBlock, 0, st>>>(b3, sp, gw, m, h->params, lmd, h->W);
+    k_lr_form_w<<<grid1(m), kBlock, 0, st>>>(b3, sp, gw, m, h->params, lmd, h->W.p);
     // With correspondence priors the diagonal scaling spans sigma2/alpha ~ 1e7 and the push-through form loses digits
     // to cancellation: two steps of fp64 iterative refinement on the original system (see prg_cpd_mstep_nonrigid)
     const int nrefine = h->nr_alpha > 0.0 ? 2 : 0;
     for (int it = 0; it < nrefine; ++it) {
-        PRG_TRY(prg::nonrigid_gw(h, h->W, gb));
-        k_residual<<<grid1(ld), kBlock, 0, st>>>(b3, sp, gb, h->W, m, ld, h->params, lmd, r3);
+        PRG_TRY(prg::nonrigid_gw(h, h->W.p, gb));
+        k_residual<<<grid1(ld), kBlock, 0, st>>>(b3, sp, gb, h->W.p, m, ld, h->params, lmd, r3);
         if (rp > rank) PRG_HIP(hipMemsetAsync(z + (size_t)rank * 3, 0, (size_t)(rp - rank) * 3 * sizeof(double), st));
         PRG_TRY(prg::lowrank_ft3(h, r3, z));
         if (small)
@@ -1064,10 +1064,10 @@ int mstep_nonrigid_lowrank(prg_cpd* h, double lmd) {
             PRG_TRY(cholesky_solve3(h, S, rp, linv, z));
         PRG_TRY(prg::lowrank_apply(h, z, fz));
         k_lr_form_w<<<grid1(m), kBlock, 0, st>>>(r3, sp, fz, m, h->params, lmd, dw);
-        k_axpy3<<<grid1(m * 3), kBlock, 0, st>>>(dw, m, h->W);
+        k_axpy3<<<grid1(m * 3), kBlock, 0, st>>>(dw, m, h->W.p);
     }
-    if (nrefine > 0) PRG_TRY(prg::nonrigid_gw(h, h->W, gw));
-    k_traces<<<tr_blk, kBlock, 0, st>>>(h->rowacc, h->Mcap, h->src4, gw, m, trpart);
+    if (nrefine > 0) PRG_TRY(prg::nonrigid_gw(h, h->W.p, gw));
+    k_traces<<<tr_blk, kBlock, 0, st>>>(h->rowacc.p, h->Mcap, h->src4.p, gw, m, trpart);
     k_nonrigid_finish<<<1, 64, 0, st>>>(trpart, tr_blk, h->moments, h->params, h->D);
     PRG_HIP(hipGetLastError());
     h->gw_valid = true;
@@ -1080,27 +1080,18 @@ int mstep_nonrigid_lowrank(prg_cpd* h, double lmd) {
 }  // namespace
 
 extern "C" int prg_cpd_mstep_nonrigid(prg_cpd* h, double lmd) {
-    PRG_REQUIRE(h && (h->G || h->F) && h->W && h->have_estep, PRG_ERR_STATE,
+    PRG_REQUIRE(h && (h->G.p || h->F.p) && h->W.p && h->have_estep, PRG_ERR_STATE,
                 "prg_cpd_mstep_nonrigid: needs build_g and an E-step first");
     PRG_REQUIRE(lmd > 0.0, PRG_ERR_INVALID, "prg_cpd_mstep_nonrigid: lmd must be > 0 (got %g)", lmd);
     prg::DeviceGuard g(h->device);
     h->estep_state_live = false;  // sigma2 in PARAMS is the next E-step's now
-    if (h->F) return mstep_nonrigid_lowrank(h, lmd);
+    if (h->F.p) return mstep_nonrigid_lowrank(h, lmd);
     const int64_t m = h->M, mp = prg::round_up(m, NB), nblk = mp / NB;
     // workspace: S [mp*mp] | Linv [nblk*128*128] | b3, gb, v, sp (each <= 3 mp) | trace partials | info
     const size_t n_s = (size_t)mp * mp, n_linv = (size_t)nblk * NB * NB, n_vec = (size_t)mp * 3;
     const int tr_blk = (int)prg::ceil_div(m, kBlock);
-    const size_t need = (n_s + n_linv + 6 * n_vec + 2 * (size_t)tr_blk + 16) * sizeof(double);
-    if (h->nr_solve_bytes < need) {
-        if (h->nr_solve) (void)hipFree(h->nr_solve);
-        h->nr_solve = nullptr;
-        h->nr_solve_bytes = 0;
-        PRG_HIP(hipMalloc((void**)&h->nr_solve, need));
-        h->nr_solve_bytes = need;
-        PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_potrf_inv),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, NB * LDP * (int)sizeof(double)));
-    }
-    double* S = h->nr_solve;
+    PRG_TRY(ensure_solve_workspace(h, n_s + n_linv + 6 * n_vec + 2 * (size_t)tr_blk + 16, false));
+    double* S = h->nr_solve.p;
     double* linv = S + n_s;
     double* b3 = linv + n_linv;
     double* gb = b3 + n_vec;
@@ -1113,9 +1104,9 @@ extern "C" int prg_cpd_mstep_nonrigid(prg_cpd* h, double lmd) {
     hipStream_t st = h->stream;
 
     PRG_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
-    k_rhs<<<grid1(mp), kBlock, 0, st>>>(h->rowacc, h->Mcap, h->src4, m, mp, h->nr_alpha > 0.0 ? h->nr_prior : nullptr,
+    k_rhs<<<grid1(mp), kBlock, 0, st>>>(h->rowacc.p, h->Mcap, h->src4.p, m, mp, h->nr_alpha > 0.0 ? h->nr_prior.p : nullptr,
                                         h->nr_alpha, h->params, b3, sp);
-    k_build_s<<<dim3((unsigned)nblk, (unsigned)nblk), kBlock, 0, st>>>(h->G, m, mp, sp, h->params, lmd, S);
+    k_build_s<<<dim3((unsigned)nblk, (unsigned)nblk), kBlock, 0, st>>>(h->G.p, m, mp, sp, h->params, lmd, S);
 
     PRG_TRY(cholesky_lookahead(h, S, mp, linv, info, m));
     // w = (rhs - D^1/2 S^-1 D^1/2 (G rhs)) / c with the factor above: two blocked triangular sweeps, 3 RHS
@@ -1138,19 +1129,19 @@ extern "C" int prg_cpd_mstep_nonrigid(prg_cpd* h, double lmd) {
         PRG_HIP(hipGetLastError());
         return PRG_OK;
     };
-    PRG_TRY(solve_with_factor(b3, h->W));
+    PRG_TRY(solve_with_factor(b3, h->W.p));
     // With correspondence priors the diagonal scaling spans sigma2/alpha ~ 1e7 and the push-through form
     // loses digits to cancellation; two steps of fp64 iterative refinement on the ORIGINAL system
     // (D G + c I) w = b bring the solution back to the backward-stable level LAPACK gesv delivers.
     const int nrefine = h->nr_alpha > 0.0 ? 2 : 0;
     for (int it = 0; it < nrefine; ++it) {
-        PRG_TRY(prg::nonrigid_gw(h, h->W, gb));
-        k_residual<<<grid1(mp), kBlock, 0, st>>>(b3, sp, gb, h->W, m, mp, h->params, lmd, r3);
+        PRG_TRY(prg::nonrigid_gw(h, h->W.p, gb));
+        k_residual<<<grid1(mp), kBlock, 0, st>>>(b3, sp, gb, h->W.p, m, mp, h->params, lmd, r3);
         PRG_TRY(solve_with_factor(r3, dw));
-        k_axpy3<<<grid1(m * 3), kBlock, 0, st>>>(dw, m, h->W);
+        k_axpy3<<<grid1(m * 3), kBlock, 0, st>>>(dw, m, h->W.p);
     }
-    PRG_TRY(prg::nonrigid_gw(h, h->W, h->nr_work));            // G W, kept for the next E-step's transform
-    k_traces<<<tr_blk, kBlock, 0, st>>>(h->rowacc, h->Mcap, h->src4, h->nr_work, m, trpart);
+    PRG_TRY(prg::nonrigid_gw(h, h->W.p, h->nr_work.p));            // G W, kept for the next E-step's transform
+    k_traces<<<tr_blk, kBlock, 0, st>>>(h->rowacc.p, h->Mcap, h->src4.p, h->nr_work.p, m, trpart);
     k_nonrigid_finish<<<1, 64, 0, st>>>(trpart, tr_blk, h->moments, h->params, h->D);
     PRG_HIP(hipGetLastError());
     h->gw_valid = true;
@@ -1363,8 +1354,8 @@ int bcpd_solve_lowrank(prg_cpd* h, double lmd, double cfac, const double* nu_hd,
     const size_t n_s = (size_t)rp * rp, n_linv = (size_t)nblk * NB * NB, n_vec = (size_t)ld * 3,
                  n_part = (size_t)nsplit * ntile * GT * GT + (size_t)nsplit * rank * 3;
     // S | X = L^-1 | block inverses (look-ahead Cholesky only) | gram partials | b3, sp, nu, diag | z | info
-    PRG_TRY(ensure_solve_workspace(h, (2 * n_s + n_linv + n_part + 4 * n_vec + (size_t)rp * 3 + 16) * sizeof(double)));
-    double* S = h->nr_solve;
+    PRG_TRY(ensure_solve_workspace(h, 2 * n_s + n_linv + n_part + 4 * n_vec + (size_t)rp * 3 + 16, true));
+    double* S = h->nr_solve.p;
     double* X = S + n_s;
     double* linv = X + n_s;
     double* part = linv + n_linv;
@@ -1379,15 +1370,15 @@ int bcpd_solve_lowrank(prg_cpd* h, double lmd, double cfac, const double* nu_hd,
 
     PRG_TRY(prg::ensure_stage(h, (size_t)m * 4 * sizeof(double)));
     double* nu_dev = nullptr;
-    PRG_HIP(hipMemcpyAsync(h->stage, resid_hd, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
+    PRG_HIP(hipMemcpyAsync(h->stage.p, resid_hd, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
     if (nu_hd) {
-        nu_dev = (double*)h->stage + (size_t)m * 3;
+        nu_dev = (double*)h->stage.p + (size_t)m * 3;
         PRG_HIP(hipMemcpyAsync(nu_dev, nu_hd, (size_t)m * sizeof(double), hipMemcpyDefault, st));
     }
     PRG_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
-    k_bcpd_rhs<<<grid1(ld), kBlock, 0, st>>>(h->rowacc, nu_dev, (const double*)h->stage, h->perm_src, m, ld, h->D, b3, sp, nu);
+    k_bcpd_rhs<<<grid1(ld), kBlock, 0, st>>>(h->rowacc.p, nu_dev, (const double*)h->stage.p, h->perm_src.p, m, ld, h->D, b3, sp, nu);
     // S = (lmd / c) I + F^T D F and z = F^T D R in one pass over the factor
-    k_lr_gram<<<dim3((unsigned)ntile, (unsigned)nsplit), kBlock, 0, st>>>(h->F, ld, m, rank, sp, nu, b3, chunk, part, upart);
+    k_lr_gram<<<dim3((unsigned)ntile, (unsigned)nsplit), kBlock, 0, st>>>(h->F.p, ld, m, rank, sp, nu, b3, chunk, part, upart);
     k_lr_gram_reduce<<<grid1(4 * std::max<int64_t>((int64_t)rp * rp, rp * 3)), kBlock, 0, st>>>(part, upart, ntile, nsplit, rank,
                                                                                               rp, nullptr, lmd / cfac, S, z);
     if (rp <= 1024) {
@@ -1397,14 +1388,14 @@ int bcpd_solve_lowrank(prg_cpd* h, double lmd, double cfac, const double* nu_hd,
         PRG_TRY(cholesky_lookahead(h, S, rp, linv, info, rank));
         PRG_TRY(cholesky_solve3(h, S, rp, linv, z));
     }
-    PRG_TRY(prg::lowrank_apply(h, z, h->W));  // v_hat = F S^-1 F^T D R, kept for the next transform
+    PRG_TRY(prg::lowrank_apply(h, z, h->W.p));  // v_hat = F S^-1 F^T D R, kept for the next transform
     k_tri_inverse<<<(unsigned)(rp / TI), kBlock, 0, st>>>(S, rp, rank, X);
-    k_lr_sigma_diag<<<(unsigned)(mp / SD_PTS), kBlock, 0, st>>>(X, rp, rank, h->F, ld, m, 1.0 / cfac, diag);
+    k_lr_sigma_diag<<<(unsigned)(mp / SD_PTS), kBlock, 0, st>>>(X, rp, rank, h->F.p, ld, m, 1.0 / cfac, diag);
 
-    double* stage = (double*)h->stage;
-    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(h->W, 3, h->D, m, h->perm_src, stage);
+    double* stage = (double*)h->stage.p;
+    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(h->W.p, 3, h->D, m, h->perm_src.p, stage);
     PRG_HIP(hipMemcpyAsync(vhat_hd, stage, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
-    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(diag, 1, 1, m, h->perm_src, b3);
+    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(diag, 1, 1, m, h->perm_src.p, b3);
     PRG_HIP(hipMemcpyAsync(sigma_diag_hd, b3, (size_t)m * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipGetLastError());
     int host_info = 0;
@@ -1417,26 +1408,17 @@ int bcpd_solve_lowrank(prg_cpd* h, double lmd, double cfac, const double* nu_hd,
 
 extern "C" int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const double* nu_hd, const double* resid_hd,
                                   double* vhat_hd, double* sigma_diag_hd) {
-    PRG_REQUIRE(h && h->bcpd && (h->G || h->F) && h->W, PRG_ERR_STATE, "prg_cpd_bcpd_solve: needs prg_cpd_bcpd_build_g first");
+    PRG_REQUIRE(h && h->bcpd && (h->G.p || h->F.p) && h->W.p, PRG_ERR_STATE, "prg_cpd_bcpd_solve: needs prg_cpd_bcpd_build_g first");
     PRG_REQUIRE(nu_hd || h->have_estep, PRG_ERR_STATE, "prg_cpd_bcpd_solve: no E-step has run and no nu was given");
     PRG_REQUIRE(resid_hd && vhat_hd && sigma_diag_hd, PRG_ERR_INVALID, "prg_cpd_bcpd_solve: NULL argument");
     PRG_REQUIRE(lmd > 0.0 && cfac > 0.0, PRG_ERR_INVALID, "prg_cpd_bcpd_solve: lmd and c must be > 0 (got %g, %g)", lmd,
                 cfac);
     prg::DeviceGuard g(h->device);
-    if (h->F) return bcpd_solve_lowrank(h, lmd, cfac, nu_hd, resid_hd, vhat_hd, sigma_diag_hd);
+    if (h->F.p) return bcpd_solve_lowrank(h, lmd, cfac, nu_hd, resid_hd, vhat_hd, sigma_diag_hd);
     const int64_t m = h->M, mp = prg::round_up(m, NB), nblk = mp / NB;
     const size_t n_s = (size_t)mp * mp, n_linv = (size_t)nblk * NB * NB, n_vec = (size_t)mp * 3;
-    const size_t need = (2 * n_s + n_linv + 6 * n_vec + (size_t)mp + 16) * sizeof(double);
-    if (h->nr_solve_bytes < need) {
-        if (h->nr_solve) (void)hipFree(h->nr_solve);
-        h->nr_solve = nullptr;
-        h->nr_solve_bytes = 0;
-        PRG_HIP(hipMalloc((void**)&h->nr_solve, need));
-        h->nr_solve_bytes = need;
-        PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_potrf_inv),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, NB * LDP * (int)sizeof(double)));
-    }
-    double* S = h->nr_solve;
+    PRG_TRY(ensure_solve_workspace(h, 2 * n_s + n_linv + 6 * n_vec + (size_t)mp + 16, false));
+    double* S = h->nr_solve.p;
     double* wt = S + n_s;
     double* linv = wt + n_s;
     double* b3 = linv + n_linv;
@@ -1451,16 +1433,16 @@ extern "C" int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const dou
 
     PRG_TRY(prg::ensure_stage(h, (size_t)m * 4 * sizeof(double)));
     double* nu_dev = nullptr;
-    PRG_HIP(hipMemcpyAsync(h->stage, resid_hd, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
+    PRG_HIP(hipMemcpyAsync(h->stage.p, resid_hd, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
     if (nu_hd) {
-        nu_dev = (double*)h->stage + (size_t)m * 3;
+        nu_dev = (double*)h->stage.p + (size_t)m * 3;
         PRG_HIP(hipMemcpyAsync(nu_dev, nu_hd, (size_t)m * sizeof(double), hipMemcpyDefault, st));
     }
     PRG_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
-    k_bcpd_rhs<<<grid1(mp), kBlock, 0, st>>>(h->rowacc, nu_dev, (const double*)h->stage, h->perm_src, m, mp, h->D, b3,
+    k_bcpd_rhs<<<grid1(mp), kBlock, 0, st>>>(h->rowacc.p, nu_dev, (const double*)h->stage.p, h->perm_src.p, m, mp, h->D, b3,
                                             sp);
-    k_build_s<<<dim3((unsigned)nblk, (unsigned)nblk), kBlock, 0, st>>>(h->G, m, mp, sp, nullptr, lmd / cfac, S);
-    k_build_bt<<<dim3((unsigned)prg::ceil_div(mp, kBlock), (unsigned)std::min<int64_t>(mp, 32768)), kBlock, 0, st>>>(h->G, m, mp, sp, wt);
+    k_build_s<<<dim3((unsigned)nblk, (unsigned)nblk), kBlock, 0, st>>>(h->G.p, m, mp, sp, nullptr, lmd / cfac, S);
+    k_build_bt<<<dim3((unsigned)prg::ceil_div(mp, kBlock), (unsigned)std::min<int64_t>(mp, 32768)), kBlock, 0, st>>>(h->G.p, m, mp, sp, wt);
     PRG_TRY(cholesky_lookahead(h, S, mp, linv, info, m));
 
     // Wt <- Wt L^-T, left-looking over panels of k 128-column blocks: one K-deep rectangular update with everything
@@ -1493,7 +1475,7 @@ extern "C" int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const dou
                                                                wt + k0, mp, NB);
         }
     }
-    k_sigma_diag<<<(unsigned)prg::ceil_div(m, 4), kBlock, 0, st>>>(wt, h->G, m, mp, lmd, diag);
+    k_sigma_diag<<<(unsigned)prg::ceil_div(m, 4), kBlock, 0, st>>>(wt, h->G.p, m, mp, lmd, diag);
 
     // v_hat = (c / lmd) (G b - G D^1/2 S^-1 D^1/2 G b)
     PRG_TRY(prg::nonrigid_gw(h, b3, gb));
@@ -1512,13 +1494,13 @@ extern "C" int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const dou
     }
     k_scale_rows<<<grid1(m), kBlock, 0, st>>>(sp, v, m, tv);
     PRG_TRY(prg::nonrigid_gw(h, tv, gt));
-    k_bcpd_vhat<<<grid1(m * 3), kBlock, 0, st>>>(gb, gt, m, cfac / lmd, h->W);
+    k_bcpd_vhat<<<grid1(m * 3), kBlock, 0, st>>>(gb, gt, m, cfac / lmd, h->W.p);
 
     // results back in the caller's point order
-    double* stage = (double*)h->stage;
-    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(h->W, 3, h->D, m, h->perm_src, stage);
+    double* stage = (double*)h->stage.p;
+    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(h->W.p, 3, h->D, m, h->perm_src.p, stage);
     PRG_HIP(hipMemcpyAsync(vhat_hd, stage, (size_t)m * h->D * sizeof(double), hipMemcpyDefault, st));
-    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(diag, 1, 1, m, h->perm_src, gb);
+    k_unsort_rows<<<grid1(m), kBlock, 0, st>>>(diag, 1, 1, m, h->perm_src.p, gb);
     PRG_HIP(hipMemcpyAsync(sigma_diag_hd, gb, (size_t)m * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipGetLastError());
     int host_info = 0;

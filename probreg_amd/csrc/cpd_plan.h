@@ -1,7 +1,9 @@
 // Internal definition of the CPD plan (opaque `prg_cpd` of include/probreg_hip.h).
 #pragma once
+#include <cstddef>
 #include <vector>
 
+#include "cpd_buffers.h"
 #include "prg_common.h"
 
 // Which engine an E-step's sweeps run on while a registration is in the dense regime.  The decision needs
@@ -25,7 +27,15 @@ struct EngineDecision {
     int fused;     // 1: ONE sweep for this E-step (k_colpass_mfma<FUSED>: rigid M-step moments from the column side, no row pass)
     int pad_;      // (64-bit counters and doubles sit right behind the device copy of this struct)
 };
-static_assert(sizeof(EngineDecision) % 8 == 0, "the engine state behind EngineDecision needs 8-byte alignment");
+// Device state of the engine decision: the decision itself, the matrix-core sweeps' tile counters and the LOCAL target's sums
+// (prg_cpd_init_sums keeps a copy here: the caller all-reduces the moments block it also writes them to).
+struct EngineState {
+    EngineDecision decision;
+    unsigned long long work[2];  // (128 x 16) tiles the matrix-core column / row pass evaluated (read + cleared by the decision)
+    double tsum[4];              // (sum x, sum y, sum z, sum |x|^2) of the local target
+};
+static_assert(offsetof(EngineState, work) == sizeof(EngineDecision), "the 64-bit counters sit right behind the decision (pad_)");
+constexpr unsigned kMailboxFlags = hipHostMallocMapped | hipHostMallocCoherent;  // how the host's copy of the decision is allocated
 struct EngineArgs {  // host -> k_chunk_meta_bbox, by value
     double ext2;
     // matrix-core sweeps while they evaluate at least this many pairs per owned point (engine_leave_below, cpd_estep.hip)
@@ -88,19 +98,7 @@ struct CpdEnv {
     std::string spatial_order;
 };
 
-// Work queue of one sparse-regime sweep (cpd_sweeps_queue.hip): 16-bit need-masks per (owned block of 128 points, segment of 16
-// streamed groups), the number of non-empty segments per block, and the units the persistent waves pop.
-struct SweepQueue {
-    unsigned long long* masks = nullptr;  // [nblocks][nchunk][8] one bit per streamed group of 32: needed or not
-    int2* chunk = nullptr;            // [nblocks][nchunk] (first slot, units) of every chunk of 512 groups
-    int2* units = nullptr;            // [<= max units] (block, first group | count << 22), in append order
-    int* ctrl = nullptr;              // counters, see k_queue_build
-    unsigned* ucount = nullptr;       // [units] (128 x 32) blocks each unit evaluated (prg_cpd_pair_counts)
-    int64_t cap_blocks = 0, cap_units = 0;
-    int cap_chunk = 0;
-    int64_t nblocks = 0;
-    int nchunk = 0, cap_soft = 0;
-};
+using prg::SweepQueue;  // (cpd_buffers.h)
 
 // Communicator of the per-iteration all-reduce (comm.hip): an RCCL communicator the library created (prg_comm_create) or
 // one the caller handed over (prg_comm_adopt).
@@ -111,34 +109,23 @@ struct prg_comm {
     int64_t calls = 0;     // all-reduces issued (tests / measurements)
 };
 
-// Row accumulator block: 4 fp64 planes of Mcap (p1, px0, px1, px2), written by the moment kernel.
-struct prg_cpd {
+// Every device or pinned allocation of the plan is an owning buffer (dev_buf.h): the capacity is buf.cap, and destroying the
+// plan frees them.  The clouds' groups (src4, z4, rowacc, zmeta, rorig, zchunk, Mcap / tgt4, pt1, tmeta, tchunk, corig, colmin,
+// Ncap) are the bases' members (cpd_buffers.h).
+struct prg_cpd : prg::SourceBuffers, prg::TargetBuffers {
     int device = 0;
     hipStream_t stream = nullptr;
 
     int64_t M = 0, N = 0, Nglobal = 0;
     int D = 0;
-    int64_t Mcap = 0, Ncap = 0;  // padded capacities (multiples of 1024, + slack for segmenting)
 
-    // clouds in their kernel layout (float4 per point: x, y, z, aux)
-    float4* src4 = nullptr;   // original source y_m            (aux = 0)
-    float4* z4 = nullptr;     // transformed source z_m         (aux = 0), rewritten every E-step
-    float4* tgt4 = nullptr;   // local target x_n               (aux = b_n = -log2(den_n + c))
-    float* pt1 = nullptr;     // [Ncap] column sums of P
+    prg::DevBuf<float2> colpart;  // column pass partials [SA][Ncap] (dmin, sum); grows, never shrinks
+    prg::DevBuf<float> rowpart;   // row pass partials [SB][5][Mcap] (p1, ux, uy, uz, e); grows, never shrinks
+    // moment block partials [nblk][24] ... and 64 doubles of scratch at the END OF THE ALLOCATION (mom_scratch, cpd_estep.h); grows,
+    // never shrinks
+    prg::DevBuf<double> mompart;
 
-    // column pass partials [SA][Ncap] (dmin, sum)
-    float2* colpart = nullptr;
-    int64_t colpart_elems = 0;
-    // row pass partials [SB][5][Mcap] (p1, ux, uy, uz, e)
-    float* rowpart = nullptr;
-    int64_t rowpart_elems = 0;
-    // fp64 per-row block [4][Mcap]
-    double* rowacc = nullptr;
-    // moment block partials [nblk][24]
-    double* mompart = nullptr;
-    int64_t mompart_elems = 0;
-
-    double* state = nullptr;    // owned: PRG_NMOMENTS + PRG_NPARAMS doubles
+    prg::DevBuf<double> state;  // PRG_NMOMENTS + PRG_NPARAMS doubles
     double* moments = nullptr;  // -> state or caller-bound memory
     double* params = nullptr;   // -> state + PRG_NMOMENTS
 
@@ -147,20 +134,14 @@ struct prg_cpd {
 
     // spatial sorting + exact culling
     bool opt_sort_src = true, opt_sort_tgt = true, opt_cull = true;
-    int* perm_src = nullptr;    // [M] sorted position -> original index (nullptr = identity order)
-    int* perm_tgt = nullptr;    // [N]
-    float* zmeta = nullptr;     // [Mcap/32][8] per group of 32 transformed source points: lo.xyz, hi.xyz, -, -
-    float* tmeta = nullptr;     // [Ncap/32][8] per group of 32 target points: lo.xyz, hi.xyz, max b_n, min b_n
-    float* colmin = nullptr;    // [Ncap] min_m d^2 per column from the previous E-step (seed of the cull bound),
-                                // followed by [Ncap/32] per-group maxima of it
-    unsigned* motion = nullptr; // [16] float bits, slot = parity of the E-step: [0,1] max_m |z_new - z_old| of the transform,
+    prg::DevBuf<int> perm_src;  // [M] sorted position -> original index (empty = identity order)
+    prg::DevBuf<int> perm_tgt;  // [N]
+    prg::DevBuf<unsigned> motion;  // [16] float bits, slot = parity of the E-step: [0,1] max_m |z_new - z_old| of the transform,
                                 // [4,5] largest column minimum of the E-step (what the host needs to decide whether the
                                 // matrix-core column pass may run); [8..13] bounding box of the transformed
                                 // source (lo.xyz, hi.xyz) of the current E-step
     bool have_colmin = false;
     // matrix-core (dense regime) sweeps
-    float4* rorig = nullptr;    // [Mcap/512] origin of each 512-row block of the last matrix-core row pass
-    float4* corig = nullptr;    // [Ncap/512] origin of each 512-column block of the last fused sweep
     bool fused_in_iterate = true;  // prg_cpd_iterate(RIGID) switches moments_only on for its own E-steps (prg_cpd_set_moments_only(2): not)
     bool moments_only = false;  // E-steps of this plan feed a RIGID M-step and nothing else: the dense regime may run the fused
                                 // single sweep, which leaves no per-point p1 / px (prg_cpd_set_moments_only, prg_cpd_iterate)
@@ -169,20 +150,18 @@ struct prg_cpd {
                                 // prg_cpd_set_resid_sweep(0): two sweeps there)
     bool last_estep_fused = false;
     bool rowacc_valid = false;  // the per-point block (p1, px) holds the last E-step's result (not after a fused sweep)
-    float* zchunk = nullptr;    // [Mcap/256][8] box of every 256-point chunk of the transformed source (per E-step)
-    float* tchunk = nullptr;    // [Ncap/256][8] box + largest b_n of every 256-point chunk of the target (per E-step)
     int dense_engine = 1;       // 0: VALU sweeps only, 1: matrix-core sweeps in the dense regime,
                                 // 2: both sweeps on the matrix cores, always (tests)
     double dense_bound = 0.0;    // > 0: matrix-core column pass while it evaluates at least this many source points per target (0: the cost model, engine_leave_below)
-    double* tsum_local = nullptr;            // (sum x, sum y, sum z, sum |x|^2) of the local target, beside the decision
-    unsigned long long* eng_work = nullptr;  // [2] tiles evaluated by the matrix-core column / row pass (read + cleared by the decision)
+    double* tsum_local = nullptr;            // -> eng_dev.p->tsum
+    unsigned long long* eng_work = nullptr;  // -> eng_dev.p->work
     // (the work queues' memory - q_first_*, q*_live below - is NOT part of the switch's: a sweep over a queue sizes its units from the
     // previous sweep over that queue, whichever registration ran it)
     int q_first_col = 32, q_first_row = 32;  // groups per unit of the first queue sweep after a matrix-core one
     EngineSwitch eng;            // the engine switch's memory of this registration (prg_cpd_init_params: eng = EngineSwitch())
-    EngineDecision* eng_dev = nullptr;   // device copy of the current E-step's decision (guard of the column-pass launches)
-    EngineDecision* eng_host = nullptr;  // mapped, coherent host memory: the mailbox the host polls
-    EngineDecision* eng_host_dev = nullptr;  // ... as the device addresses it
+    prg::DevBuf<EngineState> eng_dev;        // its `decision`: device copy of the current E-step's (guard of the column-pass launches)
+    prg::HostBuf<EngineDecision> eng_host;   // mapped, coherent host memory (kMailboxFlags): the mailbox the host polls
+    EngineDecision* eng_host_dev = nullptr;  // ... as the device addresses it (= eng_host.dev)
     bool mfma_stream = true;    // dense-regime launches of the matrix-core sweeps are cut in stream mode (prg_cpd_set_stream_mode)
     int mfma_col_planes = 0, mfma_row_planes = 0;  // partial planes the last matrix-core column / row pass wrote (grid or stream mode)
     bool last_estep_row_lean = false;  // ... matrix-core row pass without its residual sums
@@ -200,21 +179,21 @@ struct prg_cpd {
     // measurement hook: evaluated (wave, group) blocks per workgroup of the last culled column / row pass
     // ([0, wg_cap) column pass, [wg_cap, 2 wg_cap) row pass); wg_col / wg_row = workgroups of the last launches,
     // dense_pairs_* = pairs covered by the last NON-culled launches (0 when the culled kernels ran)
-    unsigned* wgcount = nullptr;
-    int64_t wg_cap = 0, wg_col = 0, wg_row = 0;
+    prg::DevBuf<unsigned> wgcount;  // two halves of wg_cap(); grows, never shrinks
+    int64_t wg_cap() const { return wgcount.cap / 2; }
+    int64_t wg_col = 0, wg_row = 0;
     double wg_col_pairs = 128.0 * 32.0, wg_row_pairs = 128.0 * 32.0;  // pairs one counted block stands for
     double dense_pairs_col = 0.0, dense_pairs_row = 0.0;
     uint64_t estep_count = 0;   // parity selects the motion slot of the current E-step
 
     // staging for uploads / moments_from_estep
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
+    prg::DevBuf<char> stage;  // grows, never shrinks (prg::ensure_stage)
 
     // non-rigid state
-    float* G = nullptr;        // [M][M] float32 (row-major)
-    double* W = nullptr;       // [M][3] float64 (row-major, 3 columns always)
+    prg::DevBuf<float> G;      // [M][M] float32 (row-major)
+    prg::DevBuf<double> W;     // [M][3] float64 (row-major, 3 columns always)
     // ... or its pivoted-Cholesky factor G = F F^T (non-rigid CPD): F[k * f_ld + i], k < f_rank
-    double* F = nullptr;
+    prg::DevBuf<double> F;
     int64_t f_ld = 0;          // round_up(M, 256) + 32
     int f_rank = 0, f_cap = 0;
     int nr_solver = 1;         // 1: low-rank factor when the rank allows (default), 0: dense G + M x M Cholesky
@@ -224,20 +203,18 @@ struct prg_cpd {
                                // of the reduced system - where 1e-14 is rank 176)
     double beta = 0.0;
     bool nonrigid = false;
-    double* nr_work = nullptr;  // [16 M] doubles: G.W product and scratch
+    prg::DevBuf<double> nr_work;  // [16 M + 3 kMaxRank]: G.W product and scratch
     bool gw_valid = false;      // nr_work[0, 3M) holds G W of the current W (left by the M-step, consumed by the transform)
-    size_t nr_work_bytes = 0;
-    double* nr_solve = nullptr;  // M-step workspace: S (fp64 M x M), block inverses, vectors
-    size_t nr_solve_bytes = 0;
-    int* nr_info = nullptr;      // device: first non-positive pivot + 1 of a low-rank M-step since the last report (0: none)
-    double* nr_prior = nullptr;            // [4][M]: p1_tilde, px_tilde (3 planes) of ConstrainedNonRigidCPD
+    prg::DevBuf<double> nr_solve;  // M-step workspace: S (fp64 M x M), block inverses, vectors; grows, never shrinks
+    int* nr_info = nullptr;      // -> into nr_solve (cleared whenever that is re-created): first non-positive pivot + 1 of a low-rank M-step since the last report (0: none)
+    prg::DevBuf<double> nr_prior;          // [4][M]: p1_tilde, px_tilde (3 planes) of ConstrainedNonRigidCPD
     double nr_alpha = 0.0;                 // 0 = no correspondence priors
     hipStream_t nr_stream2 = nullptr;      // side stream of the look-ahead Cholesky
     std::vector<hipEvent_t> nr_events;
 
     // per-source log-weights (BCPD E-step, bcpd.py:53-72): srcw[m] = ln a_m <= 0 in kernel (sorted) order; the
     // transform kernel turns it into the additive squared distance q_m = -2 sigma2 ln a_m carried in z4.w
-    float* srcw = nullptr;
+    prg::DevBuf<float> srcw;
     double uniform_ratio = 0.0;  // > 0: replaces M / N in the outlier constant of cpd.py:78-79
     bool bcpd = false;           // G is the inverse multiquadric kernel, W holds the displacement v_hat
     // solver of the next prg_cpd_bcpd_build_g (prg_cpd_bcpd_set_solver)
@@ -245,16 +222,15 @@ struct prg_cpd {
     int bcpd_max_rank = 0;       // 0: min(2048, M / 2)
     double bcpd_tol = 1.0e-11;   // largest entry of G - F F^T the factor may leave
 
-    double* pinned = nullptr;    // 64 doubles of pinned host memory for the per-iteration parameter read-back
+    prg::HostBuf<double> pinned; // 64 doubles of pinned host memory for the per-iteration parameter read-back
 
     bool have_source = false, have_target = false, have_estep = false;
     double last_w = 0.0;
     // z4, tgt4.w (b_n), the weights and sigma2 in PARAMS are still those of ONE E-step: set by every prg_cpd_estep, cleared by
     // whatever writes PARAMS, the weights or an E-step result of the caller's (what prg_cpd_correspond reads, cpd_correspond.hip)
     bool estep_state_live = false;
-    // workspace of prg_cpd_correspond (packed clouds, partial lists, results): grows, never shrinks, freed with the plan
-    void* corr_buf = nullptr;
-    size_t corr_bytes = 0;
+    // workspace of prg_cpd_correspond (packed clouds, partial lists, results): grows, never shrinks
+    prg::DevBuf<char> corr_buf;
 
     // multi-GPU: when set, prg_cpd_estep / prg_cpd_init_sums end with the SUM all-reduce of the moment block (and, for a
     // non-rigid plan, of the per-point block) on the plan's stream; not owned by the plan

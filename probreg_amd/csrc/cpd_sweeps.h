@@ -23,7 +23,7 @@ __device__ __forceinline__ float col_offset(float kk, float dmin) {
 
 // ---- matrix-core sweeps (cpd_sweeps_mfma.hip) ----
 constexpr int kMfmaOwn = 8;                       // tiles of 16 points a wave owns (128 rows / columns)
-constexpr int kMfmaWgPoints = 4 * 16 * kMfmaOwn;  // points a workgroup owns and shifts to one origin (512)
+static_assert(kMfmaWgPoints == 4 * 16 * kMfmaOwn, "cpd_buffers.h sizes the origin arrays per workgroup of the matrix-core sweeps");
 // Exponent offset of a column's sum in the matrix-core column pass, from what is known BEFORE the sweep: cm = min d^2 of
 // the previous E-step, mo = largest source displacement since.  This E-step's minimum lies in
 // [max(sqrt(cm) - mo, 0)^2, (sqrt(cm) + mo)^2] = [lo, hi]; with g = |kk| (hi - lo) the offset |kk| lo + max(g - 80, 0) keeps
@@ -64,7 +64,6 @@ int owner_planes(int64_t owned_points, int64_t streamed_points);
 void launch_colpass_owner(prg_cpd* h, bool use_seed, int planes);
 
 // ---- sparse-regime work queue (cpd_sweeps_queue.hip) ----
-constexpr int kQueueChunkGroups = 512;   // streamed groups (of 32 points) one wave of the build pass tests: 8 mask words
 constexpr int kQueueTargetUnits = 16384; // the units grow (8 -> 16 -> 32 groups) when a sweep had more than twice as many (~2 per wave slot)
 constexpr int kQueueMaxUnits = 98304;    // fine units the queue holds (250 MB of row-pass partials); beyond, a chunk is one coarse unit
 constexpr int kQueueWorkgroups = 2048;   // persistent grid: 8 workgroups of 4 waves per CU
@@ -87,14 +86,13 @@ int prepare_queues(prg_cpd* h);  // allocations of both queues for the plan's cu
 #define PRG_CULL_EXP 48
 #endif
 constexpr float kCullExp = (float)PRG_CULL_EXP;
-constexpr int kGroup = 32;     // streamed points per cull group (8 scalar quad loads)
-constexpr int kSuper = 256;    // quantum of a culled segment's length (8 groups)
+// (kGroup = 32 streamed points per cull group, kSuper = 256 quantum of a culled segment's length: cpd_buffers.h)
 // culled variants (packed arithmetic, 2 adjacent points per lane); seg_len must be a multiple of kGroup
 // resid: the residual-form single sweep of a rigid iteration (k_colpass_cull<true>): planes of 6 floats per column
 // [plane][6][Ncap] in h->colpart, followed by one touched-flag byte per (128-column block, plane) - resid_flags()
 void launch_colpass_cull(prg_cpd* h, int S, int seg_len, bool use_seed, const EngineDecision* guard = nullptr, bool resid = false);
 inline unsigned char* resid_flags(const prg_cpd* h, int planes) {
-    return reinterpret_cast<unsigned char*>(reinterpret_cast<float*>(h->colpart) + (int64_t)planes * 6 * h->Ncap);
+    return reinterpret_cast<unsigned char*>(reinterpret_cast<float*>(h->colpart.p) + (int64_t)planes * 6 * h->Ncap);
 }
 void launch_rowpass_cull(prg_cpd* h, int S, int seg_len);
 void launch_colpass_packed(prg_cpd* h, int R, int S, int seg_len);

@@ -921,8 +921,8 @@ void launch_chunk_meta_bbox(prg_cpd* h, const EngineArgs* eng) {
     EngineArgs none;
     none.dev = nullptr;
     none.host = nullptr;
-    k_chunk_meta_bbox<<<1, kBlock, 0, h->stream>>>(reinterpret_cast<const BoxMeta*>(h->zmeta), h->Mcap / kChunk,
-                                                  reinterpret_cast<BoxMeta*>(h->zchunk), h->z4, h->M, h->motion, h->params,
+    k_chunk_meta_bbox<<<1, kBlock, 0, h->stream>>>(reinterpret_cast<const BoxMeta*>(h->zmeta.p), h->Mcap / kChunk,
+                                                  reinterpret_cast<BoxMeta*>(h->zchunk.p), h->z4.p, h->M, h->motion.p, h->params,
                                                   eng ? *eng : none);
 }
 
@@ -975,11 +975,11 @@ void launch_colpass_mfma(prg_cpd* h, int S, bool first, bool fine, const EngineD
     const StreamCut cut = stream_cut(sp, nblocks, ceil_div(h->M, kChunk));
     if (sp) grid = dim3((unsigned)cut.g, 1);
     // (zchunk: boxes of this E-step's transformed source, written by launch_chunk_meta_bbox before the engine decision)
-    k_colpass_mfma<false><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, reinterpret_cast<const BoxMeta*>(h->tmeta),
-                                                   reinterpret_cast<const BoxMeta*>(h->zmeta),
-                                                   reinterpret_cast<const BoxMeta*>(h->zchunk), h->colmin, h->colmin + h->Ncap,
-                                                   h->motion + ((h->estep_count - 1) & 1), cps, h->M, h->N, h->params,
-                                                   h->colpart, h->Ncap, h->wgcount, h->eng_work, first ? 1 : 0, fine ? 1 : 0, guard,
+    k_colpass_mfma<false><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, reinterpret_cast<const BoxMeta*>(h->tmeta.p),
+                                                   reinterpret_cast<const BoxMeta*>(h->zmeta.p),
+                                                   reinterpret_cast<const BoxMeta*>(h->zchunk.p), h->colmin.p, h->colmin.p + h->Ncap,
+                                                   h->motion.p + ((h->estep_count - 1) & 1), cps, h->M, h->N, h->params,
+                                                   h->colpart.p, h->Ncap, h->wgcount.p, h->eng_work, first ? 1 : 0, fine ? 1 : 0, guard,
                                                    cut, nullptr);
     h->wg_col = nblocks * h->mfma_col_planes;  // (evaluated-tile counters: one per (plane, block))
     h->wg_col_pairs = 128.0 * 16.0;  // counted unit: one wave's 128 points x one 16-point tile
@@ -994,12 +994,12 @@ void launch_fused_mfma(prg_cpd* h, int S, bool first, bool fine, const EngineDec
     dim3 grid((unsigned)nblocks, (unsigned)ceil_div(ceil_div(h->M, kChunk), cps));
     h->mfma_col_planes = (int)grid.y;
     const StreamCut none = {0, 0, 0u, 0u};
-    k_colpass_mfma<true><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, reinterpret_cast<const BoxMeta*>(h->tmeta),
-                                                         reinterpret_cast<const BoxMeta*>(h->zmeta),
-                                                         reinterpret_cast<const BoxMeta*>(h->zchunk), h->colmin, h->colmin + h->Ncap,
-                                                         h->motion + ((h->estep_count - 1) & 1), cps, h->M, h->N, h->params,
-                                                         h->colpart, h->Ncap, h->wgcount, h->eng_work, first ? 1 : 0, fine ? 1 : 0, guard,
-                                                         none, h->corig);
+    k_colpass_mfma<true><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, reinterpret_cast<const BoxMeta*>(h->tmeta.p),
+                                                         reinterpret_cast<const BoxMeta*>(h->zmeta.p),
+                                                         reinterpret_cast<const BoxMeta*>(h->zchunk.p), h->colmin.p, h->colmin.p + h->Ncap,
+                                                         h->motion.p + ((h->estep_count - 1) & 1), cps, h->M, h->N, h->params,
+                                                         h->colpart.p, h->Ncap, h->wgcount.p, h->eng_work, first ? 1 : 0, fine ? 1 : 0, guard,
+                                                         none, h->corig.p);
     h->wg_col = nblocks * h->mfma_col_planes;
     h->wg_col_pairs = 128.0 * 16.0;
     h->dense_pairs_col = 0.0;
@@ -1014,12 +1014,12 @@ void launch_rowpass_mfma(prg_cpd* h, int S, bool fine, bool lean, bool stream) {
     const StreamCut cut = stream_cut(sp, nblocks, ceil_div(h->N, kChunk));
     if (sp) grid = dim3((unsigned)cut.g, 1);
     // touched flags: 64 bytes per 128-row block, behind the planes this launch writes (k_row_moments is told the same count)
-    unsigned char* rowflag = reinterpret_cast<unsigned char*>(h->rowpart + (int64_t)h->mfma_row_planes * 5 * h->Mcap);
-    launch_chunk_meta(h, h->tmeta, h->Ncap, h->tchunk);  // target boxes with this E-step's b_n ranges (after k_colfinal)
+    unsigned char* rowflag = reinterpret_cast<unsigned char*>(h->rowpart.p + (int64_t)h->mfma_row_planes * 5 * h->Mcap);
+    launch_chunk_meta(h, h->tmeta.p, h->Ncap, h->tchunk.p);  // target boxes with this E-step's b_n ranges (after k_colfinal)
     auto kernel = sp ? k_rowpass_mfma<true, true> : lean ? k_rowpass_mfma<true, false> : k_rowpass_mfma<false, false>;
-    kernel<<<grid, kBlock, 0, h->stream>>>(h->z4, h->tgt4, reinterpret_cast<const BoxMeta*>(h->zmeta),
-                                           reinterpret_cast<const BoxMeta*>(h->tmeta), reinterpret_cast<const BoxMeta*>(h->tchunk), cps,
-                                           h->N, h->M, h->params, h->rowpart, h->Mcap, h->rorig, rowflag, h->wgcount + h->wg_cap,
+    kernel<<<grid, kBlock, 0, h->stream>>>(h->z4.p, h->tgt4.p, reinterpret_cast<const BoxMeta*>(h->zmeta.p),
+                                           reinterpret_cast<const BoxMeta*>(h->tmeta.p), reinterpret_cast<const BoxMeta*>(h->tchunk.p), cps,
+                                           h->N, h->M, h->params, h->rowpart.p, h->Mcap, h->rorig.p, rowflag, h->wgcount.p + h->wg_cap(),
                                            h->eng_work + 1, fine ? 1 : 0, cut);
     h->wg_row = nblocks * h->mfma_row_planes;
     h->wg_row_pairs = 128.0 * 16.0;

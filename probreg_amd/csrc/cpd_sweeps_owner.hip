@@ -309,10 +309,10 @@ void launch_colpass_owner(prg_cpd* h, bool use_seed, int planes) {
     const int cpl = owner_cols_per_lane();
     dim3 grid((unsigned)ceil_div(h->N, 64 * cpl), (unsigned)planes);
 #define PRG_OWNER_ARGS                                                                                                              \
-    h->tgt4, h->z4, reinterpret_cast<const GroupMeta*>(h->zchunk), reinterpret_cast<const GroupMeta*>(h->zmeta),                    \
-        reinterpret_cast<const GroupMeta*>(h->tmeta), h->N, (int)ceil_div(h->M, kSuper), (int)ceil_div(h->M, kGroup), h->params,    \
-        use_seed ? h->colmin + h->Ncap : nullptr, h->motion + ((h->estep_count - 1) & 1), reinterpret_cast<float*>(h->colpart),     \
-        h->Ncap, h->wgcount, resid_flags(h, planes)
+    h->tgt4.p, h->z4.p, reinterpret_cast<const GroupMeta*>(h->zchunk.p), reinterpret_cast<const GroupMeta*>(h->zmeta.p),                    \
+        reinterpret_cast<const GroupMeta*>(h->tmeta.p), h->N, (int)ceil_div(h->M, kSuper), (int)ceil_div(h->M, kGroup), h->params,    \
+        use_seed ? h->colmin.p + h->Ncap : nullptr, h->motion.p + ((h->estep_count - 1) & 1), reinterpret_cast<float*>(h->colpart.p),     \
+        h->Ncap, h->wgcount.p, resid_flags(h, planes)
     if (cpl == 1)
         k_colpass_owner<1><<<grid, kThreads, 0, h->stream>>>(PRG_OWNER_ARGS);
     else

@@ -170,9 +170,9 @@ void launch_colpass_packed(prg_cpd* h, int R, int S, int seg_len) {
     h->wg_col = 0;
     h->dense_pairs_col = (double)grid.x * (kBlock * R) * (double)S * seg_len;
     if (R == 2)
-        k_colpass<1><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, seg_len, h->params, h->colpart, h->Ncap);
+        k_colpass<1><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, seg_len, h->params, h->colpart.p, h->Ncap);
     else
-        k_colpass<2><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, seg_len, h->params, h->colpart, h->Ncap);
+        k_colpass<2><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, seg_len, h->params, h->colpart.p, h->Ncap);
 }
 
 void launch_rowpass_packed(prg_cpd* h, int R, int S, int seg_len) {
@@ -180,9 +180,9 @@ void launch_rowpass_packed(prg_cpd* h, int R, int S, int seg_len) {
     h->wg_row = 0;
     h->dense_pairs_row = (double)grid.x * (kBlock * R) * (double)S * seg_len;
     if (R == 2)
-        k_rowpass<1><<<grid, kBlock, 0, h->stream>>>(h->z4, h->tgt4, seg_len, h->params, h->rowpart, h->Mcap);
+        k_rowpass<1><<<grid, kBlock, 0, h->stream>>>(h->z4.p, h->tgt4.p, seg_len, h->params, h->rowpart.p, h->Mcap);
     else
-        k_rowpass<2><<<grid, kBlock, 0, h->stream>>>(h->z4, h->tgt4, seg_len, h->params, h->rowpart, h->Mcap);
+        k_rowpass<2><<<grid, kBlock, 0, h->stream>>>(h->z4.p, h->tgt4.p, seg_len, h->params, h->rowpart.p, h->Mcap);
 }
 
 }  // namespace prg
@@ -622,17 +622,17 @@ extern "C" int prg_debug_set_wave_trace(unsigned long long* dev_buffer, unsigned
 void launch_colpass_cull(prg_cpd* h, int S, int seg_len, bool use_seed, const EngineDecision* guard, bool resid) {
     dim3 grid((unsigned)ceil_div(h->N, 128), (unsigned)ceil_div(S, 4));
     if (resid)  // planes of 6 floats per column, then one touched-flag byte per (128-column block, plane)
-        k_colpass_cull<true><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, reinterpret_cast<const GroupMeta*>(h->zmeta),
-                                                             reinterpret_cast<const GroupMeta*>(h->tmeta), seg_len, S, h->params,
-                                                             use_seed ? h->colmin + h->Ncap : nullptr,
-                                                             h->motion + ((h->estep_count - 1) & 1), h->colpart, h->Ncap,
-                                                             h->wgcount, guard, resid_flags(h, (int)grid.y));
+        k_colpass_cull<true><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, reinterpret_cast<const GroupMeta*>(h->zmeta.p),
+                                                             reinterpret_cast<const GroupMeta*>(h->tmeta.p), seg_len, S, h->params,
+                                                             use_seed ? h->colmin.p + h->Ncap : nullptr,
+                                                             h->motion.p + ((h->estep_count - 1) & 1), h->colpart.p, h->Ncap,
+                                                             h->wgcount.p, guard, resid_flags(h, (int)grid.y));
     else
-    k_colpass_cull<false><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, reinterpret_cast<const GroupMeta*>(h->zmeta),
-                                                   reinterpret_cast<const GroupMeta*>(h->tmeta), seg_len, S, h->params,
-                                                   use_seed ? h->colmin + h->Ncap : nullptr,
-                                                   h->motion + ((h->estep_count - 1) & 1), h->colpart, h->Ncap,
-                                                   h->wgcount, guard, nullptr);
+    k_colpass_cull<false><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, reinterpret_cast<const GroupMeta*>(h->zmeta.p),
+                                                   reinterpret_cast<const GroupMeta*>(h->tmeta.p), seg_len, S, h->params,
+                                                   use_seed ? h->colmin.p + h->Ncap : nullptr,
+                                                   h->motion.p + ((h->estep_count - 1) & 1), h->colpart.p, h->Ncap,
+                                                   h->wgcount.p, guard, nullptr);
     h->wg_col = (int64_t)grid.x * grid.y;
     h->wg_col_pairs = 128.0 * kGroup;  // (a mispredicted matrix-core launch ahead of this one has left its own unit here)
     h->dense_pairs_col = 0.0;
@@ -641,11 +641,11 @@ void launch_colpass_cull(prg_cpd* h, int S, int seg_len, bool use_seed, const En
 void launch_rowpass_cull(prg_cpd* h, int S, int seg_len) {
     const int planes = (int)ceil_div(S, 4);
     dim3 grid((unsigned)ceil_div(h->M, 128), (unsigned)planes);
-    k_rowpass_cull<<<grid, kBlock, 0, h->stream>>>(h->z4, h->tgt4, reinterpret_cast<const GroupMeta*>(h->tmeta),
-                                                   reinterpret_cast<const GroupMeta*>(h->zmeta), seg_len, S, h->params,
-                                                   h->rowpart, h->Mcap,
-                                                   reinterpret_cast<unsigned char*>(h->rowpart + (int64_t)planes * 5 * h->Mcap),
-                                                   h->wgcount + h->wg_cap);
+    k_rowpass_cull<<<grid, kBlock, 0, h->stream>>>(h->z4.p, h->tgt4.p, reinterpret_cast<const GroupMeta*>(h->tmeta.p),
+                                                   reinterpret_cast<const GroupMeta*>(h->zmeta.p), seg_len, S, h->params,
+                                                   h->rowpart.p, h->Mcap,
+                                                   reinterpret_cast<unsigned char*>(h->rowpart.p + (int64_t)planes * 5 * h->Mcap),
+                                                   h->wgcount.p + h->wg_cap());
     h->wg_row = (int64_t)grid.x * grid.y;
     h->wg_row_pairs = 128.0 * kGroup;
     h->dense_pairs_row = 0.0;

@@ -436,23 +436,14 @@ int64_t queue_max_units(int64_t owned, int64_t streamed) {
 }
 
 static int ensure_queue(prg_cpd* h, SweepQueue& q, int64_t nblocks, int nchunk, int64_t max_units) {
-    if (nblocks > q.cap_blocks || nchunk > q.cap_chunk || max_units > q.cap_units) {
-        PRG_HIP(hipStreamSynchronize(h->stream));
-        for (void* p : {(void*)q.masks, (void*)q.chunk, (void*)q.units, (void*)q.ctrl, (void*)q.ucount})
-            if (p) (void)hipFree(p);
-        q = SweepQueue();
-        PRG_HIP(hipMalloc((void**)&q.masks, (size_t)nblocks * nchunk * (kQueueChunkGroups / 64) * sizeof(unsigned long long)));
-        PRG_HIP(hipMalloc((void**)&q.chunk, (size_t)nblocks * nchunk * sizeof(int2)));
-        PRG_HIP(hipMalloc((void**)&q.units, (size_t)max_units * sizeof(int2)));
-        PRG_HIP(hipMalloc((void**)&q.ctrl, 16 * sizeof(int)));
-        PRG_HIP(hipMalloc((void**)&q.ucount, (size_t)max_units * sizeof(unsigned)));
+    if (!q.fits(nblocks, nchunk, max_units)) PRG_HIP(hipStreamSynchronize(h->stream));  // (a sweep may still read the old arrays)
+    bool fresh = false;
+    PRG_HIP(q.size(nblocks, nchunk, max_units, &fresh));
+    if (fresh) {
         int init[16] = {0};
         init[1] = kQueueWorkgroups * (kSweepBlock / 64);
-        PRG_HIP(hipMemcpyAsync(q.ctrl, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+        PRG_HIP(hipMemcpyAsync(q.ctrl.p, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
-        q.cap_blocks = nblocks;
-        q.cap_chunk = nchunk;
-        q.cap_units = max_units;
     }
     return PRG_OK;
 }
@@ -472,8 +463,8 @@ static int build_queue(prg_cpd* h, SweepQueue& q, int64_t owned, int64_t streame
     dim3 grid((unsigned)nblocks, (unsigned)ceil_div(nchunk, kBuildWaves));
     k_queue_build<ROW><<<grid, kBuildWaves * 64, 0, h->stream>>>(
         reinterpret_cast<const GroupMeta*>(own_meta), reinterpret_cast<const GroupMeta*>(str_meta), (int)ngroups, nchunk, h->params,
-        (!ROW && use_seed) ? h->colmin + h->Ncap : nullptr, h->motion + ((h->estep_count - 1) & 1), kQueueTargetUnits, q_init, q.cap_soft,
-        q.masks, q.chunk, q.units, q.ctrl);
+        (!ROW && use_seed) ? h->colmin.p + h->Ncap : nullptr, h->motion.p + ((h->estep_count - 1) & 1), kQueueTargetUnits, q_init, q.cap_soft,
+        q.masks.p, q.chunk.p, q.units.p, q.ctrl.p);
     return PRG_OK;
 }
 
@@ -486,26 +477,26 @@ int prepare_queues(prg_cpd* h) {
 }
 
 int launch_colpass_queue(prg_cpd* h, bool use_seed, int q_init, bool resid) {
-    PRG_TRY(build_queue<false>(h, h->qcol, h->N, h->M, h->tmeta, h->zmeta, use_seed, q_init));
+    PRG_TRY(build_queue<false>(h, h->qcol, h->N, h->M, h->tmeta.p, h->zmeta.p, use_seed, q_init));
     SweepQueue& q = h->qcol;
     if (resid)
-        k_colpass_queue<true><<<kQueueWorkgroups, kBlock, 0, h->stream>>>(h->tgt4, h->z4, q.masks, q.nchunk * (kQueueChunkGroups / 64), q.units,
-                                                                         q.ctrl, q.cap_soft, h->params, reinterpret_cast<float2*>(h->colpart),
-                                                                         q.ucount);
+        k_colpass_queue<true><<<kQueueWorkgroups, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, q.masks.p, q.nchunk * (kQueueChunkGroups / 64), q.units.p,
+                                                                         q.ctrl.p, q.cap_soft, h->params, reinterpret_cast<float2*>(h->colpart.p),
+                                                                         q.ucount.p);
     else
-    k_colpass_queue<false><<<kQueueWorkgroups, kBlock, 0, h->stream>>>(h->tgt4, h->z4, q.masks, q.nchunk * (kQueueChunkGroups / 64), q.units,
-                                                               q.ctrl, q.cap_soft, h->params, reinterpret_cast<float2*>(h->colpart),
-                                                               q.ucount);
+    k_colpass_queue<false><<<kQueueWorkgroups, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, q.masks.p, q.nchunk * (kQueueChunkGroups / 64), q.units.p,
+                                                               q.ctrl.p, q.cap_soft, h->params, reinterpret_cast<float2*>(h->colpart.p),
+                                                               q.ucount.p);
     h->wg_col = -1;  // counted per unit (prg_cpd_pair_counts reads the unit counts and ucount)
     h->dense_pairs_col = 0.0;
     return PRG_OK;
 }
 
 int launch_rowpass_queue(prg_cpd* h, int q_init) {
-    PRG_TRY(build_queue<true>(h, h->qrow, h->M, h->N, h->zmeta, h->tmeta, false, q_init));
+    PRG_TRY(build_queue<true>(h, h->qrow, h->M, h->N, h->zmeta.p, h->tmeta.p, false, q_init));
     SweepQueue& q = h->qrow;
-    k_rowpass_queue<<<kQueueWorkgroups, kBlock, 0, h->stream>>>(h->z4, h->tgt4, q.masks, q.nchunk * (kQueueChunkGroups / 64), q.units,
-                                                               q.ctrl, q.cap_soft, h->params, h->rowpart, q.ucount);
+    k_rowpass_queue<<<kQueueWorkgroups, kBlock, 0, h->stream>>>(h->z4.p, h->tgt4.p, q.masks.p, q.nchunk * (kQueueChunkGroups / 64), q.units.p,
+                                                               q.ctrl.p, q.cap_soft, h->params, h->rowpart.p, q.ucount.p);
     h->wg_row = -1;
     h->dense_pairs_row = 0.0;
     return PRG_OK;

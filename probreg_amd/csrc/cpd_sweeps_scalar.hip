@@ -136,9 +136,9 @@ void launch_colpass_scalar(prg_cpd* h, int R, int S, int seg_len) {
     h->wg_col = 0;
     h->dense_pairs_col = (double)grid.x * (kBlock * R) * (double)S * seg_len;
     if (R == 2)
-        k_colpass<2, 8><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, seg_len, h->params, h->colpart, h->Ncap);
+        k_colpass<2, 8><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, seg_len, h->params, h->colpart.p, h->Ncap);
     else
-        k_colpass<4, 4><<<grid, kBlock, 0, h->stream>>>(h->tgt4, h->z4, seg_len, h->params, h->colpart, h->Ncap);
+        k_colpass<4, 4><<<grid, kBlock, 0, h->stream>>>(h->tgt4.p, h->z4.p, seg_len, h->params, h->colpart.p, h->Ncap);
 }
 
 void launch_rowpass_scalar(prg_cpd* h, int R, int S, int seg_len) {
@@ -146,9 +146,9 @@ void launch_rowpass_scalar(prg_cpd* h, int R, int S, int seg_len) {
     h->wg_row = 0;
     h->dense_pairs_row = (double)grid.x * (kBlock * R) * (double)S * seg_len;
     if (R == 2)
-        k_rowpass<2><<<grid, kBlock, 0, h->stream>>>(h->z4, h->tgt4, seg_len, h->params, h->rowpart, h->Mcap);
+        k_rowpass<2><<<grid, kBlock, 0, h->stream>>>(h->z4.p, h->tgt4.p, seg_len, h->params, h->rowpart.p, h->Mcap);
     else
-        k_rowpass<4><<<grid, kBlock, 0, h->stream>>>(h->z4, h->tgt4, seg_len, h->params, h->rowpart, h->Mcap);
+        k_rowpass<4><<<grid, kBlock, 0, h->stream>>>(h->z4.p, h->tgt4.p, seg_len, h->params, h->rowpart.p, h->Mcap);
 }
 
 }  // namespace prg

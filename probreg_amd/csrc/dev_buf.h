@@ -36,6 +36,11 @@ struct DevBuf {
         cap = count;
         return hipSuccess;
     }
+    // exchange the blocks of two buffers (a finished local buffer is handed to its owner this way; the other goes with the local)
+    void swap(DevBuf& o) {
+        T* const q = p; p = o.p; o.p = q;
+        const int64_t c = cap; cap = o.cap; o.cap = c;
+    }
     // cap >= need: nothing happens; else reset(max(need, want)).  *grown: the buffer was re-created (contents undefined)
     hipError_t ensure(int64_t need, int64_t want, bool* grown = nullptr) {
         if (grown) *grown = false;
@@ -63,7 +68,7 @@ struct HostBuf {
         p = nullptr;
         dev = nullptr;
     }
-    hipError_t ensure(int64_t count, unsigned flags) {
+    hipError_t ensure(int64_t count, unsigned flags = hipHostMallocDefault) {
         if (p) return hipSuccess;
         void* q = nullptr;
         hipError_t e = hipHostMalloc(&q, (size_t)count * sizeof(T), flags);

@@ -1,4 +1,4 @@
-// Host check of probreg_amd/csrc/dev_buf.h against a fake allocator (tests/test_dev_buf_host.py builds this with the host
+// Host check of probreg_amd/csrc/dev_buf.h and cpd_buffers.h (the CPD plan's buffer groups) against a fake allocator (tests/test_dev_buf_host.py builds this with the host
 // compiler under AddressSanitizer / UBSan and runs it; it is not linked against the HIP runtime).  The fakes sit on malloc /
 // free, count what is live and fail the k-th allocation on request, so a double free, a leak or a buffer that keeps a freed
 // pointer or a stale capacity shows either in the counters or in the sanitizer's report.
@@ -7,6 +7,7 @@
 
 #include <set>
 
+#include "../../probreg_amd/csrc/cpd_buffers.h"
 #include "../../probreg_amd/csrc/dev_buf.h"
 
 static std::set<void*> g_live;
@@ -58,6 +59,77 @@ static int g_failed = 0;
 
 template <class B>
 static bool empty(const B& b) { return b.p == nullptr && b.cap == 0; }
+
+static bool source_empty(const prg::SourceBuffers& s) {
+    return empty(s.src4) && empty(s.z4) && empty(s.rowacc) && empty(s.zmeta) && empty(s.rorig) && empty(s.zchunk) && s.Mcap == 0;
+}
+static bool target_empty(const prg::TargetBuffers& t) {
+    return empty(t.tgt4) && empty(t.pt1) && empty(t.tmeta) && empty(t.tchunk) && empty(t.corig) && empty(t.colmin) && t.Ncap == 0;
+}
+static bool queue_empty(const prg::SweepQueue& q) {
+    return empty(q.masks) && empty(q.chunk) && empty(q.units) && empty(q.ctrl) && empty(q.ucount) && q.cap_blocks == 0 &&
+           q.cap_chunk == 0 && q.cap_units == 0 && q.nblocks == 0 && q.nchunk == 0 && q.cap_soft == 0;
+}
+
+// The three all-or-nothing groups of the CPD plan: for every position k of a group's allocations, the k-th one fails on a group
+// that already holds buffers of another size.
+static void check_groups() {
+    const int64_t capA = 19456, capB = 20480;
+    for (int k = 1; k <= 6; ++k) {
+        prg::SourceBuffers s;
+        CHECK(s.size_source(capA) == hipSuccess && s.Mcap == capA && g_live.size() == 6);
+        CHECK(s.src4.cap == capA && s.z4.cap == capA && s.rowacc.cap == 4 * capA && s.zmeta.cap == capA / 32 * 8 &&
+              s.rorig.cap == capA / 512 + 4 && s.zchunk.cap == capA / 256 * 8);
+        const int allocs = g_allocs, frees = g_frees;
+        CHECK(s.size_source(capA) == hipSuccess && g_allocs == allocs && g_frees == frees);  // unchanged extents: nothing happens
+        g_fail_in = k;
+        CHECK(s.size_source(capB) == hipErrorOutOfMemory && source_empty(s));
+        CHECK(g_allocs == allocs + k - 1 && g_frees == g_allocs && g_live.empty() && g_bad_frees == 0);
+        CHECK(s.size_source(capB) == hipSuccess && s.Mcap == capB && g_live.size() == 6);  // ... and the group works again
+    }
+    CHECK(g_live.empty() && g_bad_frees == 0 && g_allocs == g_frees);
+    for (int k = 1; k <= 6; ++k) {
+        prg::TargetBuffers t;
+        bool fresh = false;
+        CHECK(t.size_target(capA, &fresh) == hipSuccess && fresh && t.Ncap == capA && g_live.size() == 6);
+        CHECK(t.tgt4.cap == capA && t.pt1.cap == capA && t.tmeta.cap == capA / 32 * 8 && t.tchunk.cap == capA / 256 * 8 &&
+              t.corig.cap == capA / 512 + 4 && t.colmin.cap == capA + capA / 32);
+        const int allocs = g_allocs, frees = g_frees;
+        CHECK(t.size_target(capA, &fresh) == hipSuccess && !fresh && g_allocs == allocs && g_frees == frees);
+        g_fail_in = k;
+        fresh = true;
+        CHECK(t.size_target(capB, &fresh) == hipErrorOutOfMemory && !fresh && target_empty(t));
+        CHECK(g_allocs == allocs + k - 1 && g_frees == g_allocs && g_live.empty() && g_bad_frees == 0);
+        CHECK(t.size_target(capB, &fresh) == hipSuccess && fresh && t.Ncap == capB && g_live.size() == 6);
+    }
+    CHECK(g_live.empty() && g_bad_frees == 0 && g_allocs == g_frees);
+    for (int k = 1; k <= 5; ++k) {
+        prg::SweepQueue q;
+        bool fresh = false;
+        CHECK(q.size(10, 3, 500, &fresh) == hipSuccess && fresh && g_live.size() == 5);
+        CHECK(q.masks.cap == 10 * 3 * 8 && q.chunk.cap == 10 * 3 && q.units.cap == 500 && q.ctrl.cap == 16 && q.ucount.cap == 500);
+        q.nblocks = 10, q.nchunk = 3, q.cap_soft = 100;  // (what a sweep built into it leaves)
+        const int allocs = g_allocs, frees = g_frees;
+        CHECK(q.size(10, 3, 500, &fresh) == hipSuccess && !fresh && g_allocs == allocs && g_frees == frees);
+        CHECK(q.size(4, 1, 20, &fresh) == hipSuccess && !fresh && g_allocs == allocs && q.cap_blocks == 10);  // smaller: kept
+        g_fail_in = k;
+        fresh = true;
+        CHECK(q.size(11, 3, 500, &fresh) == hipErrorOutOfMemory && !fresh && queue_empty(q));
+        CHECK(g_allocs == allocs + k - 1 && g_frees == g_allocs && g_live.empty() && g_bad_frees == 0);
+    }
+    // larger in any ONE of the three extents: all five arrays are new, at the extents asked for, and the caller is told
+    const int64_t grow[3][3] = {{11, 3, 500}, {10, 4, 500}, {10, 3, 501}};
+    for (const auto& g : grow) {
+        prg::SweepQueue q;
+        bool fresh = false;
+        CHECK(q.size(10, 3, 500, &fresh) == hipSuccess && fresh);
+        const int allocs = g_allocs, frees = g_frees;
+        CHECK(q.size(g[0], (int)g[1], g[2], &fresh) == hipSuccess && fresh && g_allocs == allocs + 5 && g_frees == frees + 5);
+        CHECK(q.cap_blocks == g[0] && q.cap_chunk == g[1] && q.cap_units == g[2] && q.masks.cap == g[0] * g[1] * 8 &&
+              q.chunk.cap == g[0] * g[1] && q.units.cap == g[2] && q.ucount.cap == g[2] && g_live.size() == 5);
+    }
+    CHECK(g_live.empty() && g_bad_frees == 0 && g_allocs == g_frees);
+}
 
 int main() {
     using prg::DevBuf;
@@ -115,6 +187,20 @@ int main() {
         CHECK(a.cap == 16 && empty(b) && empty(c) && g_live.size() == 1);
     }
     CHECK(g_live.empty() && g_bad_frees == 0);
+    {
+        // swap: a finished local buffer goes to its (empty) owner, the local leaves with nothing to free
+        DevBuf<double> owner;
+        {
+            DevBuf<double> local;
+            CHECK(local.reset(12) == hipSuccess);
+            double* const block = local.p;
+            owner.swap(local);
+            CHECK(owner.p == block && owner.cap == 12 && empty(local));
+        }
+        CHECK(g_live.size() == 1 && owner.cap == 12);
+    }
+    CHECK(g_live.empty() && g_bad_frees == 0);
+    check_groups();
     {
         HostBuf<double> pinned;
         CHECK(pinned.ensure(64, hipHostMallocDefault) == hipSuccess && pinned.p && !pinned.dev);

@@ -1,4 +1,7 @@
-"""The owning buffers of the lattice and the FilterReg plan (csrc/dev_buf.h) on the host: tests/host/dev_buf_check.cpp is
+"""The owning buffers of the lattice, the FilterReg plan and the CPD plan (csrc/dev_buf.h, and csrc/cpd_buffers.h: the CPD
+plan's all-or-nothing groups - every position of a failing allocation in the source group, the target group and a sweep queue
+leaves the group empty with extents 0, unchanged extents allocate nothing, a queue larger in any one extent is re-created as a
+whole and says so) on the host: tests/host/dev_buf_check.cpp is
 built with the host C++ compiler under AddressSanitizer and UBSan (their runtimes linked in statically) against a fake
 allocator, not linked against the HIP runtime, and run as a program of its own.  It checks that a failed allocation leaves a
 buffer empty with the old block freed exactly once, that ``ensure`` allocates only above the capacity and then ``max(need, want)``, and that nothing is live after
