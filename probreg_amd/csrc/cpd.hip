@@ -297,6 +297,8 @@ const CpdEnv& cpd_env() {
         auto is_zero = [](const char* name) { const char* v = getenv(name); return v && atoi(v) == 0; };
         e.mfma_seg = getenv("PRG_MFMA_SEG") ? atoi(getenv("PRG_MFMA_SEG")) : 0;
         e.fine_grid_off = is_zero("PRG_MFMA_FINE_GRID");
+        e.mfma_deal = getenv("PRG_MFMA_DEAL") ? (atoi(getenv("PRG_MFMA_DEAL")) != 0 ? 1 : 0) : -1;
+        e.mfma_deal_below = num("PRG_MFMA_DEAL_BELOW", 0.9);
         e.r_col = num("PRG_ENGINE_RCOL", 0.0);
         e.r_row = num("PRG_ENGINE_RROW", 0.0);
         e.fused_rcol_scale = num("PRG_FUSED_RCOL_SCALE", -1.0);

@@ -859,6 +859,12 @@ int cull_segments(int64_t lane_points, int64_t stream_len, int64_t cap) {
 // workgroup, which still needs its whole segment: rank 0 of 8 stayed at 0.31 ms from EM iteration 6 to 10 while one GPU went
 // 1.78 -> 0.87 ms (profiles/r4_shard_window.log).  With >= 3 rounds of shorter segments the slots even the load out.
 // 0: the default grid is already that deep (C1 on one GPU: 4.85 rounds), or PRG_MFMA_SEG pins the count.
+// Since then a culling column launch also deals its chunks interleaved (EngineDecision::deal, k_colpass_mfma): the depth of the grid
+// no longer decides how evenly a block's neighbourhood is spread over its workgroups, only how many workgroups share it.  One GPU at
+// C1 keeps its 19 segments.  (Pinned to 32 / 48 / 64 / 96 with the interleaved deal, iterations 6 - 12 of the window took 6.90 / 6.93 /
+// 7.09 / 7.28 ms against 7.06 - 7.15 at 19, profiles/mfma_deal_ab.log: a finer grid for one GPU's culling launches may be worth
+// 0.2 ms, measured before the cloud's last block culled - DESIGN.md 8.)  The rule for shards stands as measured in round 5; it has
+// not been re-measured with the new deal.
 int mfma_fine_segments(int64_t owned, int64_t streamed, int max_planes) {
     const CpdEnv& env = prg::cpd_env();
     if (env.mfma_seg || env.fine_grid_off) return env.mfma_seg;
@@ -914,6 +920,10 @@ double engine_leave_below(int64_t owned, int64_t streamed, double tau, double de
 // it/s at 1.0 / 1.4 / 2.0 / 2.8, profiles/r6_fused_lower_bound.log: the optimum is bracketed); target shards, whose ranks leave
 // the matrix cores at their own iteration, do better the later they leave: 8 ranks 4.10 -> 3.99 ms per window at 1.4 -> 1.0
 // (0.7: 4.02), 4 ranks 6.51 -> 6.42.  1.0 it is.
+// With culling launches dealt interleaved (and the cloud's last block culling too) the matrix cores are ahead of the owner sweep for
+// two more iterations of C1 (13: 0.29 against 0.37 ms, 14: 0.24 against 0.28 ms at 0.5), but the first owner sweep behind them costs
+// 0.015 - 0.025 ms more and the window does not resolve the rest: 949 / 946 / 949 / 941 it/s at 1.0 / 0.7 / 0.5 / 0.35, each +-1.5 %
+// (profiles/mfma_deal_ab.log).  1.0 stays.
 double fused_lower_bound_scale(bool allow_resid) {
     const double env = prg::cpd_env().fused_rcol_scale;
     return env > 0.0 ? env : allow_resid ? 1.0 : 0.5;
@@ -1104,6 +1114,8 @@ void fill_engine_args(prg_cpd* h, const EstepLayout& L, int slot, EngineArgs* ou
     ea.tsum = h->tsum_local;  // (prg_cpd_init_sums: sums of the LOCAL target; zeros if it was never called: not lean)
     ea.dim = h->D;
     ea.lean_factor = h->lean_factor >= 0.0 ? h->lean_factor : env.lean_factor >= 0.0 ? env.lean_factor : kLeanFactor;
+    ea.deal_mode = env.mfma_deal;
+    ea.deal_below = env.mfma_deal_below;
     ea.fused_allowed = L.allow_fused ? 1 : 0;
     ea.resid_allowed = L.allow_resid ? 1 : 0;
     ea.fused_factor = env.fused_factor >= 0.0 ? env.fused_factor : h->fused_factor;
@@ -1145,9 +1157,9 @@ int decide_engines(prg_cpd* h, const EstepLayout& L, int slot, bool cull_seed, h
     const bool pred = h->eng.pred_col != 0, pred_fused = L.allow_fused && h->eng.pred_fused != 0;
     const bool vector_grid = !L.use_queue && !L.use_owner;  // the vector pipe's column pass would be the grid of culled waves
     if (pred_fused)  // (the single sweep of a rigid iteration, if the previous E-step ran it)
-        prg::launch_fused_mfma(h, seg_col(), !h->have_colmin, false, ea.dev);
+        prg::launch_fused_mfma(h, seg_col(), !h->have_colmin, false, h->eng.deal != 0, ea.dev);
     else if (pred)  // (stream mode if the previous decision found nothing to skip: the dense regime)
-        prg::launch_colpass_mfma(h, seg_col(), !h->have_colmin, false, ea.dev, h->mfma_stream && h->eng.pred_fine == 0 && !h->eng.grid_fine);
+        prg::launch_colpass_mfma(h, seg_col(), !h->have_colmin, false, h->eng.deal != 0, ea.dev, h->mfma_stream && h->eng.pred_fine == 0 && !h->eng.grid_fine);
     else if (vector_grid)
         prg::launch_colpass_cull(h, L.SA, L.segA, cull_seed, ea.dev, L.allow_resid);
     // (pred == vector pipe with the work queue / the owner sweep: nothing goes out ahead - inside the dense regime that engine only
@@ -1167,6 +1179,7 @@ int decide_engines(prg_cpd* h, const EstepLayout& L, int slot, bool cull_seed, h
     d.fused = L.allow_fused && mb->fused != 0;
     if (!mb->dense) h->eng.mfma_off = true;
     // the previous matrix-core column pass skipped a tenth of its pairs: its masks are at work, cut the grid finer from here on
+    // (the same count, on the device, switches the chunk deal of this E-step's launch: EngineDecision::deal)
     h->eng.grid_fine = !d.first && (double)mb->r_col < 0.9 * (double)h->M;
     if (prg::cpd_env().debug_engine)
         fprintf(stderr, "[engine] sigma2 %.4e nk*ext2 %.1f pairs per owned point col %.0f (bound %.0f) row %.0f (bound %.0f) motion %.3e cmax %.3e nk*width %.1f "
@@ -1186,11 +1199,12 @@ int decide_engines(prg_cpd* h, const EstepLayout& L, int slot, bool cull_seed, h
     h->eng.pred_col = d.use_mfma ? 1 : 0;
     h->eng.pred_fine = d.fine ? 1 : 0;
     h->eng.pred_fused = d.fused ? 1 : 0;
+    h->eng.deal = mb->deal;
     if (!d.col_launched && d.fused) {  // (the guarded launch has returned at once; rare: the engine changes a few times per registration)
-        prg::launch_fused_mfma(h, seg_col(), d.first, d.fine, ea.dev);
+        prg::launch_fused_mfma(h, seg_col(), d.first, d.fine, h->eng.deal != 0, ea.dev);
         d.col_launched = true;
     } else if (!d.col_launched && d.use_mfma) {
-        prg::launch_colpass_mfma(h, seg_col(), d.first, d.fine, ea.dev, h->mfma_stream && !d.fine && !h->eng.grid_fine);
+        prg::launch_colpass_mfma(h, seg_col(), d.first, d.fine, h->eng.deal != 0, ea.dev, h->mfma_stream && !d.fine && !h->eng.grid_fine);
         d.col_launched = true;
     }
     *out = d;

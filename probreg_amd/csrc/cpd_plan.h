@@ -25,7 +25,8 @@ struct EngineDecision {
     int row_off;
     int lean;      // 1: the matrix-core row pass runs without its residual sums (sigma2 large enough, see k_chunk_meta_bbox)
     int fused;     // 1: ONE sweep for this E-step (k_colpass_mfma<FUSED>: rigid M-step moments from the column side, no row pass)
-    int pad_;      // (64-bit counters and doubles sit right behind the device copy of this struct)
+    int deal;      // 1: a grid-mode matrix-core column launch deals its chunks interleaved (chunk c to segment c mod S): the previous
+                   // sweep skipped part of its pairs.  (Also keeps the 64-bit counters behind the device copy of this struct aligned.)
 };
 // Device state of the engine decision: the decision itself, the matrix-core sweeps' tile counters and the LOCAL target's sums
 // (prg_cpd_init_sums keeps a copy here: the caller all-reduces the moments block it also writes them to).
@@ -34,7 +35,8 @@ struct EngineState {
     unsigned long long work[2];  // (128 x 16) tiles the matrix-core column / row pass evaluated (read + cleared by the decision)
     double tsum[4];              // (sum x, sum y, sum z, sum |x|^2) of the local target
 };
-static_assert(offsetof(EngineState, work) == sizeof(EngineDecision), "the 64-bit counters sit right behind the decision (pad_)");
+static_assert(offsetof(EngineState, work) == sizeof(EngineDecision) && sizeof(EngineDecision) % 8 == 0,
+              "the 64-bit counters sit right behind the decision");
 constexpr unsigned kMailboxFlags = hipHostMallocMapped | hipHostMallocCoherent;  // how the host's copy of the decision is allocated
 struct EngineArgs {  // host -> k_chunk_meta_bbox, by value
     double ext2;
@@ -51,6 +53,8 @@ struct EngineArgs {  // host -> k_chunk_meta_bbox, by value
     unsigned long long* work;     // [2] (128 x 16) tiles the matrix-core column / row pass of the PREVIOUS E-step evaluated
     float tbox[6];
     int slot, have_colmin, forced, reset;
+    int deal_mode;                // PRG_MFMA_DEAL: 0 / 1 pin the chunk deal of grid-mode matrix-core column launches, -1: by the count
+    double deal_below;            // ... interleaved once the previous sweep evaluated fewer than this many pairs per owned point
     int fused_allowed;            // this E-step feeds a rigid M-step and nothing else (prg_cpd_iterate / prg_cpd_set_moments_only)
     int resid_allowed;            // ... and below the matrix cores it would run as ONE residual-form sweep on the vector pipe (exact at any amplification)
     unsigned seq;
@@ -67,11 +71,16 @@ struct EngineSwitch {
     int pred_fine = 0;       // ... and whether that decision had the per-wave tile masks on (0: dense regime -> stream mode)
     int pred_fused = 0;      // ... the previous E-step ran the fused sweep
     bool grid_fine = false;  // the previous matrix-core column pass skipped >= 10 % of its pairs: launches are cut into >= 3 rounds of shorter segments
+    int deal = 0;            // ... and what the previous decision said about the chunk deal (EngineDecision::deal; the guard overrides it)
 };
 
 // Environment knobs of the CPD plan, read ONCE per process (prg::cpd_env(), cpd.hip).  Precedence everywhere: the plan's setter,
 // then the environment, then the built-in default.  They exist for A/B measurements (tools/) - the defaults are the product.
 //   PRG_MFMA_SEG          segments of every matrix-core launch (0: fill the chip once; pins mfma_fine_segments and the cost model)
+//   PRG_MFMA_DEAL         how a grid-mode matrix-core column launch (k_colpass_mfma) deals the streamed chunks to its S segments:
+//                         0: contiguous runs always, 1: interleaved (chunk c to segment c mod S) always, the all-pairs launches
+//                         included; unset: interleaved once the previous sweep skipped part of its pairs (profiles/mfma_deal_ab.log)
+//   PRG_MFMA_DEAL_BELOW   ... that is: evaluated fewer than this fraction of the streamed cloud per owned point (default 0.9)
 //   PRG_MFMA_FINE_GRID    =0: never cut a culling matrix-core launch finer (profiles/r4_shard_window.log is the case it fixes)
 //   PRG_ENGINE_RCOL/RROW  > 0: leave the matrix cores below this many evaluated pairs per owned point instead of the cost model's
 //                         bound (engine_leave_below; profiles/r3_engine_switch_*.log, r4_engine_switch_*.log)
@@ -90,6 +99,8 @@ struct EngineSwitch {
 struct CpdEnv {
     int mfma_seg = 0;
     bool fine_grid_off = false;
+    int mfma_deal = -1;
+    double mfma_deal_below = 0.9;
     double r_col = 0.0, r_row = 0.0;
     double fused_rcol_scale = -1.0;
     double lean_factor = -1.0, fused_factor = -1.0;

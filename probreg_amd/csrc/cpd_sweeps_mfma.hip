@@ -102,6 +102,31 @@ __device__ __forceinline__ bool wg_box(const BoxMeta* __restrict__ gmeta, int64_
     return hi[0] >= lo[0];
 }
 
+// ... of a workgroup whose 512 points end in pads (the cloud's last block): its whole groups as above, plus the real points of
+// the group the cloud ends in.  false: no real point at all.
+__device__ __forceinline__ bool wg_box_tail(const BoxMeta* __restrict__ gmeta, const float4* __restrict__ pts, int64_t first_point,
+                                            int64_t n_points, int lane, float (&lo)[3], float (&hi)[3]) {
+    wg_box(gmeta, first_point, n_points, lane, lo, hi);
+    const int64_t tail = n_points / 32 * 32;  // first point of the partly filled group, if there is one in this block
+    if (tail < n_points && tail >= first_point) {
+        const int64_t i = tail + (lane & 31);
+        const float4 p = pts[i < n_points ? i : tail];
+        const float c[3] = {p.x, p.y, p.z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float l = c[k], h = c[k];
+#pragma unroll
+            for (int sh = 1; sh < 32; sh <<= 1) {
+                l = fminf(l, __shfl_xor(l, sh, 64));
+                h = fmaxf(h, __shfl_xor(h, sh, 64));
+            }
+            lo[k] = fminf(lo[k], l);
+            hi[k] = fmaxf(hi[k], h);
+        }
+    }
+    return hi[0] >= lo[0];
+}
+
 // Box of the 128 points a wave owns (its 4 groups), wave-uniform in SGPRs.  false: one of the groups holds pads.
 struct WaveBox { float lo[3]; float hi[3]; };
 __device__ __forceinline__ bool wave_box(const BoxMeta* __restrict__ gmeta, int64_t first_point, int64_t n_points, int lane,
@@ -239,7 +264,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, FUSED
                                                          const double* __restrict__ params,
                                                          float2* __restrict__ colpart, int64_t ncap,
                                                          unsigned* __restrict__ wgcount, unsigned long long* __restrict__ work,
-                                                         int first, int fine,
+                                                         int first, int fine, int deal,
                                                          const EngineDecision* __restrict__ guard, const StreamCut sk,
                                                          float4* __restrict__ corig) {
     __shared__ __attribute__((aligned(16))) float stage[2][kChunkTiles * kTileFloats];
@@ -248,6 +273,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, FUSED
         const bool fused_wanted = guard->col == 1 && guard->fused == 1;
         if (FUSED ? !fused_wanted : (guard->col != 1 || fused_wanted)) return;
         fine = guard->fine;
+        deal = guard->deal;
     }
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const float kk = (float)(-kLog2e / (2.0 * params[13]));
@@ -262,22 +288,34 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, FUSED
         item = sk_item(unit, unit_end, blockIdx.x, (unsigned)nchunks, sk);
     } else {
         item.blk = (int)blockIdx.x;
-        item.c0 = (int)blockIdx.y * chunks_per_seg;
-        item.nc = (item.c0 + chunks_per_seg < nchunks ? item.c0 + chunks_per_seg : nchunks) - item.c0;
+        if (deal) {  // dealt interleaved: chunks seg, seg + S, seg + 2 S, ... - at most ceil(nchunks / S) <= chunks_per_seg of them
+            item.c0 = (int)blockIdx.y;
+            item.nc = item.c0 < nchunks ? (nchunks - item.c0 + (int)gridDim.y - 1) / (int)gridDim.y : 0;
+        } else {
+            item.c0 = (int)blockIdx.y * chunks_per_seg;
+            item.nc = (item.c0 + chunks_per_seg < nchunks ? item.c0 + chunks_per_seg : nchunks) - item.c0;
+        }
         item.plane = blockIdx.y;
         item.ends_block = false;
     }
     const int64_t n0wg = (int64_t)item.blk * kWgPoints, n0 = n0wg + wv * (16 * kOwn);
-    // the workgroup's patch: box (for the chunk test) and origin (its centre).  A workgroup that holds pads has no usable
-    // box: it evaluates everything and takes its first point as origin.
+    // the workgroup's patch: box (for the chunk test) and origin (its centre).  A workgroup that holds pads takes the box of its
+    // real points (the previous E-step's group minima leave pads out, k_colfinal*) and its first point as origin; a wave of its
+    // that holds pads tests no groups.
     float lo[3], hi[3];
     float4 o;
     float thr = INFINITY;    // skip a chunk when its box is farther than thr (squared) from the patch
     float thr_w = INFINITY;  // ... and a group of 32 streamed points when it is farther than thr_w from this wave's 128
     WaveBox wb;
     bool wave_cull = wave_box(tmeta, n0, n_total, lane, wb) && !first && fine;
-    if (n0wg + kWgPoints <= n_total && wg_box(tmeta, n0wg, n_total, lane, lo, hi)) {
-        o = make_float4(0.5f * (lo[0] + hi[0]), 0.5f * (lo[1] + hi[1]), 0.5f * (lo[2] + hi[2]), 0.f);
+    const bool whole = n0wg + kWgPoints <= n_total;
+    if (whole ? wg_box(tmeta, n0wg, n_total, lane, lo, hi) : wg_box_tail(tmeta, tgt4, n0wg, n_total, lane, lo, hi)) {
+        if (whole) {
+            o = make_float4(0.5f * (lo[0] + hi[0]), 0.5f * (lo[1] + hi[1]), 0.5f * (lo[2] + hi[2]), 0.f);
+        } else {
+            o = tgt4[n0wg];
+            o.w = 0.f;
+        }
         if (!first) {  // (first E-step of a registration: no minima to bound anything with)
             // as in k_colpass_cull: (sqrt(largest column minimum of the previous E-step) + source motion)^2 bounds this
             // E-step's minima from above; a chunk beyond that by 127 / |kk| adds < 2^-127 of any column's largest term
@@ -315,17 +353,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, FUSED
         if (FUSED) uxy[t] = uze[t] = (f32x2){0.f, 0.f};
     }
     unsigned tiles_done = 0;
-    const int64_t c0 = item.c0;
+    // the item's i-th chunk is c0 + i * cstride: a contiguous run, or every S-th chunk of the stream when a grid-mode launch is
+    // dealt interleaved (a culling block needs ONE neighbourhood of the kd-ordered stream: dealt this way all of its S
+    // workgroups share it instead of a few of them owning all of it)
+    const int c0 = item.c0, cstride = !sk_g && deal ? (int)gridDim.y : 1;
+    auto chunk_of = [&](int i) { return (int64_t)(c0 + i * cstride); };
     const int nc = item.nc;  // <= 64: one ballot's worth of chunks (grid mode: chunks_per_seg; stream mode: the run length)
-    // which chunks of the segment are needed: one box test per lane, one ballot (identical in all four waves)
-    const BoxMeta cm = zchunk[c0 + (lane < nc ? lane : nc - 1)];
+    // which chunks of the item are needed: one box test per lane, one ballot (identical in all four waves)
+    const BoxMeta cm = zchunk[chunk_of(lane < nc ? lane : nc > 0 ? nc - 1 : 0)];
     unsigned long long mask = __ballot(lane < nc && !(box_gap2(lo, hi, cm) > thr));
     if (mask) {
         int cur = __builtin_ctzll(mask);
         mask &= mask - 1;
-        float4 ra = z4[(c0 + cur) * kChunk + threadIdx.x];
+        float4 ra = z4[chunk_of(cur) * kChunk + threadIdx.x];
         ra.w = 0.f;  // (weighted sources do not take this path)
-        BoxMeta gm = zmeta[wave_cull ? (c0 + cur) * 8 + (lane & 7) : 0];  // the chunk's eight groups, for this wave's finer test
+        BoxMeta gm = zmeta[wave_cull ? chunk_of(cur) * 8 + (lane & 7) : 0];  // the chunk's eight groups, for this wave's finer test
         stage_point(stage[0], threadIdx.x, ra, o, kk);
         __syncthreads();
         for (int bsel = 0;; bsel ^= 1) {
@@ -337,9 +379,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, FUSED
             const int nxt = mask ? __builtin_ctzll(mask) : -1;
             mask &= mask - 1;
             if (nxt >= 0) {
-                ra = z4[(c0 + nxt) * kChunk + threadIdx.x];
+                ra = z4[chunk_of(nxt) * kChunk + threadIdx.x];
                 ra.w = 0.f;
-                if (wave_cull) gm = zmeta[(c0 + nxt) * 8 + (lane & 7)];
+                if (wave_cull) gm = zmeta[chunk_of(nxt) * 8 + (lane & 7)];
             }
             tiles_done += __popc(tmask);
             // software pipeline: the MFMA of the NEXT (tile, column tile) pair is issued before the current pair's
@@ -810,13 +852,16 @@ __global__ __launch_bounds__(kBlock) void k_chunk_meta_bbox(const BoxMeta* __res
     d.nk_ext2 = (float)(nk * eng.ext2); d.nk_width = (float)(nk * width); d.nk_far2 = (float)(nk * far2);
     d.r_col = r_col; d.r_row = r_row; d.row_off = row_off; d.lean = lean ? 1 : 0;
     d.fused = eng.fused_allowed && col && row && fused_ok ? 1 : 0;
+    // the chunk deal of a grid-mode column launch: contiguous runs while every pair is needed (the short last segment is what
+    // mfma_dense_makespan counts on), interleaved once the previous sweep's masks skipped part of them
+    d.deal = eng.deal_mode >= 0 ? eng.deal_mode : (!first && (double)r_col < eng.deal_below * eng.streamed_col ? 1 : 0);
     *eng.dev = d;
     // mailbox: payload first, sequence number last, both at system scope
     EngineDecision* hm = eng.host;
     hm->col = d.col; hm->first = d.first; hm->row = d.row; hm->fine = d.fine; hm->dense = d.dense;
     hm->sigma2 = d.sigma2; hm->motion = d.motion; hm->cmax = d.cmax;
     hm->nk_ext2 = d.nk_ext2; hm->nk_width = d.nk_width; hm->nk_far2 = d.nk_far2;
-    hm->r_col = d.r_col; hm->r_row = d.r_row; hm->row_off = d.row_off; hm->lean = d.lean; hm->fused = d.fused;
+    hm->r_col = d.r_col; hm->r_row = d.r_row; hm->row_off = d.row_off; hm->lean = d.lean; hm->fused = d.fused; hm->deal = d.deal;
     __threadfence_system();
     __hip_atomic_store(&hm->seq, d.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -966,7 +1011,7 @@ static StreamCut stream_cut(int planes, int64_t blocks, int64_t chunks) {
     return c;
 }
 
-void launch_colpass_mfma(prg_cpd* h, int S, bool first, bool fine, const EngineDecision* guard, bool stream) {
+void launch_colpass_mfma(prg_cpd* h, int S, bool first, bool fine, bool deal, const EngineDecision* guard, bool stream) {
     const int cps = mfma_chunks_per_seg(h->N, h->M, S);
     const int sp = stream ? mfma_stream_planes(h->N, h->M) : 0;
     const int64_t nblocks = ceil_div(h->N, kWgPoints);
@@ -979,7 +1024,7 @@ void launch_colpass_mfma(prg_cpd* h, int S, bool first, bool fine, const EngineD
                                                    reinterpret_cast<const BoxMeta*>(h->zmeta.p),
                                                    reinterpret_cast<const BoxMeta*>(h->zchunk.p), h->colmin.p, h->colmin.p + h->Ncap,
                                                    h->motion.p + ((h->estep_count - 1) & 1), cps, h->M, h->N, h->params,
-                                                   h->colpart.p, h->Ncap, h->wgcount.p, h->eng_work, first ? 1 : 0, fine ? 1 : 0, guard,
+                                                   h->colpart.p, h->Ncap, h->wgcount.p, h->eng_work, first ? 1 : 0, fine ? 1 : 0, deal ? 1 : 0, guard,
                                                    cut, nullptr);
     h->wg_col = nblocks * h->mfma_col_planes;  // (evaluated-tile counters: one per (plane, block))
     h->wg_col_pairs = 128.0 * 16.0;  // counted unit: one wave's 128 points x one 16-point tile
@@ -988,7 +1033,7 @@ void launch_colpass_mfma(prg_cpd* h, int S, bool first, bool fine, const EngineD
 
 // the single sweep of a rigid EM iteration (k_colpass_mfma<true>): grid mode, planes of 6 floats per column in h->colpart,
 // block origins in h->corig
-void launch_fused_mfma(prg_cpd* h, int S, bool first, bool fine, const EngineDecision* guard) {
+void launch_fused_mfma(prg_cpd* h, int S, bool first, bool fine, bool deal, const EngineDecision* guard) {
     const int cps = mfma_chunks_per_seg(h->N, h->M, S);
     const int64_t nblocks = ceil_div(h->N, kWgPoints);
     dim3 grid((unsigned)nblocks, (unsigned)ceil_div(ceil_div(h->M, kChunk), cps));
@@ -998,7 +1043,7 @@ void launch_fused_mfma(prg_cpd* h, int S, bool first, bool fine, const EngineDec
                                                          reinterpret_cast<const BoxMeta*>(h->zmeta.p),
                                                          reinterpret_cast<const BoxMeta*>(h->zchunk.p), h->colmin.p, h->colmin.p + h->Ncap,
                                                          h->motion.p + ((h->estep_count - 1) & 1), cps, h->M, h->N, h->params,
-                                                         h->colpart.p, h->Ncap, h->wgcount.p, h->eng_work, first ? 1 : 0, fine ? 1 : 0, guard,
+                                                         h->colpart.p, h->Ncap, h->wgcount.p, h->eng_work, first ? 1 : 0, fine ? 1 : 0, deal ? 1 : 0, guard,
                                                          none, h->corig.p);
     h->wg_col = nblocks * h->mfma_col_planes;
     h->wg_col_pairs = 128.0 * 16.0;
