@@ -678,6 +678,54 @@ int prg_fpfh_get_spfh(prg_fpfh* h, double* spfh_host);
 int prg_fpfh_fpfh(prg_fpfh* h);
 int prg_fpfh_get_fpfh(prg_fpfh* h, double* fpfh_host);
 
+/* ---- Global registration: feature matching and RANSAC pose search ----------------------------------------------------
+ * None of this is in the reference: its examples get a start pose from Open3D (compute_fpfh_feature, then
+ * registration_ransac_based_on_feature_matching).  These entry points restate that pipeline in fp64 on the device
+ * (csrc/global_reg.hip; the definition with every order of summation and every tie rule is DESIGN.md section 3.13).
+ * Two runs on the same input give byte-identical results (no floating-point atomics). */
+/* For every row of a (na x d float64, host or device) the row of b (nb x d) of least squared distance, accumulated over the
+ * d columns in ascending order with every operation rounded once; ties go to the smaller index.  1 <= d <= 64.  segments:
+ * pieces the streamed side is cut into (0: automatic; the result does not depend on it).  idx_out_hd na int32, d2_out_hd na
+ * float64.  Replaces: none in the reference; the correspondence search inside Open3D's
+ * registration_ransac_based_on_feature_matching in its examples.  Synchronises. */
+int prg_feature_match(int device, void* hip_stream, const double* a_hd, int64_t na, const double* b_hd, int64_t nb, int d,
+                      int segments, int* idx_out_hd, double* d2_out_hd);
+/* The same plus the sweep with the roles swapped: mutual_out_hd[a] = 1 iff a is also the best row of a for idx[a]
+ * (Open3D's mutual_filter).  Replaces: none in the reference (see prg_feature_match). */
+int prg_feature_match_mutual(int device, void* hip_stream, const double* a_hd, int64_t na, const double* b_hd, int64_t nb,
+                             int d, int segments, int* idx_out_hd, double* d2_out_hd, int* mutual_out_hd);
+typedef struct prg_ransac prg_ransac;
+/* One pose search on one device / stream.  Replaces: none in the reference; Open3D's
+ * registration_ransac_based_on_feature_matching in its examples (as every prg_ransac_* entry point below). */
+int prg_ransac_create(prg_ransac** out, int device, void* hip_stream);
+int prg_ransac_destroy(prg_ransac* h);
+/* The correspondences: source points p_hd and matched target points q_hd, C x 3 float64 each (host or device), C >= 3. */
+int prg_ransac_set_correspondences(prg_ransac* h, const double* p_hd, const double* q_hd, int64_t C);
+/* Hypotheses h_offset .. h_offset + H - 1 of the stream `seed`: hypothesis h draws three correspondences by splitmix64 on the
+ * counters 3h + 1 .. 3h + 3, is valid iff the indices are distinct, every edge passes Open3D's edge-length check with
+ * edge_similarity in [0, 1] and the source triangle is not degenerate, and then gets the Kabsch pose of its three pairs.
+ * Invalid draws are not redrawn.  Two calls that cover a range in pieces give what one call gives. */
+int prg_ransac_build(prg_ransac* h, uint64_t seed, uint64_t h_offset, int64_t H, double edge_similarity);
+/* The hypotheses: triples_host H x 3 int32 (built hypotheses only), pose_host H x 12 (rotation row-major, then the shift;
+ * zeros where invalid), valid_host H int32; each may be NULL. */
+int prg_ransac_get_hypotheses(prg_ransac* h, int* triples_host, double* pose_host, int* valid_host);
+/* Install explicit hypotheses instead of building them (the scoring stage on its own). */
+int prg_ransac_set_hypotheses(prg_ransac* h, const double* pose_host, const int* valid_host, int64_t H);
+/* Per valid hypothesis: the number of correspondences with |R p + t - q|^2 <= tau^2 and the sum of those squares in
+ * ascending order (segments of 1024 correspondences, segment sums added in ascending order).  The sweep runs over the valid hypotheses only (their indices are compacted
+ * first); waits for their number, then enqueues. */
+int prg_ransac_score(prg_ransac* h, double tau);
+/* counts_host H int32 (-1 for an invalid hypothesis), sums_host H float64 (0 there); each may be NULL. */
+int prg_ransac_get_scores(prg_ransac* h, int* counts_host, double* sums_host);
+/* The winner: largest count, then smallest sum, then smallest index; each pointer may be NULL.  PRG_ERR_STATE with a message
+ * when no hypothesis is valid. */
+int prg_ransac_best(prg_ransac* h, int64_t* index_host, int* count_host, double* sum_host, double* pose_host);
+/* `iters` refits from pose_io_host (12 doubles, overwritten with the result): Kabsch over the inliers of the current pose,
+ * sums in ascending order (runs of 64 correspondences, run sums added in ascending order); a pose with fewer than 3 inliers
+ * is kept.  Then count_host / sum_host / inlier_host (C int32 flags) at the final pose; each may be NULL.  Synchronises. */
+int prg_ransac_refine(prg_ransac* h, double tau, int iters, double* pose_io_host, int* count_host, double* sum_host,
+                      int* inlier_host);
+
 #ifdef __cplusplus
 }
 #endif

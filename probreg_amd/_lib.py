@@ -205,6 +205,18 @@ SIGNATURES = {
     "prg_fpfh_get_spfh": [_vp, _vp],
     "prg_fpfh_fpfh": [_vp],
     "prg_fpfh_get_fpfh": [_vp, _vp],
+    "prg_feature_match": [_i, _vp, _vp, _i64, _vp, _i64, _i, _i, _vp, _vp],
+    "prg_feature_match_mutual": [_i, _vp, _vp, _i64, _vp, _i64, _i, _i, _vp, _vp, _vp],
+    "prg_ransac_create": [_pp, _i, _vp],
+    "prg_ransac_destroy": [_vp],
+    "prg_ransac_set_correspondences": [_vp, _vp, _vp, _i64],
+    "prg_ransac_build": [_vp, _c.c_uint64, _c.c_uint64, _i64, _d],
+    "prg_ransac_get_hypotheses": [_vp, _vp, _vp, _vp],
+    "prg_ransac_set_hypotheses": [_vp, _vp, _vp, _i64],
+    "prg_ransac_score": [_vp, _d],
+    "prg_ransac_get_scores": [_vp, _vp, _vp],
+    "prg_ransac_best": [_vp, _c.POINTER(_i64), _c.POINTER(_i), _c.POINTER(_d), _vp],
+    "prg_ransac_refine": [_vp, _d, _i, _vp, _c.POINTER(_i), _c.POINTER(_d), _vp],
 }
 
 for _name, _args in SIGNATURES.items():
