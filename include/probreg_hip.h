@@ -726,6 +726,46 @@ int prg_ransac_best(prg_ransac* h, int64_t* index_host, int* count_host, double*
 int prg_ransac_refine(prg_ransac* h, double tau, int iters, double* pose_io_host, int* count_host, double* sum_host,
                       int* inlier_host);
 
+/* ---- Voxel down-sampling ------------------------------------------------------------------------------------------------
+ * None of this is in the reference: every 3-D example of it calls Open3D's voxel_down_sample(voxel_size) on both clouds
+ * before it registers (examples/utils.py: prepare_source_and_target_rigid_3d, prepare_source_and_target_nonrigid_3d).  These
+ * entry points restate PointCloud::VoxelDownSample in fp64 on the device (csrc/voxel.hip; the definition with the order of
+ * the voxels and of every sum is DESIGN.md section 3.14).  Two runs on the same input give byte-identical results (no
+ * floating-point atomics), whatever the launch geometry. */
+typedef struct prg_voxel prg_voxel;
+/* One down-sampling context on one device / stream; a plan can be run again with other data or another voxel size.
+ * Replaces: none in the reference; Open3D's voxel_down_sample in its examples (as every prg_voxel_* entry point below). */
+int prg_voxel_create(prg_voxel** out, int device, void* hip_stream);
+int prg_voxel_destroy(prg_voxel* h);
+/* The cloud (`pcd.points` of the examples): n x d float64, d = 2 or 3, finite, host or device, 1 <= n < 2^31; uploaded once.
+ * Drops the channels of an earlier cloud. */
+int prg_voxel_set_data(prg_voxel* h, const double* points_hd, int64_t n, int d);
+/* Per-point channels that are averaged like the coordinates (Open3D averages `pcd.normals` and `pcd.colors`): n x c float64,
+ * 0 <= c <= 67 - the caller puts normals and attributes side by side; c = 0 removes them. */
+int prg_voxel_set_channels(prg_voxel* h, const double* channels_hd, int c);
+/* voxel_down_sample(v): cells floor((p - (min - v / 2)) / v) per axis, voxels in ascending (c_x, c_y, c_z), the points of a
+ * voxel in ascending index, sums over pieces of 64 sorted positions (section 3.14).  v > 0 and finite.  PRG_ERR_INVALID,
+ * before anything is sorted, when an axis needs 2^21 cells or more (Open3D allows INT_MAX).  Waits twice (the box, the
+ * number of voxels). */
+int prg_voxel_run(prg_voxel* h, double v);
+/* The number of voxels V of the last run (len(result.points) in Open3D). */
+int prg_voxel_count(prg_voxel* h, int64_t* v_host);
+/* Open3D's result.points: V x d means.  And result.normals / result.colors: V x c channel means, not renormalised. */
+int prg_voxel_get_means(prg_voxel* h, double* means_host);
+int prg_voxel_get_channel_means(prg_voxel* h, double* means_host);
+/* Per voxel: the number of its points and the smallest original index among them, V int32 each (no counterpart in
+ * voxel_down_sample; Open3D's voxel_down_sample_and_trace reports the members). */
+int prg_voxel_get_counts(prg_voxel* h, int* counts_host);
+int prg_voxel_get_first(prg_voxel* h, int* first_host);
+/* Per input point the row of its voxel, n int32 (the first result of voxel_down_sample_and_trace, inverted). */
+int prg_voxel_get_inverse(prg_voxel* h, int* inverse_host);
+/* The stages of the last run, for tests and tools (no counterpart: Open3D keeps a hash map): the key c_x 2^42 + c_y 2^21 +
+ * c_z of every point (n uint64), the point at every position of the stably sorted sequence (n int32), and the voxel row of
+ * every sorted position (n int32). */
+int prg_voxel_get_keys(prg_voxel* h, uint64_t* keys_host);
+int prg_voxel_get_order(prg_voxel* h, int* order_host);
+int prg_voxel_get_rows(prg_voxel* h, int* rows_host);
+
 #ifdef __cplusplus
 }
 #endif

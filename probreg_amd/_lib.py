@@ -217,6 +217,20 @@ SIGNATURES = {
     "prg_ransac_get_scores": [_vp, _vp, _vp],
     "prg_ransac_best": [_vp, _c.POINTER(_i64), _c.POINTER(_i), _c.POINTER(_d), _vp],
     "prg_ransac_refine": [_vp, _d, _i, _vp, _c.POINTER(_i), _c.POINTER(_d), _vp],
+    "prg_voxel_create": [_pp, _i, _vp],
+    "prg_voxel_destroy": [_vp],
+    "prg_voxel_set_data": [_vp, _vp, _i64, _i],
+    "prg_voxel_set_channels": [_vp, _vp, _i],
+    "prg_voxel_run": [_vp, _d],
+    "prg_voxel_count": [_vp, _c.POINTER(_i64)],
+    "prg_voxel_get_means": [_vp, _vp],
+    "prg_voxel_get_channel_means": [_vp, _vp],
+    "prg_voxel_get_counts": [_vp, _vp],
+    "prg_voxel_get_first": [_vp, _vp],
+    "prg_voxel_get_inverse": [_vp, _vp],
+    "prg_voxel_get_keys": [_vp, _vp],
+    "prg_voxel_get_order": [_vp, _vp],
+    "prg_voxel_get_rows": [_vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <new>
 
+#include "block_scan.h"
 #include "dev_buf.h"
 #include "prg_common.h"
 #include "small_linalg.h"
@@ -324,34 +325,10 @@ __global__ __launch_bounds__(kBlock) void k_valid_count(const int* __restrict__ 
     if (threadIdx.x == 0) tile_count[blockIdx.x] = cnt[0];
 }
 
-// inclusive scan of one int per lane over a workgroup of N lanes
-template <int N>
-__device__ __forceinline__ void scan_inclusive(int* cnt) {
-    __syncthreads();
-    for (int off = 1; off < N; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? cnt[threadIdx.x - off] : 0;
-        __syncthreads();
-        cnt[threadIdx.x] += v;
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(kBestThreads) void k_tile_scan(const int* __restrict__ tile_count, int ntiles,
                                                             int* __restrict__ tile_start, int* __restrict__ n_out) {
     __shared__ int cnt[kBestThreads];
-    const int per = (ntiles + kBestThreads - 1) / kBestThreads;
-    const int b = (int)threadIdx.x * per;
-    const int e = b + per < ntiles ? b + per : ntiles;
-    int c = 0;
-    for (int t = b; t < e; ++t) c += tile_count[t];
-    cnt[threadIdx.x] = c;
-    scan_inclusive<kBestThreads>(cnt);
-    int pos = cnt[threadIdx.x] - c;
-    for (int t = b; t < e; ++t) {
-        tile_start[t] = pos;
-        pos += tile_count[t];
-    }
-    if (threadIdx.x == kBestThreads - 1) *n_out = cnt[threadIdx.x];
+    prg::tile_scan<kBestThreads>(tile_count, ntiles, tile_start, n_out, cnt);
 }
 
 __global__ __launch_bounds__(kBlock) void k_valid_write(const int* __restrict__ valid, int64_t H, const int* __restrict__ tile_start,
@@ -360,7 +337,7 @@ __global__ __launch_bounds__(kBlock) void k_valid_write(const int* __restrict__ 
     const int64_t b = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kCompactPer;
     const int c = count_run(valid, H, b);
     cnt[threadIdx.x] = c;
-    scan_inclusive<kBlock>(cnt);
+    prg::scan_inclusive<kBlock>(cnt);
     int pos = tile_start[blockIdx.x] + cnt[threadIdx.x] - c;  // < the number of valid hypotheses whenever one is written
 #pragma unroll
     for (int u = 0; u < kCompactPer; ++u)

@@ -1,6 +1,7 @@
-// Stable LSD radix sort of (vertex id, incidence) pairs for the order-preserving splat of the permutohedral lattice
-// (lattice.hip, lat_segments).  The sort itself is rocPRIM's device-wide radix sort - a plain library primitive, in a
-// translation unit of its own so that its templates are instantiated once.
+// Stable LSD radix sorts: of (vertex id, incidence) pairs for the order-preserving splat of the permutohedral lattice
+// (lattice.hip, lat_segments) and of (cell key, point) pairs for the voxel grid (voxel.hip).  The sort itself is rocPRIM's
+// device-wide radix sort - a plain library primitive, in a translation unit of its own so that its templates are
+// instantiated once.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "prg_common.h"
@@ -10,6 +11,15 @@ namespace prg {
 // Sorts n (key, value) pairs by the low `bits` bits of the key; equal keys keep their input order.  tmp == nullptr: only
 // *tmp_bytes is set (workspace query).
 int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
+                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream) {
+    size_t bytes = *tmp_bytes;
+    PRG_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, bits, stream));
+    *tmp_bytes = bytes;
+    return PRG_OK;
+}
+
+// The same for 64-bit keys (voxel.hip: the packed cell indices of the voxel grid).
+int sort_pairs_u64(void* tmp, size_t* tmp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const int* vals_in,
                    int* vals_out, unsigned n, unsigned bits, hipStream_t stream) {
     size_t bytes = *tmp_bytes;
     PRG_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, bits, stream));

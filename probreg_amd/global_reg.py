@@ -212,16 +212,26 @@ def registration_ransac(source, target, correspondences, max_distance, n_hypothe
     return GlobalResult(tf, cnt / float(corr.shape[0]), float(np.sqrt(sm / cnt)) if cnt else 0.0, np.nonzero(inl)[0])
 
 
-def registration_global(source, target, feature_fn=None, max_distance=0.05, mutual=True, **ransac_kwargs):
+def registration_global(source, target, feature_fn=None, max_distance=0.05, mutual=True, voxel_size=None, **ransac_kwargs):
     """Descriptors of both clouds (default ``fpfh.FPFH()``), their matches, then ``registration_ransac``.  ``source`` and
-    ``target`` are (n, 3) arrays or anything with ``.points``."""
+    ``target`` are (n, 3) arrays or anything with ``.points``.
+
+    ``voxel_size``: when given, both clouds go through ``preprocess.voxel_down_sample(cloud, voxel_size)`` first, and
+    descriptors, matching and the pose search run on the down-sampled clouds (FPFH stops being discriminative on dense
+    clouds).  ``fitness`` and ``inliers`` of the result then refer to the down-sampled clouds and their correspondences, not
+    to the rows of ``source`` and ``target``; the pose holds for the full clouds all the same."""
     src, tgt = _as_rows(source, "source", 3), _as_rows(target, "target", 3)
     _check_tau(max_distance)
     _single_process("registration_global")
+    device = ransac_kwargs.get("device")
+    if voxel_size is not None:
+        from . import preprocess
+        voxel_size = preprocess._check_voxel_size(voxel_size)
+        src = preprocess.voxel_down_sample(src, voxel_size, device=device).points
+        tgt = preprocess.voxel_down_sample(tgt, voxel_size, device=device).points
     if feature_fn is None:
         from . import fpfh
         feature_fn = fpfh.FPFH()
-    device = ransac_kwargs.get("device")
     pairs, _ = feature_matching(feature_fn(src), feature_fn(tgt), mutual, device=device)
     if pairs.shape[0] < 3:
         raise ValueError("fewer than 3 correspondences are left after matching (%d)" % pairs.shape[0])

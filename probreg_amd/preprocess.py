@@ -1,0 +1,222 @@
+"""Preprocessing of clouds: ``voxel_down_sample``, the first step of every 3-D example of the reference.
+
+The reference has no counterpart; its examples call Open3D's ``voxel_down_sample(voxel_size)`` on both clouds before they
+register (examples/utils.py: ``prepare_source_and_target_rigid_3d``, ``prepare_source_and_target_nonrigid_3d``).  Here it
+runs in ``libprobreg_hip.so`` (``prg_voxel_*``, csrc/voxel.hip) in fp64: a 64-bit cell key per point, a stable device radix
+sort and a segmented sum in a fixed order.  DESIGN.md section 3.14 is the definition; results are byte-identical from run
+to run.  Neither Open3D nor scikit-learn is imported.
+
+Differences from Open3D a caller can see (on purpose):
+  * The output voxels come in ascending cell order (x, then y, then z); Open3D's order is that of its hash map.
+  * An axis may span at most 2^21 cells (Open3D: INT_MAX); a larger grid raises ``ValueError``.
+  * Arrays go in and come out: ``VoxelDownSample(points, normals, attributes, counts, first, inverse)``.
+
+The result of a global registration on the down-sampled clouds starts a local one on the full clouds::
+
+    from probreg_amd import cpd, global_reg
+    res = global_reg.registration_global(source, target, max_distance=0.08, voxel_size=0.05)
+    tf = cpd.registration_cpd(source, target, tf_init_params=dict(rot=res.transformation.rot, t=res.transformation.t))
+"""
+import collections
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from . import dist as pdist
+from .engine import _current_device_and_stream
+
+MAX_ATTRIBUTES = 64
+MAX_CELLS = 1 << 21
+
+VoxelDownSample = collections.namedtuple("VoxelDownSample", ["points", "normals", "attributes", "counts", "first", "inverse"])
+
+
+def _as_cloud(points):
+    pts = np.ascontiguousarray(np.asarray(getattr(points, "points", points)), dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] not in (2, 3):
+        raise ValueError("points must be (n, 2) or (n, 3), got shape %s" % (pts.shape,))
+    if pts.shape[0] < 1:
+        raise ValueError("points must hold at least one point")
+    if not np.all(np.isfinite(pts)):
+        raise ValueError("points contains NaN or infinity")
+    return pts
+
+
+def _as_channel(a, name, n, cols, max_cols=None):
+    a = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != n:
+        raise ValueError("%s must have one row per point (%d), got shape %s" % (name, n, a.shape))
+    if cols is not None and a.shape[1] != cols:
+        raise ValueError("%s must be (%d, %d), got shape %s" % (name, n, cols, a.shape))
+    if max_cols is not None and not 1 <= a.shape[1] <= max_cols:
+        raise ValueError("%s must have 1 .. %d columns, got %d" % (name, max_cols, a.shape[1]))
+    if not np.all(np.isfinite(a)):
+        raise ValueError("%s contains NaN or infinity" % name)
+    return a
+
+
+def _check_voxel_size(v):
+    try:
+        size = float("nan") if isinstance(v, (bool, str, bytes)) else float(v)
+    except (TypeError, ValueError):
+        size = float("nan")
+    if not (np.isfinite(size) and size > 0.0):
+        raise ValueError("voxel_size must be a finite number > 0, got %r" % (v,))
+    return size
+
+
+def _single_process(what):
+    if pdist.world()[1] > 1:
+        raise NotImplementedError("%s: sharding over %d ranks is not supported; run it in one process."
+                                  % (what, pdist.world()[1]))
+
+
+class VoxelPlan(object):
+    """One ``prg_voxel`` handle: a cloud on one device / stream and the stages of the down-sampling.  A plan can be run
+    again with other data or another voxel size."""
+
+    def __init__(self, device=None):
+        _lib.require_gpu()
+        dev, st = _current_device_and_stream(device)
+        self.device = dev
+        self._h = ctypes.c_void_p()
+        _lib.check(_lib.lib.prg_voxel_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        self.n = 0
+        self.dim = 0
+        self.n_channels = 0
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            _lib.lib.prg_voxel_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+    def set_data(self, points):
+        """The cloud (n, 2) or (n, 3); the channels of an earlier cloud go."""
+        points = _as_cloud(points)
+        _lib.check(_lib.lib.prg_voxel_set_data(self._h, _lib.ptr(points), points.shape[0], points.shape[1]))
+        self.n, self.dim = points.shape
+        self.n_channels = 0
+
+    def set_channels(self, channels):
+        """Per-point channels (n, c) that are averaged like the coordinates; ``None`` removes them."""
+        if channels is None:
+            _lib.check(_lib.lib.prg_voxel_set_channels(self._h, None, 0))
+            self.n_channels = 0
+            return
+        channels = _as_channel(channels, "channels", self.n, None, MAX_ATTRIBUTES + 3)
+        _lib.check(_lib.lib.prg_voxel_set_channels(self._h, _lib.ptr(channels), channels.shape[1]))
+        self.n_channels = channels.shape[1]
+
+    def run(self, voxel_size):
+        _lib.check(_lib.lib.prg_voxel_run(self._h, _check_voxel_size(voxel_size)))
+
+    def count(self):
+        """The number of voxels V."""
+        v = ctypes.c_int64(0)
+        _lib.check(_lib.lib.prg_voxel_count(self._h, ctypes.byref(v)))
+        return int(v.value)
+
+    def _get(self, fn, shape, dtype):
+        out = np.empty(shape, dtype=dtype)
+        _lib.check(fn(self._h, _lib.ptr(out)))
+        return out
+
+    def keys(self):
+        """The cell key ``c_x 2^42 + c_y 2^21 + c_z`` of every point, (n,) uint64."""
+        self.count()
+        return self._get(_lib.lib.prg_voxel_get_keys, self.n, np.uint64)
+
+    def order(self):
+        """The point at every position of the sequence stably sorted by key, (n,) int32."""
+        self.count()
+        return self._get(_lib.lib.prg_voxel_get_order, self.n, np.int32)
+
+    def rows(self):
+        """The voxel row of every sorted position, (n,) int32."""
+        self.count()
+        return self._get(_lib.lib.prg_voxel_get_rows, self.n, np.int32)
+
+    def means(self):
+        """The mean point of every voxel, (V, d)."""
+        return self._get(_lib.lib.prg_voxel_get_means, (self.count(), self.dim), np.float64)
+
+    def channel_means(self):
+        """The mean channels of every voxel, (V, c)."""
+        return self._get(_lib.lib.prg_voxel_get_channel_means, (self.count(), self.n_channels), np.float64)
+
+    def counts(self):
+        return self._get(_lib.lib.prg_voxel_get_counts, self.count(), np.int32)
+
+    def first(self):
+        """The smallest original index in every voxel, (V,) int32."""
+        return self._get(_lib.lib.prg_voxel_get_first, self.count(), np.int32)
+
+    def inverse(self):
+        """The voxel row of every input point, (n,) int32."""
+        self.count()
+        return self._get(_lib.lib.prg_voxel_get_inverse, self.n, np.int32)
+
+
+def _unit_rows(a):
+    """Rows divided by their Euclidean norm (squares summed over the columns in ascending order); rows of norm 0 stay 0."""
+    sq = np.zeros(a.shape[0])
+    for k in range(a.shape[1]):
+        sq = sq + a[:, k] * a[:, k]
+    norm = np.sqrt(sq)
+    return a / np.where(norm > 0.0, norm, 1.0)[:, None]
+
+
+def voxel_down_sample(points, voxel_size, normals=None, attributes=None, unit_normals=False, device=None):
+    """One point per occupied cell of a grid of pitch ``voxel_size``: the mean of the cell's points (Open3D's
+    ``voxel_down_sample``).
+
+    Args:
+        points: (n, 2) or (n, 3) array, or anything with ``.points``.  An object's ``.normals`` is used when ``normals`` is
+            None and it has as many rows as the cloud.
+        voxel_size: pitch of the grid, > 0.  The grid starts at ``min - voxel_size / 2`` per axis, as Open3D's.
+        normals: (n, d), averaged like the points; the means are not renormalised (as in Open3D) unless ``unit_normals``.
+        attributes: (n, c) with 1 <= c <= 64 (colours, intensities, ...), averaged like the points.
+        unit_normals: divide every mean normal by its Euclidean norm (on the host); a mean of norm 0 stays 0.
+    Returns:
+        ``VoxelDownSample(points (V, d), normals (V, d) or None, attributes (V, c) or None, counts (V,) int32,
+        first (V,) int32: the smallest original index in the voxel, inverse (n,) int32: the voxel row of every input
+        point)``.  Voxels are in ascending cell order (x, then y, then z).
+    """
+    pts = _as_cloud(points)
+    n, d = pts.shape
+    v = _check_voxel_size(voxel_size)
+    if normals is None and not isinstance(points, np.ndarray) and hasattr(points, "points"):
+        own = getattr(points, "normals", None)
+        if own is not None and np.ndim(own) == 2 and np.shape(own)[0] == n:
+            normals = own
+    if normals is not None:
+        normals = _as_channel(normals, "normals", n, d)
+    if attributes is not None:
+        attributes = _as_channel(attributes, "attributes", n, None, MAX_ATTRIBUTES)
+    _single_process("voxel_down_sample")
+    channels = [a for a in (normals, attributes) if a is not None]
+    plan = VoxelPlan(device)
+    try:
+        plan.set_data(pts)
+        if channels:
+            plan.set_channels(np.concatenate(channels, axis=1))
+        plan.run(v)
+        means, counts, first, inverse = plan.means(), plan.counts(), plan.first(), plan.inverse()
+        cm = plan.channel_means() if channels else None
+    finally:
+        plan.close()
+    out_normals = out_attributes = None
+    if normals is not None:
+        out_normals = np.ascontiguousarray(cm[:, :d])
+        if unit_normals:
+            out_normals = _unit_rows(out_normals)
+    if attributes is not None:
+        out_attributes = np.ascontiguousarray(cm[:, cm.shape[1] - attributes.shape[1]:])
+    return VoxelDownSample(means, out_normals, out_attributes, counts, first, inverse)
