@@ -766,6 +766,53 @@ int prg_voxel_get_keys(prg_voxel* h, uint64_t* keys_host);
 int prg_voxel_get_order(prg_voxel* h, int* order_host);
 int prg_voxel_get_rows(prg_voxel* h, int* rows_host);
 
+/* ---- ICP: point-to-point and point-to-plane on a grid nearest-neighbour search ----------------------------------------------
+ * None of this is in the reference: examples/time_measurement.py and examples/icp_test.py call Open3D's registration_icp.
+ * These entry points restate it in fp64 on the device (csrc/icp.hip; the definition with the tie rule of the search, the
+ * order of every sum and the loop is DESIGN.md section 3.15).  Two runs on the same input give byte-identical results (no
+ * floating-point atomics), whatever the launch geometry and the grid.  kind: 0 point-to-point, 1 point-to-plane. */
+typedef struct prg_icp prg_icp;
+/* One ICP context on one device / stream; the pose starts as the identity.  Replaces: none in the reference; Open3D's
+ * registration_icp / evaluate_registration in its examples (as every prg_icp_* entry point below). */
+int prg_icp_create(prg_icp** out, int device, void* hip_stream);
+int prg_icp_destroy(prg_icp* h);
+/* The target: n x 3 float64, finite, host or device, 1 <= n < 2^31, and its normals (n x 3, or NULL: point-to-point only).
+ * Builds the search grid once (and coarser levels of it, for queries far from the cloud); cell_edge > 0 sets the finest cell
+ * edge, 0 lets the cloud choose it (a few distinct points per occupied cell); either is raised to the largest extent / 2^30, so
+ * that the levels always reach one on which the box is two cells wide.  The grid never changes a result.  Memory: about
+ * 64 n bytes plus 32 to 48 n bytes per level.  Synchronises. */
+int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normals_hd, int64_t n, double cell_edge);
+/* The finest grid of the target: its cell edge, cells per axis (3 int32), whether the cells are addressed directly (1) or
+ * hashed (0), and the number of levels (each four times coarser than the one below); each may be NULL.  For tools (no
+ * counterpart). */
+int prg_icp_get_grid(prg_icp* h, double* cell_edge_host, int* dims_host, int* dense_host, int* levels_host);
+/* The source: m x 3 float64, finite, host or device, 1 <= m < 2^31.  Synchronises. */
+int prg_icp_set_source(prg_icp* h, const double* points_hd, int64_t m);
+/* The pose q = R p + t as 12 doubles: R row-major, then t (registration_icp's `init`). */
+int prg_icp_set_pose(prg_icp* h, const double* pose_host);
+int prg_icp_get_pose(prg_icp* h, double* pose_host);
+/* For every moved source point the target index of the smallest (d2, index) among d2 <= r * r, -1 when there is none;
+ * r > 0, infinity allowed.  Enqueues only. */
+int prg_icp_search(prg_icp* h, double r);
+/* The matches of the last search: index_host m int32, d2_host m float64 (+inf where unmatched); each may be NULL. */
+int prg_icp_get_matches(prg_icp* h, int* index_host, double* d2_host);
+/* The raw ordered sums of a step over the current matches, out_host 32 doubles (unused ones 0): kind 0: count, sum d2,
+ * sum q (3), sum y (3), then the centred products (q - qm)_a (y - ym)_b (9, a major); kind 1: count, sum d2, the upper
+ * triangle of sum J J^T (21, row-major), sum J res (6).  Synchronises. */
+int prg_icp_sums(prg_icp* h, int kind, double* out_host);
+/* One step on the current matches: Kabsch (kind 0, at least 3 matches) or the 6 x 6 Cholesky solve (kind 1, at least 6 matches
+ * and no pivot <= 1e-12 max diag).  A missing step leaves the pose as it is and shows in the status.  Enqueues only. */
+int prg_icp_step(prg_icp* h, int kind);
+/* Open3D's loop from the current pose: evaluate, then up to max_iteration times step and evaluate; stops converged when
+ * fitness and rmse both change by less than rel_fitness / rel_rmse, and unconverged on a missing step.  The stop test runs
+ * on the device; the host looks at the flag every `chunk` iterations, and the result does not depend on chunk. */
+int prg_icp_iterate(prg_icp* h, int kind, double r, int max_iteration, double rel_fitness, double rel_rmse, int chunk);
+/* After prg_icp_iterate (or a single stage): pose_host 12 doubles, the matched count and the ordered sum of d2 of the last
+ * evaluation, the steps done, converged (0 / 1) and the status: 0 ok, 1 fewer than 3 matches (kind 0), 2 degenerate (kind 1:
+ * fewer than 6 matches or a pivot at the floor).  Each may be NULL.  Synchronises. */
+int prg_icp_get_state(prg_icp* h, double* pose_host, int64_t* count_host, double* sum_host, int* n_iter_host,
+                      int* converged_host, int* status_host);
+
 #ifdef __cplusplus
 }
 #endif

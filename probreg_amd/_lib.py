@@ -231,6 +231,19 @@ SIGNATURES = {
     "prg_voxel_get_keys": [_vp, _vp],
     "prg_voxel_get_order": [_vp, _vp],
     "prg_voxel_get_rows": [_vp, _vp],
+    "prg_icp_create": [_pp, _i, _vp],
+    "prg_icp_destroy": [_vp],
+    "prg_icp_set_target": [_vp, _vp, _vp, _i64, _d],
+    "prg_icp_get_grid": [_vp, _c.POINTER(_d), _vp, _c.POINTER(_i), _c.POINTER(_i)],
+    "prg_icp_set_source": [_vp, _vp, _i64],
+    "prg_icp_set_pose": [_vp, _vp],
+    "prg_icp_get_pose": [_vp, _vp],
+    "prg_icp_search": [_vp, _d],
+    "prg_icp_get_matches": [_vp, _vp, _vp],
+    "prg_icp_sums": [_vp, _i, _vp],
+    "prg_icp_step": [_vp, _i],
+    "prg_icp_iterate": [_vp, _i, _d, _i, _d, _d, _i],
+    "prg_icp_get_state": [_vp, _vp, _c.POINTER(_i64), _c.POINTER(_d), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)],
 }
 
 for _name, _args in SIGNATURES.items():

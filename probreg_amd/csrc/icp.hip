@@ -1,0 +1,895 @@
+// ICP: Open3D's registration_icp, point-to-point and point-to-plane, on a cross-cloud grid search.  All in
+// fp64 with fixed-order sums and no floating-point atomics.
+//
+//   grid     built once per target: cell key per point (row-major while the box has at most `table` cells, a multiplicative
+//            hash of the clamped cell coordinates otherwise - the scheme of fpfh.hip), stable radix sort, bucket bounds, points
+//            gathered in cell order with the original index in .w.  The cell edge comes from the cloud (a few points per
+//            occupied cell), never from the search radius.  Coarser levels (edge x kLevelStep each, until the box is one or
+//            two cells wide - always reached, see floor_edge) are built the same way: they carry a query that is far from the cloud
+//            over the empty space, and the last one bounds every search.
+//   search   one query per lane, queries in Morton order of their moved position.  Shells of cells of growing Chebyshev
+//            distance s around the query's clamped cell, kLevelShells of them per level and any number on the last level;
+//            after shell s of a level with edge h everything unvisited is farther than
+//            sqrt((s h)^2 + D^2), D the query's distance to the target's box.  The lane stops when its best d2 is strictly
+//            below that bound (shrunk by a hair), when the bound exceeds r, or when every cell that meets the cube of half
+//            edge min(r, sqrt(best d2)) around the query is visited (the shells are clipped to that cube).  The result is the
+//            minimum of (d2, index) over the visited points, which does not depend on the order of the visits: the grid
+//            does not show.
+//   sums     one lane per run of kRun consecutive source points (ascending m), a workgroup of kSlots lanes adds the runs in
+//            ascending order and finishes: count, sum of d2, the stop test, the centroids.
+//   step     one lane: Kabsch (kabsch_pose.h) or the 6 x 6 Cholesky solve, then the pose update.
+// The loop "search, sums, step" stays on the device: its state (pose, stop flag, counters) is a device array, every kernel
+// returns at once when the stop flag is set, and the host looks at the flag once per chunk of iterations.
+//
+// Every decision value is computed with separately rounded multiplications and additions (no contraction into FMAs), so that
+// a restatement in plain IEEE arithmetic takes the same branches and gets the same sums.
+#pragma clang fp contract(off)
+#include <math.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "dev_buf.h"
+#include "kabsch_pose.h"
+#include "prg_common.h"
+
+namespace prg {
+int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
+                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream);  // lattice_sort.hip
+}
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kRun = 64;                   // source points per run of the ordered sums (part of the definition)
+constexpr int kSlots = 32;                 // sums per run: 8 / 9 (point-to-point, two passes), 29 (point-to-plane)
+constexpr double kCellMax = 1073741823.0;  // cell coordinates are clamped to [0, 2^30)
+constexpr double kReach = 1.0 + 1.0e-12;   // the stop bound is a hair smaller than (s h)^2 + D^2: covers the rounding of d2
+constexpr unsigned kMinTableBits = 10, kMaxTableBits = 26;
+constexpr int kOrderBits = 10;             // per axis, of the Morton key that orders the queries
+constexpr double kPivot = 1.0e-12;         // a Cholesky pivot <= kPivot max diag(A) is degenerate (part of the definition)
+constexpr int kSample = 16384;             // points that choose the cell edge
+constexpr int kMaxLevels = 16;             // grids of growing cell edge: kLevelStep^(kMaxLevels - 1) = 2^kFloorBits
+constexpr int kFloorBits = 30;             // no cell edge is below the largest extent / 2^kFloorBits
+constexpr double kLevelStep = 4.0;         // edge of a level / edge of the level below
+constexpr int kLevelShells = 2;            // shells 0 .. kLevelShells of a level are walked before the next level takes over
+
+// state (doubles)
+constexpr int kStPose = 0, kStCentre = 12, kStStop = 18, kStCount = 19, kStSum = 20, kStFitness = 21, kStRmse = 22,
+              kStIter = 23, kStConverged = 24, kStStatus = 25, kStEvals = 26, kStSumsA = 32, kStSumsB = 64, kStLen = 96;
+constexpr int kStatusOk = 0, kStatusTooFew = 1, kStatusDegenerate = 2;
+constexpr int kPointToPoint = 0, kPointToPlane = 1;
+
+struct Grid {
+    double lo[3], hi[3];  // the target's box
+    double edge;
+    double slack;         // cells: what the rounding of (x - lo) / edge can move a cell difference by
+    int dim[3];
+    unsigned mask;        // table - 1
+    int dense;
+};
+
+struct Levels {
+    int count;
+    Grid g[kMaxLevels];
+    const double4* sp[kMaxLevels];  // the points in the cell order of the level, original index in .w
+    const int2* cells[kMaxLevels];  // (begin, end) of every bucket
+};
+
+// Monotone in x and clamped, so a difference of clamped cells never exceeds the difference of the unclamped ones.
+__host__ __device__ inline int cell_of(double x, double lo, double edge) {
+    double c = floor((x - lo) / edge);
+    c = c > 0.0 ? c : 0.0;
+    c = c < kCellMax ? c : kCellMax;
+    return (int)c;
+}
+
+__device__ inline unsigned cell_key(int cx, int cy, int cz, const Grid& g) {
+    if (g.dense) return ((unsigned)cz * (unsigned)g.dim[1] + (unsigned)cy) * (unsigned)g.dim[0] + (unsigned)cx;
+    // Teschner et al. 2003, "Optimized spatial hashing for collision detection of deformable objects"
+    const uint64_t h = ((uint64_t)cx * 73856093ull) ^ ((uint64_t)cy * 19349663ull) ^ ((uint64_t)cz * 83492791ull);
+    return (unsigned)(h ^ (h >> 29)) & g.mask;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- grid
+__global__ __launch_bounds__(kBlock) void k_icp_cell_keys(const double4* __restrict__ pts, int64_t n, Grid g,
+                                                          unsigned* __restrict__ keys, int* __restrict__ vals) {
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const double4 p = pts[t];
+    keys[t] = cell_key(cell_of(p.x, g.lo[0], g.edge), cell_of(p.y, g.lo[1], g.edge), cell_of(p.z, g.lo[2], g.edge), g);
+    vals[t] = (int)t;
+}
+
+// points (index in .w) in cell order, and (begin, end) of every bucket (zeroed before)
+__global__ __launch_bounds__(kBlock) void k_icp_cell_bounds(const double4* __restrict__ pts, const unsigned* __restrict__ skeys,
+                                                            const int* __restrict__ order, int64_t n, double4* __restrict__ sp,
+                                                            int2* __restrict__ cells) {
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const int i = order[t];
+    double4 p = pts[i];
+    p.w = (double)i;
+    sp[t] = p;
+    const unsigned key = skeys[t];
+    if (t == 0 || skeys[t - 1] != key) cells[key].x = (int)t;
+    if (t == n - 1 || skeys[t + 1] != key) cells[key].y = (int)(t + 1);
+}
+
+// q_a = ((R_a0 p_0 + R_a1 p_1) + R_a2 p_2) + t_a
+__device__ __forceinline__ void moved(const double (&m)[12], const double* __restrict__ p, double (&q)[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = ((m[3 * a] * p[0] + m[3 * a + 1] * p[1]) + m[3 * a + 2] * p[2]) + m[9 + a];
+}
+
+__device__ __forceinline__ unsigned spread10(unsigned v) {  // 10 bits -> every third bit
+    v &= 0x3ffu;
+    v = (v | v << 16) & 0x030000ffu;
+    v = (v | v << 8) & 0x0300f00fu;
+    v = (v | v << 4) & 0x030c30c3u;
+    v = (v | v << 2) & 0x09249249u;
+    return v;
+}
+
+// Morton key of the moved source point on a 2^kOrderBits grid over the target's box (clamped): orders the queries only
+__global__ __launch_bounds__(kBlock) void k_icp_query_keys(const double* __restrict__ src, int64_t M,
+                                                           const double* __restrict__ state, Grid g, double scale,
+                                                           unsigned* __restrict__ keys, int* __restrict__ vals) {
+    const int64_t m = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (m >= M) return;
+    double pose[12], q[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pose[k] = state[kStPose + k];
+    moved(pose, src + m * 3, q);
+    unsigned key = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        double c = floor((q[a] - g.lo[a]) * scale);
+        c = c > 0.0 ? c : 0.0;
+        c = c < (double)((1 << kOrderBits) - 1) ? c : (double)((1 << kOrderBits) - 1);
+        key |= spread10((unsigned)c) << a;
+    }
+    keys[m] = key;
+    vals[m] = (int)m;
+}
+
+// --------------------------------------------------------------------------------------------------------------- search
+struct Best {
+    double d2;
+    int idx;
+};
+
+// every point of the bucket of cell (cx, cy, cz): d2 = (dx dx + dy dy) + dz dz, minimum of (d2, index)
+__device__ __forceinline__ void visit(const double4* __restrict__ sp, const int2* __restrict__ cells, const Grid& g, int cx,
+                                      int cy, int cz, const double (&q)[3], Best& b) {
+    const int2 be = cells[cell_key(cx, cy, cz, g)];
+    for (int t = be.x; t < be.y; ++t) {
+        const double4 y = sp[t];
+        const double dx = y.x - q[0], dy = y.y - q[1], dz = y.z - q[2];
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        const int idx = (int)y.w;
+        if (b.idx < 0 || d2 < b.d2 || (d2 == b.d2 && idx < b.idx)) {
+            b.d2 = d2;
+            b.idx = idx;
+        }
+    }
+}
+
+// The shells of one level around the query, clipped to the cells that can hold a point at most rho = min(r, sqrt(best d2))
+// (a hair more) from it: cell_of is monotone, so a point in a cell below lo[a] has y_a < q_a - rho and d2 > rho^2.  Returns
+// true when the search is over: the best d2 is strictly below what anything unvisited can have, that bound exceeds r, or every
+// cell that matters has been visited.  false: `shells` shells were not enough (never on the last level).
+__device__ inline bool walk_level(const Grid& g, const double4* __restrict__ sp, const int2* __restrict__ cells,
+                                  const double (&q)[3], double box2, double r2, int shells, double& rho, Best& b) {
+    int c[3], lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = min(cell_of(q[a], g.lo[a], g.edge), g.dim[a] - 1);
+    for (int s = 0;; ++s) {
+        int smax = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double wide = rho + (fabs(q[a]) + rho) * 0x1p-50;  // the rounding of q_a -+ rho
+            lo[a] = min(cell_of(q[a] - wide, g.lo[a], g.edge), g.dim[a] - 1);
+            hi[a] = min(cell_of(q[a] + wide, g.lo[a], g.edge), g.dim[a] - 1);
+            smax = max(smax, max(c[a] - lo[a], hi[a] - c[a]));
+        }
+        if (s > smax) return true;
+        if (s > shells) return false;
+        const int z0 = max(c[2] - s, lo[2]), z1 = min(c[2] + s, hi[2]);
+        const int y0 = max(c[1] - s, lo[1]), y1 = min(c[1] + s, hi[1]);
+        const int xl = c[0] - s, xh = c[0] + s;
+        for (int z = z0; z <= z1; ++z) {
+            const bool zf = z - c[2] == s || c[2] - z == s;
+            for (int y = y0; y <= y1; ++y) {
+                if (zf || y - c[1] == s || c[1] - y == s) {  // a face of the shell: the whole row
+                    const int x1 = min(xh, hi[0]);
+                    for (int x = max(xl, lo[0]); x <= x1; ++x) visit(sp, cells, g, x, y, z, q, b);
+                } else {  // inside: the two ends of the row (s > 0 here)
+                    if (xl >= lo[0]) visit(sp, cells, g, xl, y, z, q, b);
+                    if (xh <= hi[0]) visit(sp, cells, g, xh, y, z, q, b);
+                }
+            }
+        }
+        // what is not visited yet lies in cells at Chebyshev distance > s of the clamped cell: farther than the bound
+        const double reach = fmax((double)s - g.slack, 0.0) * g.edge / kReach;
+        const double bound = reach * reach + box2;
+        if ((b.idx >= 0 && b.d2 < bound) || bound > r2) return true;
+        if (b.idx >= 0) rho = fmin(rho, sqrt(b.d2) * kReach);
+    }
+}
+
+// Lane l serves source point qorder[l] and writes by that index: out_idx (-1: nothing within r) and out_d2 (+inf then).
+// The level loop is uniform; a lane whose search is over sits the coarser levels out.
+__global__ __launch_bounds__(kBlock) void k_icp_search(Levels lv, const double* __restrict__ src,
+                                                       const int* __restrict__ qorder, int64_t M,
+                                                       const double* __restrict__ state, double r, double r2,
+                                                       int* __restrict__ out_idx, double* __restrict__ out_d2) {
+    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (l >= M || state[kStStop] != 0.0) return;
+    const int m = qorder[l];
+    double pose[12], q[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pose[k] = state[kStPose + k];
+    moved(pose, src + (int64_t)m * 3, q);
+    double box2 = 0.0;  // squared distance of the query to the target's box
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double lo = lv.g[0].lo[a], hi = lv.g[0].hi[a];
+        const double out = q[a] < lo ? lo - q[a] : (q[a] > hi ? q[a] - hi : 0.0);
+        box2 += out * out;
+    }
+    box2 = box2 / kReach;
+    Best b = {INFINITY, -1};
+    double rho = r * kReach;
+    bool done = false;
+    for (int k = 0; k < lv.count; ++k)
+        if (!done)
+            done = walk_level(lv.g[k], lv.sp[k], lv.cells[k], q, box2, r2,
+                              k + 1 < lv.count ? kLevelShells : 0x7fffffff, rho, b);
+    const bool hit = b.idx >= 0 && b.d2 <= r2;
+    out_idx[m] = hit ? b.idx : -1;
+    out_d2[m] = hit ? b.d2 : INFINITY;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- sums
+// One run of kRun source points per lane, ascending m, matched points only; the target point and its normal are read by
+// their index.  part: [run][kSlots].
+//   MODE 0  (count, sum d2, sum q (3), sum y (3))                          point-to-point, first pass
+//   MODE 1  (q - qm)_a (y - ym)_b, a major (9)                              point-to-point, second pass
+//   MODE 2  (count, sum d2, J J^T upper triangle row-major (21), J res (6)) point-to-plane; J = (q x n, n), res = n . (q - y)
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_icp_sums(const double* __restrict__ src, int64_t M, const double4* __restrict__ tp,
+                                                     const double4* __restrict__ tn, const int* __restrict__ idx,
+                                                     const double* __restrict__ d2, const double* __restrict__ state,
+                                                     double* __restrict__ part) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t m0 = r * kRun;
+    if (m0 >= M || state[kStStop] != 0.0) return;
+    const int64_t m1 = m0 + kRun < M ? m0 + kRun : M;
+    double pose[12], ctr[6], acc[kSlots];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pose[k] = state[kStPose + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ctr[k] = state[kStCentre + k];
+#pragma unroll
+    for (int k = 0; k < kSlots; ++k) acc[k] = 0.0;
+    for (int64_t m = m0; m < m1; ++m) {
+        const int t = idx[m];
+        if (t < 0) continue;
+        double q[3];
+        moved(pose, src + m * 3, q);
+        const double4 y4 = tp[t];
+        const double y[3] = {y4.x, y4.y, y4.z};
+        if (MODE == 0) {
+            acc[0] += 1.0;
+            acc[1] += d2[m];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                acc[2 + a] += q[a];
+                acc[5 + a] += y[a];
+            }
+        } else if (MODE == 1) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) acc[3 * a + b] += (q[a] - ctr[a]) * (y[b] - ctr[3 + b]);
+        } else {
+            const double4 n4 = tn[t];
+            const double n[3] = {n4.x, n4.y, n4.z};
+            const double res = (n[0] * (q[0] - y[0]) + n[1] * (q[1] - y[1])) + n[2] * (q[2] - y[2]);
+            const double J[6] = {q[1] * n[2] - q[2] * n[1], q[2] * n[0] - q[0] * n[2], q[0] * n[1] - q[1] * n[0],
+                                 n[0], n[1], n[2]};
+            acc[0] += 1.0;
+            acc[1] += d2[m];
+            int s = 2;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = i; j < 6; ++j) acc[s++] += J[i] * J[j];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc[23 + i] += J[i] * res;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kSlots; ++k) part[r * kSlots + k] = acc[k];
+}
+
+// One workgroup of kSlots lanes: lane k adds slot k of the runs in ascending run order and keeps the total in the state
+// (mode 1: kStSumsB, else kStSumsA).  Modes 0 and 2 are also the evaluation of the current pose: count, sum, fitness,
+// rmse - and, with `test`, Open3D's stop test against the evaluation before.  Mode 0 leaves the centroids for the second pass.
+__global__ __launch_bounds__(kSlots) void k_icp_finish(const double* __restrict__ part, int64_t nruns, int mode, int test,
+                                                       double m_total, double rel_fitness, double rel_rmse,
+                                                       double* __restrict__ state) {
+    __shared__ double tot[kSlots];
+    if (state[kStStop] != 0.0) return;
+    double acc = 0.0;
+    int64_t r = 0;
+    for (; r + 16 <= nruns; r += 16) {  // sixteen loads in flight; the additions stay in ascending run order
+        double v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = part[(r + u) * kSlots + threadIdx.x];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc += v[u];
+    }
+    for (; r < nruns; ++r) acc += part[r * kSlots + threadIdx.x];
+    tot[threadIdx.x] = acc;
+    state[(mode == 1 ? kStSumsB : kStSumsA) + threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0 || mode == 1) return;
+    const double cnt = tot[0];
+    const double fitness = cnt / m_total;
+    const double rmse = cnt > 0.0 ? sqrt(tot[1] / cnt) : 0.0;
+    if (test) {
+        if (state[kStEvals] > 0.0 && fabs(fitness - state[kStFitness]) < rel_fitness &&
+            fabs(rmse - state[kStRmse]) < rel_rmse) {
+            state[kStStop] = 1.0;
+            state[kStConverged] = 1.0;
+        }
+        state[kStEvals] += 1.0;
+    }
+    state[kStCount] = cnt;
+    state[kStSum] = tot[1];
+    state[kStFitness] = fitness;
+    state[kStRmse] = rmse;
+    if (mode == 0)
+        for (int k = 0; k < 6; ++k) state[kStCentre + k] = cnt > 0.0 ? tot[2 + k] / cnt : 0.0;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- step
+// x of A x = b by Cholesky, A from its upper triangle (row-major, 21), b = -g.  false: a pivot <= kPivot max diag(A).
+__device__ inline bool cholesky6(const double* __restrict__ a21, const double* __restrict__ g, double (&x)[6]) {
+    double L[6][6];
+    int s = 0;
+    double top = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+            L[j][i] = a21[s++];
+            if (i == j) top = fmax(top, L[i][i]);
+        }
+    const double floor_ = kPivot * top;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        double d = L[k][k];
+#pragma unroll
+        for (int j = 0; j < k; ++j) d -= L[k][j] * L[k][j];
+        if (!(d > floor_)) return false;
+        L[k][k] = sqrt(d);
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) {
+            double v = L[i][k];
+#pragma unroll
+            for (int j = 0; j < k; ++j) v -= L[i][j] * L[k][j];
+            L[i][k] = v / L[k][k];
+        }
+    }
+    double w[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double v = -g[i];
+#pragma unroll
+        for (int j = 0; j < i; ++j) v -= L[i][j] * w[j];
+        w[i] = v / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double v = w[i];
+#pragma unroll
+        for (int j = i + 1; j < 6; ++j) v -= L[j][i] * x[j];
+        x[i] = v / L[i][i];
+    }
+    return true;
+}
+
+// One lane.  The step from the sums in the state; a missing step (too few matches, degenerate) sets the stop flag and the
+// status and leaves the pose as it is.  R <- dR R, t <- dR t + dt.
+__global__ void k_icp_step(int kind, double* __restrict__ state) {
+    if (threadIdx.x != 0 || state[kStStop] != 0.0) return;
+    const double cnt = state[kStCount];
+    double d[12];
+    if (kind == kPointToPoint) {
+        if (cnt < 3.0) {
+            state[kStStop] = 1.0;
+            state[kStStatus] = (double)kStatusTooFew;
+            return;
+        }
+        double hm[3][3], qm[3], ym[3];
+        for (int a = 0; a < 3; ++a) {
+            qm[a] = state[kStCentre + a];
+            ym[a] = state[kStCentre + 3 + a];
+            for (int b = 0; b < 3; ++b) hm[a][b] = state[kStSumsB + 3 * a + b];
+        }
+        prg::kabsch_pose(hm, qm, ym, d);
+    } else {
+        double x[6];
+        if (cnt < 6.0 || !cholesky6(state + kStSumsA + 2, state + kStSumsA + 23, x)) {
+            state[kStStop] = 1.0;
+            state[kStStatus] = (double)kStatusDegenerate;
+            return;
+        }
+        // Open3D's TransformVector6dToMatrix4d: Rz(x2) Ry(x1) Rx(x0), shift (x3, x4, x5)
+        const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+        d[0] = cg * cb; d[1] = cg * sb * sa - sg * ca; d[2] = cg * sb * ca + sg * sa;
+        d[3] = sg * cb; d[4] = sg * sb * sa + cg * ca; d[5] = sg * sb * ca - cg * sa;
+        d[6] = -sb;     d[7] = cb * sa;                d[8] = cb * ca;
+        d[9] = x[3]; d[10] = x[4]; d[11] = x[5];
+    }
+    double old[12];
+    for (int k = 0; k < 12; ++k) old[k] = state[kStPose + k];
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b)
+            state[kStPose + 3 * a + b] = (d[3 * a] * old[b] + d[3 * a + 1] * old[3 + b]) + d[3 * a + 2] * old[6 + b];
+        state[kStPose + 9 + a] = ((d[3 * a] * old[9] + d[3 * a + 1] * old[10]) + d[3 * a + 2] * old[11]) + d[9 + a];
+    }
+    state[kStIter] += 1.0;
+}
+
+// clears the stop flag and the status; `loop`: the counters of a loop as well
+__global__ void k_icp_reset(int loop, double* __restrict__ state) {
+    if (threadIdx.x != 0) return;
+    state[kStStop] = 0.0;
+    state[kStStatus] = (double)kStatusOk;
+    if (loop) {
+        state[kStIter] = 0.0;
+        state[kStConverged] = 0.0;
+        state[kStEvals] = 0.0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ cell edge
+// The smallest edge a level may have: below it the cell coordinates of the box would pass kCellMax and pile up in the last
+// cell.  With it, kMaxLevels levels of step kLevelStep always reach a level on which the box is at most two cells wide.
+double floor_edge(double edge, const double* lo, const double* hi) {
+    const double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+    return std::max(edge, std::ldexp(ext, -kFloorBits));
+}
+
+// The edge at which the distinct points of a sample of the cloud are at most four to an occupied cell (halving from the
+// largest extent, kFloorBits times at the most), carried over to the whole cloud by the dimension the last halving shows:
+// occupied cells grow as edge^-D, D in [1, 3].  Copies of a point count once - no edge separates them - so a cloud that
+// repeats its points, or whose coordinates are quantised, stops where its distinct points are apart.
+double choose_edge(const std::vector<double>& raw, int64_t n, const double* lo, const double* hi) {
+    const double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+    if (!(ext > 0.0)) return 1.0;
+    const int64_t ns = std::min<int64_t>(n, kSample), stride = n / ns;
+    struct P3 {
+        double c[3];
+        bool operator<(const P3& o) const { return std::lexicographical_compare(c, c + 3, o.c, o.c + 3); }
+        bool operator==(const P3& o) const { return c[0] == o.c[0] && c[1] == o.c[1] && c[2] == o.c[2]; }
+    };
+    std::vector<P3> pts((size_t)ns);
+    for (int64_t i = 0; i < ns; ++i)
+        for (int a = 0; a < 3; ++a) pts[(size_t)i].c[a] = raw[(size_t)(i * stride) * 3 + a];
+    std::sort(pts.begin(), pts.end());
+    pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+    const double distinct = (double)pts.size();
+    std::vector<uint64_t> keys(pts.size());
+    double h = ext, before = 1.0, now = 1.0;
+    for (int level = 0; level < kFloorBits; ++level) {
+        for (size_t i = 0; i < pts.size(); ++i) {
+            uint64_t key = 0;
+            for (int a = 0; a < 3; ++a) {
+                const uint64_t c = (uint64_t)std::floor((pts[i].c[a] - lo[a]) / h);
+                key = (key ^ c) * 0x9E3779B97F4A7C15ull;
+                key ^= key >> 29;
+            }
+            keys[i] = key;
+        }
+        std::sort(keys.begin(), keys.end());
+        before = now;
+        now = (double)(std::unique(keys.begin(), keys.end()) - keys.begin());
+        if (distinct <= 4.0 * now) break;
+        h *= 0.5;
+    }
+    if (n > ns) {
+        const double dim = std::min(3.0, std::max(1.0, std::log2(now / before)));
+        h *= std::pow((double)ns / (double)n, 1.0 / dim);
+    }
+    return h;
+}
+
+}  // namespace
+
+struct prg_icp {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int64_t N = 0, M = 0;
+    bool have_normals = false, have_order = false, have_matches = false;
+    Levels lv;
+    prg::DevBuf<double4> tp, tn;          // target points and normals, padded to four doubles
+    prg::DevBuf<double4> sp[kMaxLevels];  // per level: the points in cell order, original index in .w
+    prg::DevBuf<int2> cells[kMaxLevels];  // per level, table entries: (begin, end)
+    prg::DevBuf<double> src;              // [M][3]
+    prg::DevBuf<unsigned> qkeys;          // 2 M: unsorted, sorted
+    prg::DevBuf<int> qvals;               // 2 M: iota, order
+    prg::DevBuf<char> sort_tmp;
+    prg::DevBuf<int> idx;                 // [M]
+    prg::DevBuf<double> d2;               // [M]
+    prg::DevBuf<double> part;             // [runs][kSlots]
+    prg::DevBuf<double> state;            // [kStLen]
+};
+
+namespace {
+
+int require_ready(prg_icp* h, const char* who, bool matches) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "%s: NULL argument", who);
+    PRG_REQUIRE(h->N >= 1, PRG_ERR_STATE, "%s: no target (prg_icp_set_target first)", who);
+    PRG_REQUIRE(h->M >= 1, PRG_ERR_STATE, "%s: no source (prg_icp_set_source first)", who);
+    PRG_REQUIRE(!matches || h->have_matches, PRG_ERR_STATE, "%s: no matches (prg_icp_search first)", who);
+    return PRG_OK;
+}
+
+int check_kind(const char* who, prg_icp* h, int kind) {
+    PRG_REQUIRE(kind == kPointToPoint || kind == kPointToPlane, PRG_ERR_INVALID,
+                "%s: kind must be 0 (point-to-point) or 1 (point-to-plane), got %d", who, kind);
+    PRG_REQUIRE(kind == kPointToPoint || h->have_normals, PRG_ERR_STATE,
+                "%s: point-to-plane needs the target's normals (prg_icp_set_target)", who);
+    return PRG_OK;
+}
+
+int ensure_state(prg_icp* h) {
+    if (h->state.p) return PRG_OK;
+    PRG_HIP(h->state.reset(kStLen));
+    double init[kStLen] = {0.0};
+    init[0] = init[4] = init[8] = 1.0;
+    PRG_HIP(hipMemcpy(h->state.p, init, sizeof(init), hipMemcpyHostToDevice));
+    return PRG_OK;
+}
+
+// the queries in Morton order of their position under the current pose (once per source / target)
+int ensure_order(prg_icp* h) {
+    if (h->have_order) return PRG_OK;
+    const int64_t M = h->M;
+    hipStream_t st = h->stream;
+    const Grid& g = h->lv.g[0];
+    const double ext = std::max(g.hi[0] - g.lo[0], std::max(g.hi[1] - g.lo[1], g.hi[2] - g.lo[2]));
+    const double scale = ext > 0.0 ? (double)(1 << kOrderBits) / ext : 0.0;
+    size_t need = 0;
+    PRG_TRY(prg::sort_pairs_u32(nullptr, &need, h->qkeys.p, h->qkeys.p + M, h->qvals.p, h->qvals.p + M, (unsigned)M,
+                                3 * kOrderBits, st));
+    PRG_HIP(h->sort_tmp.ensure((int64_t)need + 256, (int64_t)need + 256));
+    k_icp_query_keys<<<(unsigned)prg::ceil_div(M, kBlock), kBlock, 0, st>>>(h->src.p, M, h->state.p, g, scale, h->qkeys.p,
+                                                                            h->qvals.p);
+    PRG_HIP(hipGetLastError());
+    PRG_TRY(prg::sort_pairs_u32(h->sort_tmp.p, &need, h->qkeys.p, h->qkeys.p + M, h->qvals.p, h->qvals.p + M, (unsigned)M,
+                                3 * kOrderBits, st));
+    h->have_order = true;
+    return PRG_OK;
+}
+
+void enqueue_search(prg_icp* h, double r) {
+    k_icp_search<<<(unsigned)prg::ceil_div(h->M, kBlock), kBlock, 0, h->stream>>>(h->lv, h->src.p, h->qvals.p + h->M, h->M,
+                                                                                  h->state.p, r, r * r, h->idx.p, h->d2.p);
+}
+
+template <int MODE>
+void enqueue_sums(prg_icp* h, int test, double rel_fitness, double rel_rmse) {
+    const int64_t nruns = prg::ceil_div(h->M, kRun);
+    k_icp_sums<MODE><<<(unsigned)prg::ceil_div(nruns, kBlock), kBlock, 0, h->stream>>>(h->src.p, h->M, h->tp.p, h->tn.p, h->idx.p,
+                                                                                     h->d2.p, h->state.p, h->part.p);
+    k_icp_finish<<<1, kSlots, 0, h->stream>>>(h->part.p, nruns, MODE, test, (double)h->M, rel_fitness, rel_rmse, h->state.p);
+}
+
+// the sums of the current matches that evaluate the pose and start a step of `kind`
+void enqueue_eval(prg_icp* h, int kind, int test, double rel_fitness, double rel_rmse) {
+    if (kind == kPointToPoint) enqueue_sums<0>(h, test, rel_fitness, rel_rmse);
+    else enqueue_sums<2>(h, test, rel_fitness, rel_rmse);
+}
+
+// the step itself, from the sums of enqueue_eval
+void enqueue_step(prg_icp* h, int kind) {
+    if (kind == kPointToPoint) enqueue_sums<1>(h, 0, 0.0, 0.0);
+    k_icp_step<<<1, 1, 0, h->stream>>>(kind, h->state.p);
+}
+
+}  // namespace
+
+extern "C" {
+
+int prg_icp_create(prg_icp** out, int device, void* hip_stream) {
+    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_icp_create: out is NULL");
+    int count = 0;
+    PRG_HIP(hipGetDeviceCount(&count));
+    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_icp_create: device %d out of range", device);
+    prg_icp* h = new (std::nothrow) prg_icp();
+    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_icp_create: out of host memory");
+    h->device = device;
+    h->stream = (hipStream_t)hip_stream;
+    *out = h;
+    return PRG_OK;
+}
+
+int prg_icp_destroy(prg_icp* h) {
+    if (!h) return PRG_OK;
+    prg::DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+    return PRG_OK;
+}
+
+int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normals_hd, int64_t n, double cell_edge) {
+    PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_icp_set_target: NULL argument");
+    PRG_REQUIRE(n >= 1 && n < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_icp_set_target: need 1 <= n < 2^31 points, got %lld",
+                (long long)n);
+    PRG_REQUIRE(cell_edge >= 0.0 && std::isfinite(cell_edge), PRG_ERR_INVALID,
+                "prg_icp_set_target: cell_edge must be finite and >= 0 (0: chosen from the cloud), got %g", cell_edge);
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_target: hipSetDevice(%d) failed", h->device);
+    hipStream_t st = h->stream;
+    PRG_HIP(hipStreamSynchronize(st));
+    h->N = 0;
+    h->have_normals = h->have_order = h->have_matches = false;
+    std::vector<double> raw((size_t)n * 3), pad((size_t)n * 4, 0.0);
+    PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    double lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = raw[a];
+    for (int64_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const double v = raw[(size_t)i * 3 + a];
+            PRG_REQUIRE(std::isfinite(v), PRG_ERR_INVALID, "prg_icp_set_target: the points contain NaN or infinity");
+            pad[(size_t)i * 4 + a] = v;
+            lo[a] = std::min(lo[a], v);
+            hi[a] = std::max(hi[a], v);
+        }
+    const double edge0 = floor_edge(cell_edge > 0.0 ? cell_edge : choose_edge(raw, n, lo, hi), lo, hi);
+    unsigned bits = kMinTableBits;
+    while (bits < kMaxTableBits && ((int64_t)1 << bits) < 2 * n) ++bits;
+    const int64_t table = (int64_t)1 << bits;
+
+    PRG_HIP(h->tp.ensure(n, n));
+    PRG_HIP(hipMemcpy(h->tp.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (normals_hd) {
+        PRG_HIP(hipMemcpy(raw.data(), normals_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+        for (int64_t i = 0; i < n; ++i)
+            for (int a = 0; a < 3; ++a) {
+                PRG_REQUIRE(std::isfinite(raw[(size_t)i * 3 + a]), PRG_ERR_INVALID,
+                            "prg_icp_set_target: the normals contain NaN or infinity");
+                pad[(size_t)i * 4 + a] = raw[(size_t)i * 3 + a];
+            }
+        PRG_HIP(h->tn.ensure(n, n));
+        PRG_HIP(hipMemcpy(h->tn.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    prg::DevBuf<unsigned> keys;
+    prg::DevBuf<int> vals;
+    PRG_HIP(keys.reset(2 * n));
+    PRG_HIP(vals.reset(2 * n));
+    size_t need = 0;
+    PRG_TRY(prg::sort_pairs_u32(nullptr, &need, keys.p, keys.p + n, vals.p, vals.p + n, (unsigned)n, bits, st));
+    PRG_HIP(h->sort_tmp.ensure((int64_t)need + 256, (int64_t)need + 256));
+    const unsigned nb = (unsigned)prg::ceil_div(n, kBlock);
+    Levels& lv = h->lv;
+    lv.count = 0;
+    double edge = edge0;
+    for (int k = 0; k < kMaxLevels; ++k, edge *= kLevelStep) {  // ends at a level at most two cells wide (floor_edge)
+        Grid& gr = lv.g[k];
+        gr.edge = edge;
+        gr.mask = (unsigned)(table - 1);
+        double cells = 1.0;
+        int dim_max = 1;
+        for (int a = 0; a < 3; ++a) {
+            gr.lo[a] = lo[a];
+            gr.hi[a] = hi[a];
+            gr.dim[a] = cell_of(hi[a], lo[a], edge) + 1;
+            cells *= (double)gr.dim[a];
+            dim_max = std::max(dim_max, gr.dim[a]);
+        }
+        gr.dense = cells <= (double)table ? 1 : 0;
+        gr.slack = std::ldexp((double)dim_max + 1.0, -48);
+        const int64_t entries = gr.dense ? (int64_t)cells : table;  // a dense level needs one entry per cell, no more
+        PRG_HIP(h->sp[k].ensure(n, n));
+        PRG_HIP(h->cells[k].ensure(entries, entries));
+        k_icp_cell_keys<<<nb, kBlock, 0, st>>>(h->tp.p, n, gr, keys.p, vals.p);
+        PRG_HIP(hipGetLastError());
+        PRG_TRY(prg::sort_pairs_u32(h->sort_tmp.p, &need, keys.p, keys.p + n, vals.p, vals.p + n, (unsigned)n, bits, st));
+        PRG_HIP(hipMemsetAsync(h->cells[k].p, 0, (size_t)entries * sizeof(int2), st));
+        k_icp_cell_bounds<<<nb, kBlock, 0, st>>>(h->tp.p, keys.p + n, vals.p + n, n, h->sp[k].p, h->cells[k].p);
+        PRG_HIP(hipGetLastError());
+        lv.sp[k] = h->sp[k].p;
+        lv.cells[k] = h->cells[k].p;
+        lv.count = k + 1;
+        if (dim_max <= 2) break;  // at most 27 cells hold every point: whatever the query, this level ends its search
+    }
+    PRG_HIP(hipStreamSynchronize(st));  // the scratch goes away with this scope
+    PRG_TRY(ensure_state(h));
+    h->N = n;
+    h->have_normals = normals_hd != nullptr;
+    return PRG_OK;
+}
+
+int prg_icp_get_grid(prg_icp* h, double* cell_edge_host, int* dims_host, int* dense_host, int* levels_host) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_icp_get_grid: NULL argument");
+    PRG_REQUIRE(h->N >= 1, PRG_ERR_STATE, "prg_icp_get_grid: no target (prg_icp_set_target first)");
+    if (cell_edge_host) *cell_edge_host = h->lv.g[0].edge;
+    if (dims_host)
+        for (int a = 0; a < 3; ++a) dims_host[a] = h->lv.g[0].dim[a];
+    if (dense_host) *dense_host = h->lv.g[0].dense;
+    if (levels_host) *levels_host = h->lv.count;
+    return PRG_OK;
+}
+
+int prg_icp_set_source(prg_icp* h, const double* points_hd, int64_t m) {
+    PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_icp_set_source: NULL argument");
+    PRG_REQUIRE(m >= 1 && m < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_icp_set_source: need 1 <= m < 2^31 points, got %lld",
+                (long long)m);
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_source: hipSetDevice(%d) failed", h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    h->M = 0;
+    h->have_order = h->have_matches = false;
+    std::vector<double> raw((size_t)m * 3);
+    PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    for (size_t i = 0; i < raw.size(); ++i)
+        PRG_REQUIRE(std::isfinite(raw[i]), PRG_ERR_INVALID, "prg_icp_set_source: the points contain NaN or infinity");
+    const int64_t nruns = prg::ceil_div(m, kRun);
+    PRG_HIP(h->src.ensure(m * 3, m * 3));
+    PRG_HIP(h->qkeys.ensure(2 * m, 2 * m));
+    PRG_HIP(h->qvals.ensure(2 * m, 2 * m));
+    PRG_HIP(h->idx.ensure(m, m));
+    PRG_HIP(h->d2.ensure(m, m));
+    PRG_HIP(h->part.ensure(nruns * kSlots, nruns * kSlots));
+    PRG_HIP(hipMemcpy(h->src.p, raw.data(), raw.size() * sizeof(double), hipMemcpyHostToDevice));
+    PRG_TRY(ensure_state(h));
+    h->M = m;
+    return PRG_OK;
+}
+
+int prg_icp_set_pose(prg_icp* h, const double* pose_host) {
+    PRG_REQUIRE(h && pose_host, PRG_ERR_INVALID, "prg_icp_set_pose: NULL argument");
+    for (int k = 0; k < 12; ++k)
+        PRG_REQUIRE(std::isfinite(pose_host[k]), PRG_ERR_INVALID, "prg_icp_set_pose: the pose contains NaN or infinity");
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_pose: hipSetDevice(%d) failed", h->device);
+    PRG_TRY(ensure_state(h));
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(h->state.p + kStPose, pose_host, 12 * sizeof(double), hipMemcpyHostToDevice));
+    h->have_matches = false;
+    return PRG_OK;
+}
+
+int prg_icp_get_pose(prg_icp* h, double* pose_host) {
+    PRG_REQUIRE(h && pose_host, PRG_ERR_INVALID, "prg_icp_get_pose: NULL argument");
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_pose: hipSetDevice(%d) failed", h->device);
+    PRG_TRY(ensure_state(h));
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(pose_host, h->state.p + kStPose, 12 * sizeof(double), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+int prg_icp_search(prg_icp* h, double r) {
+    PRG_TRY(require_ready(h, "prg_icp_search", false));
+    PRG_REQUIRE(r > 0.0, PRG_ERR_INVALID, "prg_icp_search: r must be > 0 (infinity: no limit), got %g", r);
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_search: hipSetDevice(%d) failed", h->device);
+    PRG_TRY(ensure_order(h));
+    k_icp_reset<<<1, 1, 0, h->stream>>>(0, h->state.p);
+    enqueue_search(h, r);
+    PRG_HIP(hipGetLastError());
+    h->have_matches = true;
+    return PRG_OK;
+}
+
+int prg_icp_get_matches(prg_icp* h, int* index_host, double* d2_host) {
+    PRG_TRY(require_ready(h, "prg_icp_get_matches", true));
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_matches: hipSetDevice(%d) failed", h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    if (index_host) PRG_HIP(hipMemcpy(index_host, h->idx.p, (size_t)h->M * sizeof(int), hipMemcpyDeviceToHost));
+    if (d2_host) PRG_HIP(hipMemcpy(d2_host, h->d2.p, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+int prg_icp_sums(prg_icp* h, int kind, double* out_host) {
+    PRG_TRY(require_ready(h, "prg_icp_sums", true));
+    PRG_REQUIRE(out_host != nullptr, PRG_ERR_INVALID, "prg_icp_sums: NULL argument");
+    PRG_TRY(check_kind("prg_icp_sums", h, kind));
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_sums: hipSetDevice(%d) failed", h->device);
+    k_icp_reset<<<1, 1, 0, h->stream>>>(0, h->state.p);
+    enqueue_eval(h, kind, 0, 0.0, 0.0);
+    if (kind == kPointToPoint) enqueue_sums<1>(h, 0, 0.0, 0.0);
+    PRG_HIP(hipGetLastError());
+    double sums[2 * kSlots];
+    PRG_HIP(hipMemcpyAsync(sums, h->state.p + kStSumsA, sizeof(sums), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < kSlots; ++k) out_host[k] = 0.0;
+    if (kind == kPointToPoint) {
+        for (int k = 0; k < 8; ++k) out_host[k] = sums[k];
+        for (int k = 0; k < 9; ++k) out_host[8 + k] = sums[kSlots + k];
+    } else {
+        for (int k = 0; k < 29; ++k) out_host[k] = sums[k];
+    }
+    return PRG_OK;
+}
+
+int prg_icp_step(prg_icp* h, int kind) {
+    PRG_TRY(require_ready(h, "prg_icp_step", true));
+    PRG_TRY(check_kind("prg_icp_step", h, kind));
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_step: hipSetDevice(%d) failed", h->device);
+    k_icp_reset<<<1, 1, 0, h->stream>>>(1, h->state.p);
+    enqueue_eval(h, kind, 0, 0.0, 0.0);
+    enqueue_step(h, kind);
+    PRG_HIP(hipGetLastError());
+    h->have_matches = false;  // they belong to the pose before the step
+    return PRG_OK;
+}
+
+int prg_icp_iterate(prg_icp* h, int kind, double r, int max_iteration, double rel_fitness, double rel_rmse, int chunk) {
+    PRG_TRY(require_ready(h, "prg_icp_iterate", false));
+    PRG_TRY(check_kind("prg_icp_iterate", h, kind));
+    PRG_REQUIRE(r > 0.0, PRG_ERR_INVALID, "prg_icp_iterate: r must be > 0 (infinity: no limit), got %g", r);
+    PRG_REQUIRE(max_iteration >= 0 && max_iteration <= 1000000, PRG_ERR_INVALID,
+                "prg_icp_iterate: max_iteration must lie in 0 .. 1000000, got %d", max_iteration);
+    PRG_REQUIRE(std::isfinite(rel_fitness) && std::isfinite(rel_rmse), PRG_ERR_INVALID,
+                "prg_icp_iterate: relative_fitness and relative_rmse must be finite");
+    PRG_REQUIRE(chunk >= 1, PRG_ERR_INVALID, "prg_icp_iterate: chunk must be >= 1, got %d", chunk);
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_iterate: hipSetDevice(%d) failed", h->device);
+    hipStream_t st = h->stream;
+    PRG_TRY(ensure_order(h));
+    k_icp_reset<<<1, 1, 0, st>>>(1, h->state.p);
+    enqueue_search(h, r);
+    enqueue_eval(h, kind, 1, rel_fitness, rel_rmse);
+    PRG_HIP(hipGetLastError());
+    h->have_matches = true;
+    for (int done = 0; done < max_iteration;) {
+        const int c = std::min(chunk, max_iteration - done);
+        for (int i = 0; i < c; ++i) {
+            enqueue_step(h, kind);
+            enqueue_search(h, r);
+            enqueue_eval(h, kind, 1, rel_fitness, rel_rmse);
+        }
+        PRG_HIP(hipGetLastError());
+        done += c;
+        double stop = 0.0;
+        PRG_HIP(hipMemcpyAsync(&stop, h->state.p + kStStop, sizeof(double), hipMemcpyDeviceToHost, st));
+        PRG_HIP(hipStreamSynchronize(st));
+        if (stop != 0.0) break;
+    }
+    return PRG_OK;
+}
+
+int prg_icp_get_state(prg_icp* h, double* pose_host, int64_t* count_host, double* sum_host, int* n_iter_host,
+                      int* converged_host, int* status_host) {
+    PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_icp_get_state: NULL argument");
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_state: hipSetDevice(%d) failed", h->device);
+    PRG_TRY(ensure_state(h));
+    double s[kStLen];
+    PRG_HIP(hipMemcpyAsync(s, h->state.p, sizeof(s), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    if (pose_host)
+        for (int k = 0; k < 12; ++k) pose_host[k] = s[kStPose + k];
+    if (count_host) *count_host = (int64_t)s[kStCount];
+    if (sum_host) *sum_host = s[kStSum];
+    if (n_iter_host) *n_iter_host = (int)s[kStIter];
+    if (converged_host) *converged_host = (int)s[kStConverged];
+    if (status_host) *status_host = (int)s[kStStatus];
+    return PRG_OK;
+}
+
+}  // extern "C"
