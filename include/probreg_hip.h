@@ -770,7 +770,8 @@ int prg_voxel_get_rows(prg_voxel* h, int* rows_host);
  * None of this is in the reference: examples/time_measurement.py and examples/icp_test.py call Open3D's registration_icp.
  * These entry points restate it in fp64 on the device (csrc/icp.hip; the definition with the tie rule of the search, the
  * order of every sum and the loop is DESIGN.md section 3.15).  Two runs on the same input give byte-identical results (no
- * floating-point atomics), whatever the launch geometry and the grid.  kind: 0 point-to-point, 1 point-to-plane. */
+ * floating-point atomics), whatever the launch geometry and the grid.  kind: 0 point-to-point, 1 point-to-plane, 2 generalized
+ * (needs covariances, see the end of this section). */
 typedef struct prg_icp prg_icp;
 /* One ICP context on one device / stream; the pose starts as the identity.  Replaces: none in the reference; Open3D's
  * registration_icp / evaluate_registration in its examples (as every prg_icp_* entry point below). */
@@ -812,6 +813,23 @@ int prg_icp_iterate(prg_icp* h, int kind, double r, int max_iteration, double re
  * fewer than 6 matches or a pivot at the floor).  Each may be NULL.  Synchronises. */
 int prg_icp_get_state(prg_icp* h, double* pose_host, int64_t* count_host, double* sum_host, int* n_iter_host,
                       int* converged_host, int* status_host);
+/* ---- Generalized ICP (plane-to-plane; Segal et al., Open3D's registration_generalized_icp): kind 2 of prg_icp_sums,
+ * prg_icp_step and prg_icp_iterate, on the same search, ordered sums, Cholesky step and loop.  Every
+ * point of both clouds carries a symmetric positive-definite 3 x 3 covariance, 6 doubles (xx, xy, xz, yy, yz, zz); a matched
+ * pair is weighted by the inverse of C_target + R C_source R^T.  prg_icp_sums then gives: count, sum d2, the upper triangle of
+ * sum J^T P J (21), sum J^T P d (6) and, in slot 29, the objective sum d^T P d.  Fitness, rmse and the stop test stay
+ * Euclidean.  Kind 2 without both sets of covariances is PRG_ERR_STATE.  which: 0 source, 1 target; the cloud must be set, n
+ * is its number of points, and setting the cloud again drops its covariances.  None of this is in the reference. */
+/* Explicit covariances, n x 6 float64, host or device: finite, and positive definite by the pivot rule of the step (no
+ * Cholesky pivot <= 1e-12 max diag).  Replaces: the `covariances` of the clouds handed to registration_generalized_icp.
+ * Synchronises. */
+int prg_icp_set_covariances(prg_icp* h, int which, const double* cov_hd, int64_t n);
+/* Covariances I - (1 - epsilon) u u^T from normals (n x 3 float64, host or device, every norm finite and > 0; u = n / |n|),
+ * 0 < epsilon <= 1: Open3D's R diag(epsilon, 1, 1) R^T in closed form, independent of the sign of the normal.  Computed on the
+ * device.  Synchronises. */
+int prg_icp_set_covariances_from_normals(prg_icp* h, int which, const double* normals_hd, int64_t n, double epsilon);
+/* The covariances of a cloud as they are stored, n x 6 float64 to the host.  Synchronises. */
+int prg_icp_get_covariances(prg_icp* h, int which, double* cov_host);
 
 #ifdef __cplusplus
 }

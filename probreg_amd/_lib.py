@@ -244,6 +244,9 @@ SIGNATURES = {
     "prg_icp_step": [_vp, _i],
     "prg_icp_iterate": [_vp, _i, _d, _i, _d, _d, _i],
     "prg_icp_get_state": [_vp, _vp, _c.POINTER(_i64), _c.POINTER(_d), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)],
+    "prg_icp_set_covariances": [_vp, _i, _vp, _i64],
+    "prg_icp_set_covariances_from_normals": [_vp, _i, _vp, _i64, _d],
+    "prg_icp_get_covariances": [_vp, _i, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

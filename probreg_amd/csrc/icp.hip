@@ -1,5 +1,6 @@
-// ICP: Open3D's registration_icp, point-to-point and point-to-plane, on a cross-cloud grid search.  All in
-// fp64 with fixed-order sums and no floating-point atomics.
+// ICP: Open3D's registration_icp, point-to-point and point-to-plane, on a cross-cloud grid search, and
+// generalized ICP (plane-to-plane) on the same search, sums and loop.  All in fp64 with fixed-order sums and
+// no floating-point atomics.
 //
 //   grid     built once per target: cell key per point (row-major while the box has at most `table` cells, a multiplicative
 //            hash of the clamped cell coordinates otherwise - the scheme of fpfh.hip), stable radix sort, bucket bounds, points
@@ -18,6 +19,8 @@
 //   sums     one lane per run of kRun consecutive source points (ascending m), a workgroup of kSlots lanes adds the runs in
 //            ascending order and finishes: count, sum of d2, the stop test, the centroids.
 //   step     one lane: Kabsch (kabsch_pose.h) or the 6 x 6 Cholesky solve, then the pose update.
+//   gicp     a covariance per point (6 doubles, given or from a unit normal in closed form); per matched pair the 3 x 3
+//            M = C_target + R C_source R^T is inverted by its adjugate and weights the pair's 6 x 6 system (MODE 3 of the sums).
 // The loop "search, sums, step" stays on the device: its state (pose, stop flag, counters) is a device array, every kernel
 // returns at once when the stop flag is set, and the host looks at the flag once per chunk of iterations.
 //
@@ -44,7 +47,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kRun = 64;                   // source points per run of the ordered sums (part of the definition)
-constexpr int kSlots = 32;                 // sums per run: 8 / 9 (point-to-point, two passes), 29 (point-to-plane)
+constexpr int kSlots = 32;                 // sums per run: 8 / 9 (point-to-point, two passes), 29 (point-to-plane), 30 (generalized)
 constexpr double kCellMax = 1073741823.0;  // cell coordinates are clamped to [0, 2^30)
 constexpr double kReach = 1.0 + 1.0e-12;   // the stop bound is a hair smaller than (s h)^2 + D^2: covers the rounding of d2
 constexpr unsigned kMinTableBits = 10, kMaxTableBits = 26;
@@ -60,7 +63,8 @@ constexpr int kLevelShells = 2;            // shells 0 .. kLevelShells of a leve
 constexpr int kStPose = 0, kStCentre = 12, kStStop = 18, kStCount = 19, kStSum = 20, kStFitness = 21, kStRmse = 22,
               kStIter = 23, kStConverged = 24, kStStatus = 25, kStEvals = 26, kStSumsA = 32, kStSumsB = 64, kStLen = 96;
 constexpr int kStatusOk = 0, kStatusTooFew = 1, kStatusDegenerate = 2;
-constexpr int kPointToPoint = 0, kPointToPlane = 1;
+constexpr int kPointToPoint = 0, kPointToPlane = 1, kGeneralized = 2;
+constexpr int kCov = 6;  // doubles per covariance: xx, xy, xz, yy, yz, zz
 
 struct Grid {
     double lo[3], hi[3];  // the target's box
@@ -259,9 +263,12 @@ __global__ __launch_bounds__(kBlock) void k_icp_search(Levels lv, const double* 
 //   MODE 0  (count, sum d2, sum q (3), sum y (3))                          point-to-point, first pass
 //   MODE 1  (q - qm)_a (y - ym)_b, a major (9)                              point-to-point, second pass
 //   MODE 2  (count, sum d2, J J^T upper triangle row-major (21), J res (6)) point-to-plane; J = (q x n, n), res = n . (q - y)
+//   MODE 3  (count, sum d2, J^T P J upper triangle row-major (21), J^T P d (6), d^T P d) generalized; J = (-[q]x | I),
+//           d = q - y, P the inverse of C_target + R C_source R^T (cs, ct: kCov doubles per source / target point)
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_icp_sums(const double* __restrict__ src, int64_t M, const double4* __restrict__ tp,
-                                                     const double4* __restrict__ tn, const int* __restrict__ idx,
+                                                     const double4* __restrict__ tn, const double* __restrict__ cs,
+                                                     const double* __restrict__ ct, const int* __restrict__ idx,
                                                      const double* __restrict__ d2, const double* __restrict__ state,
                                                      double* __restrict__ part) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -295,6 +302,65 @@ __global__ __launch_bounds__(kBlock) void k_icp_sums(const double* __restrict__ 
             for (int a = 0; a < 3; ++a)
 #pragma unroll
                 for (int b = 0; b < 3; ++b) acc[3 * a + b] += (q[a] - ctr[a]) * (y[b] - ctr[3 + b]);
+        } else if (MODE == 3) {
+            const double* __restrict__ a = cs + m * kCov;
+            const double* __restrict__ b = ct + (int64_t)t * kCov;
+            const double c[3][3] = {{a[0], a[1], a[2]}, {a[1], a[3], a[4]}, {a[2], a[4], a[5]}};
+            double rc[3][3];  // R C_source
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    rc[i][j] = (pose[3 * i] * c[0][j] + pose[3 * i + 1] * c[1][j]) + pose[3 * i + 2] * c[2][j];
+            double mm[6];  // M = C_target + (R C_source) R^T, upper triangle
+            int s = 0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = i; j < 3; ++j, ++s)
+                    mm[s] = b[s] + ((rc[i][0] * pose[3 * j] + rc[i][1] * pose[3 * j + 1]) + rc[i][2] * pose[3 * j + 2]);
+            // P = adj(M) / det(M)
+            const double c00 = mm[3] * mm[5] - mm[4] * mm[4], c01 = mm[2] * mm[4] - mm[1] * mm[5];
+            const double c02 = mm[1] * mm[4] - mm[2] * mm[3], c11 = mm[0] * mm[5] - mm[2] * mm[2];
+            const double c12 = mm[1] * mm[2] - mm[0] * mm[4], c22 = mm[0] * mm[3] - mm[1] * mm[1];
+            const double det = (mm[0] * c00 + mm[1] * c01) + mm[2] * c02;
+            const double p01 = c01 / det, p02 = c02 / det, p12 = c12 / det;
+            const double P[3][3] = {{c00 / det, p01, p02}, {p01, c11 / det, p12}, {p02, p12, c22 / det}};
+            const double d[3] = {q[0] - y[0], q[1] - y[1], q[2] - y[2]};
+            double B[3][3], E[3][3], v[3];  // B = P (-[q]x): row a is q x P_a;  E = (-[q]x)^T B;  v = P d
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                B[i][0] = q[1] * P[i][2] - q[2] * P[i][1];
+                B[i][1] = q[2] * P[i][0] - q[0] * P[i][2];
+                B[i][2] = q[0] * P[i][1] - q[1] * P[i][0];
+                v[i] = (P[i][0] * d[0] + P[i][1] * d[1]) + P[i][2] * d[2];
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                E[0][j] = q[1] * B[2][j] - q[2] * B[1][j];
+                E[1][j] = q[2] * B[0][j] - q[0] * B[2][j];
+                E[2][j] = q[0] * B[1][j] - q[1] * B[0][j];
+            }
+            acc[0] += 1.0;
+            acc[1] += d2[m];
+            s = 2;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = i; j < 3; ++j) acc[s++] += E[i][j];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[s++] += B[j][i];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = i; j < 3; ++j) acc[s++] += P[i][j];
+            acc[23] += q[1] * v[2] - q[2] * v[1];
+            acc[24] += q[2] * v[0] - q[0] * v[2];
+            acc[25] += q[0] * v[1] - q[1] * v[0];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) acc[26 + i] += v[i];
+            acc[29] += (d[0] * v[0] + d[1] * v[1]) + d[2] * v[2];
         } else {
             const double4 n4 = tn[t];
             const double n[3] = {n4.x, n4.y, n4.z};
@@ -317,7 +383,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_sums(const double* __restrict__ 
 }
 
 // One workgroup of kSlots lanes: lane k adds slot k of the runs in ascending run order and keeps the total in the state
-// (mode 1: kStSumsB, else kStSumsA).  Modes 0 and 2 are also the evaluation of the current pose: count, sum, fitness,
+// (mode 1: kStSumsB, else kStSumsA).  Modes 0, 2 and 3 are also the evaluation of the current pose: count, sum, fitness,
 // rmse - and, with `test`, Open3D's stop test against the evaluation before.  Mode 0 leaves the centroids for the second pass.
 __global__ __launch_bounds__(kSlots) void k_icp_finish(const double* __restrict__ part, int64_t nruns, int mode, int test,
                                                        double m_total, double rel_fitness, double rel_rmse,
@@ -355,6 +421,27 @@ __global__ __launch_bounds__(kSlots) void k_icp_finish(const double* __restrict_
     state[kStRmse] = rmse;
     if (mode == 0)
         for (int k = 0; k < 6; ++k) state[kStCentre + k] = cnt > 0.0 ? tot[2 + k] / cnt : 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------- covariances
+// C = I - (1 - eps) u u^T of the unit normal u = n / |n| (Open3D's R diag(eps, 1, 1) R^T without the rotation): kCov doubles
+// per point.  The host has checked that every |n| is finite and > 0.
+__global__ __launch_bounds__(kBlock) void k_icp_cov_from_normals(const double* __restrict__ nrm, int64_t n, double eps,
+                                                                 double* __restrict__ cov) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double n0 = nrm[i * 3], n1 = nrm[i * 3 + 1], n2 = nrm[i * 3 + 2];
+    const double len = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+    const double u[3] = {n0 / len, n1 / len, n2 / len};
+    const double k = 1.0 - eps;
+    const double w[3] = {k * u[0], k * u[1], k * u[2]};
+    double* __restrict__ c = cov + i * kCov;
+    c[0] = 1.0 - w[0] * u[0];
+    c[1] = -(w[0] * u[1]);
+    c[2] = -(w[0] * u[2]);
+    c[3] = 1.0 - w[1] * u[1];
+    c[4] = -(w[1] * u[2]);
+    c[5] = 1.0 - w[2] * u[2];
 }
 
 // ----------------------------------------------------------------------------------------------------------------- step
@@ -518,11 +605,13 @@ struct prg_icp {
     hipStream_t stream = nullptr;
     int64_t N = 0, M = 0;
     bool have_normals = false, have_order = false, have_matches = false;
+    bool have_cov[2] = {false, false};    // source, target
     Levels lv;
     prg::DevBuf<double4> tp, tn;          // target points and normals, padded to four doubles
     prg::DevBuf<double4> sp[kMaxLevels];  // per level: the points in cell order, original index in .w
     prg::DevBuf<int2> cells[kMaxLevels];  // per level, table entries: (begin, end)
     prg::DevBuf<double> src;              // [M][3]
+    prg::DevBuf<double> cov[2];           // [M][kCov] of the source, [N][kCov] of the target
     prg::DevBuf<unsigned> qkeys;          // 2 M: unsorted, sorted
     prg::DevBuf<int> qvals;               // 2 M: iota, order
     prg::DevBuf<char> sort_tmp;
@@ -543,11 +632,39 @@ int require_ready(prg_icp* h, const char* who, bool matches) {
 }
 
 int check_kind(const char* who, prg_icp* h, int kind) {
-    PRG_REQUIRE(kind == kPointToPoint || kind == kPointToPlane, PRG_ERR_INVALID,
-                "%s: kind must be 0 (point-to-point) or 1 (point-to-plane), got %d", who, kind);
-    PRG_REQUIRE(kind == kPointToPoint || h->have_normals, PRG_ERR_STATE,
+    PRG_REQUIRE(kind == kPointToPoint || kind == kPointToPlane || kind == kGeneralized, PRG_ERR_INVALID,
+                "%s: kind must be 0 (point-to-point), 1 (point-to-plane) or 2 (generalized), got %d", who, kind);
+    PRG_REQUIRE(kind != kPointToPlane || h->have_normals, PRG_ERR_STATE,
                 "%s: point-to-plane needs the target's normals (prg_icp_set_target)", who);
+    PRG_REQUIRE(kind != kGeneralized || (h->have_cov[0] && h->have_cov[1]), PRG_ERR_STATE,
+                "%s: generalized ICP needs the covariances of the %s (prg_icp_set_covariances or "
+                "prg_icp_set_covariances_from_normals, after the cloud is set)", who,
+                h->have_cov[0] ? "target" : (h->have_cov[1] ? "source" : "source and of the target"));
     return PRG_OK;
+}
+
+// the cloud `which` (0 source, 1 target) is set and has n points
+int cov_rows(prg_icp* h, const char* who, int which, int64_t n, int64_t* rows) {
+    PRG_REQUIRE(which == 0 || which == 1, PRG_ERR_INVALID, "%s: which must be 0 (source) or 1 (target), got %d", who, which);
+    *rows = which == 0 ? h->M : h->N;
+    PRG_REQUIRE(*rows >= 1, PRG_ERR_STATE, "%s: no %s (prg_icp_set_%s first)", who, which == 0 ? "source" : "target",
+                which == 0 ? "source" : "target");
+    PRG_REQUIRE(n == *rows, PRG_ERR_INVALID, "%s: need one row per %s point (%lld), got %lld", who,
+                which == 0 ? "source" : "target", (long long)*rows, (long long)n);
+    return PRG_OK;
+}
+
+// the pivot rule of cholesky6 on a 3 x 3 covariance (xx, xy, xz, yy, yz, zz)
+bool positive_definite3(const double* c) {
+    const double floor_ = kPivot * std::max(c[0], std::max(c[3], c[5]));
+    const double d0 = c[0];
+    if (!(d0 > floor_)) return false;
+    const double l00 = std::sqrt(d0), l10 = c[1] / l00, l20 = c[2] / l00;
+    const double d1 = c[3] - l10 * l10;
+    if (!(d1 > floor_)) return false;
+    const double l11 = std::sqrt(d1), l21 = (c[4] - l20 * l10) / l11;
+    const double d2 = (c[5] - l20 * l20) - l21 * l21;
+    return d2 > floor_;
 }
 
 int ensure_state(prg_icp* h) {
@@ -588,15 +705,17 @@ void enqueue_search(prg_icp* h, double r) {
 template <int MODE>
 void enqueue_sums(prg_icp* h, int test, double rel_fitness, double rel_rmse) {
     const int64_t nruns = prg::ceil_div(h->M, kRun);
-    k_icp_sums<MODE><<<(unsigned)prg::ceil_div(nruns, kBlock), kBlock, 0, h->stream>>>(h->src.p, h->M, h->tp.p, h->tn.p, h->idx.p,
-                                                                                     h->d2.p, h->state.p, h->part.p);
+    k_icp_sums<MODE><<<(unsigned)prg::ceil_div(nruns, kBlock), kBlock, 0, h->stream>>>(h->src.p, h->M, h->tp.p, h->tn.p, h->cov[0].p,
+                                                                                     h->cov[1].p, h->idx.p, h->d2.p, h->state.p,
+                                                                                     h->part.p);
     k_icp_finish<<<1, kSlots, 0, h->stream>>>(h->part.p, nruns, MODE, test, (double)h->M, rel_fitness, rel_rmse, h->state.p);
 }
 
 // the sums of the current matches that evaluate the pose and start a step of `kind`
 void enqueue_eval(prg_icp* h, int kind, int test, double rel_fitness, double rel_rmse) {
     if (kind == kPointToPoint) enqueue_sums<0>(h, test, rel_fitness, rel_rmse);
-    else enqueue_sums<2>(h, test, rel_fitness, rel_rmse);
+    else if (kind == kPointToPlane) enqueue_sums<2>(h, test, rel_fitness, rel_rmse);
+    else enqueue_sums<3>(h, test, rel_fitness, rel_rmse);
 }
 
 // the step itself, from the sums of enqueue_eval
@@ -641,7 +760,7 @@ int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normal
     hipStream_t st = h->stream;
     PRG_HIP(hipStreamSynchronize(st));
     h->N = 0;
-    h->have_normals = h->have_order = h->have_matches = false;
+    h->have_normals = h->have_order = h->have_matches = h->have_cov[1] = false;
     std::vector<double> raw((size_t)n * 3), pad((size_t)n * 4, 0.0);
     PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
     double lo[3], hi[3];
@@ -738,7 +857,7 @@ int prg_icp_set_source(prg_icp* h, const double* points_hd, int64_t m) {
     PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_source: hipSetDevice(%d) failed", h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->M = 0;
-    h->have_order = h->have_matches = false;
+    h->have_order = h->have_matches = h->have_cov[0] = false;
     std::vector<double> raw((size_t)m * 3);
     PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
     for (size_t i = 0; i < raw.size(); ++i)
@@ -753,6 +872,74 @@ int prg_icp_set_source(prg_icp* h, const double* points_hd, int64_t m) {
     PRG_HIP(hipMemcpy(h->src.p, raw.data(), raw.size() * sizeof(double), hipMemcpyHostToDevice));
     PRG_TRY(ensure_state(h));
     h->M = m;
+    return PRG_OK;
+}
+
+int prg_icp_set_covariances(prg_icp* h, int which, const double* cov_hd, int64_t n) {
+    PRG_REQUIRE(h && cov_hd, PRG_ERR_INVALID, "prg_icp_set_covariances: NULL argument");
+    int64_t rows = 0;
+    PRG_TRY(cov_rows(h, "prg_icp_set_covariances", which, n, &rows));
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_covariances: hipSetDevice(%d) failed", h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    h->have_cov[which] = false;
+    std::vector<double> raw((size_t)rows * kCov);
+    PRG_HIP(hipMemcpy(raw.data(), cov_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    for (int64_t i = 0; i < rows; ++i) {
+        const double* c = raw.data() + (size_t)i * kCov;
+        for (int k = 0; k < kCov; ++k)
+            PRG_REQUIRE(std::isfinite(c[k]), PRG_ERR_INVALID, "prg_icp_set_covariances: the covariances contain NaN or infinity");
+        PRG_REQUIRE(positive_definite3(c), PRG_ERR_INVALID,
+                    "prg_icp_set_covariances: covariance %lld is not positive definite (a Cholesky pivot <= 1e-12 max diag)",
+                    (long long)i);
+    }
+    PRG_HIP(h->cov[which].ensure(rows * kCov, rows * kCov));
+    PRG_HIP(hipMemcpy(h->cov[which].p, raw.data(), raw.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->have_cov[which] = true;
+    return PRG_OK;
+}
+
+int prg_icp_set_covariances_from_normals(prg_icp* h, int which, const double* normals_hd, int64_t n, double epsilon) {
+    PRG_REQUIRE(h && normals_hd, PRG_ERR_INVALID, "prg_icp_set_covariances_from_normals: NULL argument");
+    int64_t rows = 0;
+    PRG_TRY(cov_rows(h, "prg_icp_set_covariances_from_normals", which, n, &rows));
+    PRG_REQUIRE(epsilon > 0.0 && epsilon <= 1.0, PRG_ERR_INVALID,
+                "prg_icp_set_covariances_from_normals: epsilon must lie in (0, 1], got %g", epsilon);
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_covariances_from_normals: hipSetDevice(%d) failed", h->device);
+    hipStream_t st = h->stream;
+    PRG_HIP(hipStreamSynchronize(st));
+    h->have_cov[which] = false;
+    std::vector<double> raw((size_t)rows * 3);
+    PRG_HIP(hipMemcpy(raw.data(), normals_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    for (int64_t i = 0; i < rows; ++i) {
+        const double* v = raw.data() + (size_t)i * 3;
+        const double len = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);  // NaN for a NaN entry
+        PRG_REQUIRE(std::isfinite(len) && len > 0.0, PRG_ERR_INVALID,
+                    "prg_icp_set_covariances_from_normals: normal %lld has no finite length > 0", (long long)i);
+    }
+    prg::DevBuf<double> nrm;
+    PRG_HIP(nrm.reset(rows * 3));
+    PRG_HIP(h->cov[which].ensure(rows * kCov, rows * kCov));
+    PRG_HIP(hipMemcpy(nrm.p, raw.data(), raw.size() * sizeof(double), hipMemcpyHostToDevice));
+    k_icp_cov_from_normals<<<(unsigned)prg::ceil_div(rows, kBlock), kBlock, 0, st>>>(nrm.p, rows, epsilon, h->cov[which].p);
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipStreamSynchronize(st));  // the normals go away with this scope
+    h->have_cov[which] = true;
+    return PRG_OK;
+}
+
+int prg_icp_get_covariances(prg_icp* h, int which, double* cov_host) {
+    PRG_REQUIRE(h && cov_host, PRG_ERR_INVALID, "prg_icp_get_covariances: NULL argument");
+    PRG_REQUIRE(which == 0 || which == 1, PRG_ERR_INVALID, "prg_icp_get_covariances: which must be 0 (source) or 1 (target), got %d",
+                which);
+    PRG_REQUIRE(h->have_cov[which], PRG_ERR_STATE, "prg_icp_get_covariances: the %s has no covariances",
+                which == 0 ? "source" : "target");
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_covariances: hipSetDevice(%d) failed", h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    const int64_t rows = which == 0 ? h->M : h->N;
+    PRG_HIP(hipMemcpy(cov_host, h->cov[which].p, (size_t)rows * kCov * sizeof(double), hipMemcpyDeviceToHost));
     return PRG_OK;
 }
 
@@ -820,7 +1007,7 @@ int prg_icp_sums(prg_icp* h, int kind, double* out_host) {
         for (int k = 0; k < 8; ++k) out_host[k] = sums[k];
         for (int k = 0; k < 9; ++k) out_host[8 + k] = sums[kSlots + k];
     } else {
-        for (int k = 0; k < 29; ++k) out_host[k] = sums[k];
+        for (int k = 0; k < (kind == kGeneralized ? 30 : 29); ++k) out_host[k] = sums[k];
     }
     return PRG_OK;
 }

@@ -13,6 +13,9 @@ Open3D nor scikit-learn is imported.
 
 ``evaluate_registration`` scores the result of any method of the library, ``nearest_neighbour`` is the search on its own, and
 ``IcpPlan`` gives every stage: matches, raw sums, one step, the pose, the loop.
+
+``registration_gicp`` is generalized (plane-to-plane) ICP, Open3D's ``registration_generalized_icp``, on the same search, sums,
+step and loop: every point carries a covariance, given or ``I - (1 - epsilon) u u^T`` of its unit normal.
 """
 import collections
 import ctypes
@@ -25,6 +28,9 @@ from .global_reg import _as_rows, _single_process
 from .transformation import RigidTransformation
 
 POINT_TO_POINT, POINT_TO_PLANE = 0, 1
+GENERALIZED = 2
+PIVOT = 1.0e-12  # a Cholesky pivot <= PIVOT max diag is not positive (the rule of the 6 x 6 step)
+_WHICH = {"source": 0, "target": 1}
 _KINDS = {"point_to_point": POINT_TO_POINT, "point_to_plane": POINT_TO_PLANE}
 STATUS = ("ok", "too_few_matches", "degenerate")
 N_SUMS = 32
@@ -32,6 +38,8 @@ N_SUMS = 32
 IcpResult = collections.namedtuple("IcpResult", ["transformation", "fitness", "inlier_rmse", "correspondences", "n_iter",
                                                  "converged"])
 IcpState = collections.namedtuple("IcpState", ["pose", "count", "sum", "n_iter", "converged", "status"])
+GicpResult = collections.namedtuple("GicpResult", ["transformation", "fitness", "inlier_rmse", "correspondences", "n_iter",
+                                                   "converged", "objective"])
 
 
 def _check_r(r, name="max_correspondence_distance"):
@@ -47,6 +55,93 @@ def _kind(estimation):
     if estimation not in _KINDS:
         raise ValueError("estimation must be 'point_to_point' or 'point_to_plane', got %r" % (estimation,))
     return _KINDS[estimation]
+
+
+def _plan_kind(estimation):
+    """``_kind`` and, for the stages of a plan, the generalized estimator."""
+    if (estimation == GENERALIZED and not isinstance(estimation, str)) or estimation == "generalized":
+        return GENERALIZED
+    return _kind(estimation)
+
+
+def _check_epsilon(epsilon):
+    eps = float(epsilon)
+    if not 0.0 < eps <= 1.0:  # also NaN
+        raise ValueError("epsilon must lie in (0, 1], got %r" % (epsilon,))
+    return eps
+
+
+def _checked_normals(normals, name, n=None):
+    """(normals (n, 3), their lengths): finite, one row per point, no length 0."""
+    nrm = _as_rows(normals, name, 3)
+    if n is not None and nrm.shape[0] != n:
+        raise ValueError("%s must have one row per point (%d), got %d" % (name, n, nrm.shape[0]))
+    with np.errstate(over="ignore"):
+        length = np.sqrt((nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1]) + nrm[:, 2] * nrm[:, 2])
+    bad = np.nonzero(~(np.isfinite(length) & (length > 0.0)))[0]
+    if bad.size:
+        raise ValueError("%s: row %d has norm 0 (or one that is not finite); a covariance needs a direction"
+                         % (name, int(bad[0])))
+    return nrm, length
+
+
+def _cov6_from_normals(nrm, length, eps):
+    """The host mirror of the device's covariances from normals, (n, 6): xx, xy, xz, yy, yz, zz."""
+    u = nrm / length[:, None]
+    w = (1.0 - eps) * u
+    c = np.empty((nrm.shape[0], 6))
+    c[:, 0] = 1.0 - w[:, 0] * u[:, 0]
+    c[:, 1] = -(w[:, 0] * u[:, 1])
+    c[:, 2] = -(w[:, 0] * u[:, 2])
+    c[:, 3] = 1.0 - w[:, 1] * u[:, 1]
+    c[:, 4] = -(w[:, 1] * u[:, 2])
+    c[:, 5] = 1.0 - w[:, 2] * u[:, 2]
+    return c
+
+
+def _full(c6):
+    return np.ascontiguousarray(c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3))
+
+
+def covariances_from_normals(normals, epsilon=1.0e-3):
+    """(n, 3, 3): ``C = I - (1 - epsilon) u u^T`` of the unit normals ``u = n / |n|`` - Open3D's ``R diag(epsilon, 1, 1) R^T``,
+    whatever the sign of the normal.  The host mirror of what ``set_source_covariances(normals=...)`` computes on the
+    device, operation for operation."""
+    eps = _check_epsilon(epsilon)
+    nrm, length = _checked_normals(normals, "normals")
+    return _full(_cov6_from_normals(nrm, length, eps))
+
+
+def _checked_cov6(covariances, name, n=None):
+    """(n, 6) of covariances given as (n, 3, 3) or (n, 6): finite, symmetric, positive definite by the pivot rule."""
+    c = np.asarray(covariances, dtype=np.float64)
+    if c.ndim == 3 and c.shape[0] >= 1 and c.shape[1:] == (3, 3):
+        if not np.all(np.isfinite(c)):
+            raise ValueError("%s contains NaN or infinity" % name)
+        if not np.array_equal(c, c.transpose(0, 2, 1)):
+            raise ValueError("%s must be symmetric" % name)
+        c = c.reshape(-1, 9)[:, [0, 1, 2, 4, 5, 8]]
+    elif c.ndim == 2 and c.shape[0] >= 1 and c.shape[1] == 6:
+        if not np.all(np.isfinite(c)):
+            raise ValueError("%s contains NaN or infinity" % name)
+    else:
+        raise ValueError("%s must be (n, 3, 3) or (n, 6: xx, xy, xz, yy, yz, zz) with n >= 1, got shape %s" % (name, c.shape))
+    if n is not None and c.shape[0] != n:
+        raise ValueError("%s must have one covariance per point (%d), got %d" % (name, n, c.shape[0]))
+    c = np.ascontiguousarray(c)
+    floor = PIVOT * np.max(c[:, [0, 3, 5]], axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        l00 = np.sqrt(c[:, 0])
+        l10, l20 = c[:, 1] / l00, c[:, 2] / l00
+        d1 = c[:, 3] - l10 * l10
+        l11 = np.sqrt(d1)
+        l21 = (c[:, 4] - l20 * l10) / l11
+        d2 = (c[:, 5] - l20 * l20) - l21 * l21
+        good = (c[:, 0] > floor) & (d1 > floor) & (d2 > floor)
+    bad = np.nonzero(~good)[0]
+    if bad.size:
+        raise ValueError("%s: covariance %d is not positive definite (a Cholesky pivot <= 1e-12 max diag)" % (name, int(bad[0])))
+    return c
 
 
 def _pose12(init):
@@ -136,6 +231,38 @@ class IcpPlan(object):
         _lib.check(_lib.lib.prg_icp_set_source(self._h, _lib.ptr(pts), pts.shape[0]))
         self.n_source = pts.shape[0]
 
+    def _set_covariances(self, which, n, covariances, normals, epsilon):
+        name = "%s_covariances" % which
+        if (covariances is None) == (normals is None):
+            raise ValueError("set_%s takes either covariances or normals" % name)
+        if n < 1:
+            raise ValueError("set_%s: set the %s first (its covariances go with it)" % (name, which))
+        if covariances is not None:
+            c = _checked_cov6(covariances, name, n)
+            _lib.check(_lib.lib.prg_icp_set_covariances(self._h, _WHICH[which], _lib.ptr(c), n))
+        else:
+            eps = _check_epsilon(epsilon)
+            nrm, _ = _checked_normals(normals, "%s_normals" % which, n)
+            _lib.check(_lib.lib.prg_icp_set_covariances_from_normals(self._h, _WHICH[which], _lib.ptr(nrm), n, eps))
+
+    def set_source_covariances(self, covariances=None, normals=None, epsilon=1.0e-3):
+        """The source's covariances for the generalized estimator: ``covariances`` (M, 3, 3) or (M, 6: xx, xy, xz, yy, yz, zz),
+        symmetric positive definite, or ``normals`` (M, 3) with ``epsilon`` (``covariances_from_normals``, on the device).
+        After ``set_source``, which drops them."""
+        self._set_covariances("source", self.n_source, covariances, normals, epsilon)
+
+    def set_target_covariances(self, covariances=None, normals=None, epsilon=1.0e-3):
+        """The target's covariances, as ``set_source_covariances``.  After ``set_target``, which drops them."""
+        self._set_covariances("target", self.n_target, covariances, normals, epsilon)
+
+    def covariances(self, which):
+        """(n, 3, 3): the covariances of ``which`` ("source" or "target") as the device holds them."""
+        if which not in _WHICH:
+            raise ValueError("which must be 'source' or 'target', got %r" % (which,))
+        c = np.empty((self.n_source if which == "source" else self.n_target, 6))
+        _lib.check(_lib.lib.prg_icp_get_covariances(self._h, _WHICH[which], _lib.ptr(c)))
+        return _full(c)
+
     def set_pose(self, pose):
         """``pose``: None, a RigidTransformation with scale 1, a 4 x 4 array or 12 doubles (rotation row-major, then the shift)."""
         p = np.asarray(pose, dtype=np.float64) if pose is not None and not hasattr(pose, "rot") else None
@@ -163,17 +290,18 @@ class IcpPlan(object):
         return idx, d2
 
     def sums(self, estimation):
-        """The raw ordered sums of a step over the current matches (32 doubles, laid out as ``prg_icp_sums`` documents)."""
+        """The raw ordered sums of a step over the current matches (32 doubles, laid out as ``prg_icp_sums`` documents).
+        ``estimation``: as in ``registration_icp``, or ``GENERALIZED`` / "generalized" (here, in ``step`` and in ``iterate``)."""
         out = np.empty(N_SUMS)
-        _lib.check(_lib.lib.prg_icp_sums(self._h, _kind(estimation), _lib.ptr(out)))
+        _lib.check(_lib.lib.prg_icp_sums(self._h, _plan_kind(estimation), _lib.ptr(out)))
         return out
 
     def step(self, estimation):
         """One step on the current matches; a missing step leaves the pose and shows in ``state().status``."""
-        _lib.check(_lib.lib.prg_icp_step(self._h, _kind(estimation)))
+        _lib.check(_lib.lib.prg_icp_step(self._h, _plan_kind(estimation)))
 
     def iterate(self, estimation, r, max_iteration=30, relative_fitness=1.0e-6, relative_rmse=1.0e-6, chunk=8):
-        _lib.check(_lib.lib.prg_icp_iterate(self._h, _kind(estimation), _check_r(r), int(max_iteration), float(relative_fitness),
+        _lib.check(_lib.lib.prg_icp_iterate(self._h, _plan_kind(estimation), _check_r(r), int(max_iteration), float(relative_fitness),
                                             float(relative_rmse), int(chunk)))
 
     def state(self):
@@ -234,6 +362,70 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     fitness, rmse = _score(st.count, st.sum, src.shape[0])
     tf = RigidTransformation(st.pose[:9].reshape(3, 3).copy(), st.pose[9:].copy(), 1.0)
     return IcpResult(tf, fitness, rmse, _correspondences(idx), st.n_iter, st.converged)
+
+
+def _gicp_covariances(cloud, name, n, covariances, normals, normal_radius):
+    """What ``registration_gicp`` hands to the plan for one cloud: ("covariances", (n, 6)), ("normals", (n, 3)) or
+    ("estimate", None), from the first source that applies; everything given is validated here, on the host."""
+    if covariances is not None:
+        return "covariances", _checked_cov6(covariances, "%s_covariances" % name, n)
+    nrm = normals if normals is not None else getattr(cloud, "normals", None)
+    if nrm is not None and not (hasattr(nrm, "__len__") and len(nrm) == 0):
+        return "normals", _checked_normals(nrm, "%s_normals" % name, n)[0]
+    if normal_radius is None:
+        raise ValueError("generalized ICP needs covariances or normals of the %s: pass %s_covariances, %s_normals, a %s with "
+                         ".normals, or normal_radius (then fpfh.FPFH(radius_normal=normal_radius).estimate_normals computes "
+                         "them)" % (name, name, name, name))
+    return "estimate", None
+
+
+def registration_gicp(source, target, max_correspondence_distance, init=None, source_normals=None, target_normals=None,
+                      source_covariances=None, target_covariances=None, epsilon=1.0e-3, normal_radius=None, normal_max_nn=30,
+                      max_iteration=30, relative_fitness=1.0e-6, relative_rmse=1.0e-6, device=None):
+    """Generalized (plane-to-plane) ICP, Open3D's ``registration_generalized_icp``: the loop, the search and the stop test
+    of ``registration_icp``; a step minimises ``sum d^T (C_target + R C_source R^T)^-1 d`` over the matches, linearised at
+    the current pose.
+
+    A cloud gets its covariances from the first of: its ``*_covariances`` argument ((n, 3, 3) or (n, 6), symmetric positive
+    definite); its ``*_normals`` argument; its ``.normals`` attribute; ``fpfh.FPFH(radius_normal=normal_radius,
+    max_nn_normal=normal_max_nn).estimate_normals`` when ``normal_radius`` is given.  Normals become
+    ``I - (1 - epsilon) u u^T``, ``0 < epsilon <= 1``.
+
+    ``GicpResult(transformation, fitness, inlier_rmse, correspondences, n_iter, converged, objective)``: as ``IcpResult``
+    (fitness and inlier_rmse are Euclidean), and ``objective`` the Mahalanobis sum over the final matches at the final pose.
+    A step that cannot be taken (fewer than 6 matches, a degenerate system) ends the loop with ``converged`` False."""
+    src, tgt = _as_rows(source, "source", 3), _as_rows(target, "target", 3)
+    r = _check_r(max_correspondence_distance)
+    pose = _pose12(init)
+    eps = _check_epsilon(epsilon)
+    if normal_radius is not None and not (np.isfinite(normal_radius) and normal_radius > 0.0):
+        raise ValueError("normal_radius must be > 0 and finite, got %r" % (normal_radius,))
+    how = [_gicp_covariances(source, "source", src.shape[0], source_covariances, source_normals, normal_radius),
+           _gicp_covariances(target, "target", tgt.shape[0], target_covariances, target_normals, normal_radius)]
+    _check_loop(max_iteration, relative_fitness, relative_rmse)
+    _single_process("registration_gicp")
+    for k, pts in enumerate((src, tgt)):
+        if how[k][0] == "estimate":
+            from . import fpfh
+
+            est = fpfh.FPFH(radius_normal=normal_radius, max_nn_normal=normal_max_nn, device=device).estimate_normals(pts)
+            how[k] = ("normals", _checked_normals(est, "the estimated %s normals" % ("source", "target")[k], pts.shape[0])[0])
+    plan = IcpPlan(device)
+    try:
+        plan.set_target(tgt)
+        plan.set_source(src)
+        for setter, (what, value) in zip((plan.set_source_covariances, plan.set_target_covariances), how):
+            setter(**{what: value, "epsilon": eps})
+        plan.set_pose(pose)
+        plan.iterate(GENERALIZED, r, max_iteration, relative_fitness, relative_rmse)
+        st = plan.state()
+        idx, _ = plan.matches()
+        objective = float(plan.sums(GENERALIZED)[29])
+    finally:
+        plan.close()
+    fitness, rmse = _score(st.count, st.sum, src.shape[0])
+    tf = RigidTransformation(st.pose[:9].reshape(3, 3).copy(), st.pose[9:].copy(), 1.0)
+    return GicpResult(tf, fitness, rmse, _correspondences(idx), st.n_iter, st.converged, objective)
 
 
 def evaluate_registration(source, target, max_correspondence_distance, transformation=None, device=None):
