@@ -24,26 +24,14 @@ struct SourceBuffers {
     DevBuf<float> zchunk;   // [Mcap/256][8] box of every 256-point chunk of the transformed source (per E-step)
     int64_t Mcap = 0;       // padded capacity (a multiple of 1024, + slack for segmenting)
 
-    void release_source() {
-        src4.release(); z4.release(); rowacc.release(); zmeta.release(); rorig.release(); zchunk.release();
-        Mcap = 0;
-    }
     // exact sizes for `cap` points: kept when cap == Mcap, re-created as a whole otherwise (the contents are gone)
     hipError_t size_source(int64_t cap) {
         if (cap == Mcap) return hipSuccess;
-        release_source();
-        hipError_t e = src4.reset(cap);
-        if (e == hipSuccess) e = z4.reset(cap);
-        if (e == hipSuccess) e = rowacc.reset(4 * cap);
-        if (e == hipSuccess) e = zmeta.reset(cap / kGroup * 8);
-        if (e == hipSuccess) e = rorig.reset(cap / kMfmaWgPoints + 4);
-        if (e == hipSuccess) e = zchunk.reset(cap / kSuper * 8);
-        if (e != hipSuccess) {
-            release_source();
-            return e;
-        }
-        Mcap = cap;
-        return hipSuccess;
+        Mcap = 0;
+        const hipError_t e = reset_group(src4, cap, z4, cap, rowacc, 4 * cap, zmeta, cap / kGroup * 8, rorig, cap / kMfmaWgPoints + 4,
+                                         zchunk, cap / kSuper * 8);
+        if (e == hipSuccess) Mcap = cap;
+        return e;
     }
 };
 
@@ -58,25 +46,14 @@ struct TargetBuffers {
                            // [Ncap/32] per-group maxima of it
     int64_t Ncap = 0;
 
-    void release_target() {
-        tgt4.release(); pt1.release(); tmeta.release(); tchunk.release(); corig.release(); colmin.release();
-        Ncap = 0;
-    }
     // as size_source; *recreated: the group is new (the owner zeroes colmin)
     hipError_t size_target(int64_t cap, bool* recreated) {
         *recreated = false;
         if (cap == Ncap) return hipSuccess;
-        release_target();
-        hipError_t e = tgt4.reset(cap);
-        if (e == hipSuccess) e = pt1.reset(cap);
-        if (e == hipSuccess) e = tmeta.reset(cap / kGroup * 8);
-        if (e == hipSuccess) e = tchunk.reset(cap / kSuper * 8);
-        if (e == hipSuccess) e = corig.reset(cap / kMfmaWgPoints + 4);
-        if (e == hipSuccess) e = colmin.reset(cap + cap / kGroup);
-        if (e != hipSuccess) {
-            release_target();
-            return e;
-        }
+        Ncap = 0;
+        const hipError_t e = reset_group(tgt4, cap, pt1, cap, tmeta, cap / kGroup * 8, tchunk, cap / kSuper * 8, corig,
+                                         cap / kMfmaWgPoints + 4, colmin, cap + cap / kGroup);
+        if (e != hipSuccess) return e;
         Ncap = cap;
         *recreated = true;
         return hipSuccess;
@@ -109,19 +86,14 @@ struct SweepQueue {
     hipError_t size(int64_t blocks, int chunks, int64_t max_units, bool* recreated) {
         *recreated = false;
         if (fits(blocks, chunks, max_units)) return hipSuccess;
-        release();
-        hipError_t e = masks.reset(blocks * chunks * (kQueueChunkGroups / 64));
-        if (e == hipSuccess) e = chunk.reset(blocks * chunks);
-        if (e == hipSuccess) e = units.reset(max_units);
-        if (e == hipSuccess) e = ctrl.reset(16);
-        if (e == hipSuccess) e = ucount.reset(max_units);
-        if (e != hipSuccess) {
-            release();
-            return e;
-        }
-        cap_blocks = blocks;
-        cap_chunk = chunks;
-        cap_units = max_units;
+        const hipError_t e = reset_group(masks, blocks * chunks * (kQueueChunkGroups / 64), chunk, blocks * chunks, units, max_units,
+                                         ctrl, 16, ucount, max_units);
+        nblocks = 0;  // (the sweep built into the old arrays went with them)
+        nchunk = cap_soft = 0;
+        cap_blocks = e == hipSuccess ? blocks : 0;
+        cap_chunk = e == hipSuccess ? chunks : 0;
+        cap_units = e == hipSuccess ? max_units : 0;
+        if (e != hipSuccess) return e;
         *recreated = true;
         return hipSuccess;
     }

@@ -51,6 +51,37 @@ struct DevBuf {
     }
 };
 
+// Buffers that are sized together, of any element types: reset_group(a, na, b, nb, ...) releases all of them, then allocates
+// them in the order given, each exactly its count.  All-or-nothing: the first error is returned and EVERY listed buffer is
+// empty then, so one pointer of a group answers for the rest.  The owner writes whatever describes the group (a point count, a
+// capacity, "have" flags) after it has succeeded, and clears it otherwise.  release_all(a, b, ...) is the one way to drop
+// several buffers at once (a later step of the owner failed).
+template <class... Bufs>
+void release_all(Bufs&... bufs) {
+    (bufs.release(), ...);
+}
+namespace detail {  // the two passes of reset_group over its (buffer, count) pairs
+inline void release_pairs() {}
+template <class T, class... Rest>
+void release_pairs(DevBuf<T>& b, int64_t, Rest&&... rest) {
+    b.release();
+    release_pairs(rest...);
+}
+inline hipError_t reset_pairs() { return hipSuccess; }
+template <class T, class... Rest>
+hipError_t reset_pairs(DevBuf<T>& b, int64_t count, Rest&&... rest) {
+    hipError_t e = b.reset(count);
+    if (e == hipSuccess) e = reset_pairs(rest...);
+    if (e != hipSuccess) b.release();
+    return e;
+}
+}  // namespace detail
+template <class... Pairs>
+hipError_t reset_group(Pairs&&... pairs) {
+    detail::release_pairs(pairs...);
+    return detail::reset_pairs(pairs...);
+}
+
 // Pinned host memory, allocated once and zero-filled; with hipHostMallocMapped in `flags`, `dev` is the address the device
 // reaches it by.
 template <class T>

@@ -13,6 +13,7 @@
 #include <new>
 #include <vector>
 
+#include "dev_buf.h"
 #include "fr_plan.h"
 
 namespace {
@@ -217,42 +218,40 @@ __global__ void k_kin_segsum(const double* __restrict__ part, const int* __restr
 struct Kin {
     int64_t M = 0;
     int K = 0, S = 0, n_chunks = 0;
-    int* ord_plan = nullptr;    // [M] sorted position -> plan position
-    int* ord_caller = nullptr;  // [M] sorted position -> caller's index
-    int2* kp = nullptr;         // [M] node pair, sorted order
-    double2* kw = nullptr;      // [M] weights widened to fp64, sorted order
-    Chunk* chunks = nullptr;    // [n_chunks]
-    int* seg_chunk = nullptr;   // [S + 1]
-    double4* pt = nullptr;      // [M] (moved source, s), sorted order
-    double4* mu = nullptr;      // [M] m1 / m0, sorted order
-    double* part = nullptr;     // [n_chunks][kNrm]
-    double* segsum = nullptr;   // [S][kNrm]
-    double* dq = nullptr;       // [K][8] the model's dual quaternions
-    double* dq_inc = nullptr;   // [K][8] dualquat_from_twist of the inner loop's increments
-    double* tw = nullptr;       // [6 K]
-    double* moved = nullptr;    // [M][4] skinned source, plan order
+    // one group (dev_buf.h: reset_group), created by build_kin for the life of the Kin
+    prg::DevBuf<int> ord_plan;    // [M] sorted position -> plan position
+    prg::DevBuf<int> ord_caller;  // [M] sorted position -> caller's index
+    prg::DevBuf<int2> kp;         // [M] node pair, sorted order
+    prg::DevBuf<double2> kw;      // [M] weights widened to fp64, sorted order
+    prg::DevBuf<Chunk> chunks;    // [n_chunks]
+    prg::DevBuf<int> seg_chunk;   // [S + 1]
+    prg::DevBuf<double4> pt;      // [M] (moved source, s), sorted order
+    prg::DevBuf<double4> mu;      // [M] m1 / m0, sorted order
+    prg::DevBuf<double> part;     // [n_chunks][kNrm]
+    prg::DevBuf<double> segsum;   // [S][kNrm]
+    prg::DevBuf<double> dq;       // [K][8] the model's dual quaternions
+    prg::DevBuf<double> dq_inc;   // [K][8] dualquat_from_twist of the inner loop's increments
+    prg::DevBuf<double> tw;       // [6 K]
+    prg::DevBuf<double> moved;    // [M][4] skinned source, plan order
     std::vector<double> dq_host;
     // E-step values supplied by the caller (prg_fr_kinematic_set_arrays) instead of the plan's last E-step
-    void* arrays = nullptr;
+    prg::DevBuf<char> arrays;  // allocated once
     EstepIn arr_in{};
     int64_t arr_n_target = 0;
     bool use_arrays = false, have_normal = false;
 };
 
-void kin_free(void* p) {
-    Kin* k = (Kin*)p;
-    if (!k) return;
-    for (void* q : {(void*)k->ord_plan, (void*)k->ord_caller, (void*)k->kp, (void*)k->kw, (void*)k->chunks,
-                    (void*)k->seg_chunk, (void*)k->pt, (void*)k->mu, (void*)k->part, (void*)k->segsum, (void*)k->dq,
-                    (void*)k->dq_inc, (void*)k->tw, (void*)k->moved, k->arrays})
-        if (q) (void)hipFree(q);
-    delete k;
+void kin_free(void* p) { delete (Kin*)p; }
+
+// an uploaded array has at least one element
+template <typename T>
+int64_t slots(const std::vector<T>& host) {
+    return (int64_t)std::max<size_t>(host.size(), 1);
 }
 
 template <typename T>
-int upload(T** dev, const std::vector<T>& host, hipStream_t st) {
-    PRG_HIP(hipMalloc((void**)dev, std::max<size_t>(host.size(), 1) * sizeof(T)));
-    if (!host.empty()) PRG_HIP(hipMemcpyAsync(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, st));
+int upload(const prg::DevBuf<T>& dev, const std::vector<T>& host, hipStream_t st) {
+    if (!host.empty()) PRG_HIP(hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, st));
     return PRG_OK;
 }
 
@@ -302,22 +301,19 @@ int build_kin(Kin* k, const prg::FrView& v, const std::vector<int>& pairs, const
     }
     k->S = n_seg;
     k->n_chunks = (int)chunks.size();
-    PRG_TRY(upload(&k->ord_plan, ord_plan, st));
-    PRG_TRY(upload(&k->ord_caller, order, st));
-    PRG_TRY(upload(&k->kp, kp, st));
-    PRG_TRY(upload(&k->kw, kw, st));
-    PRG_TRY(upload(&k->chunks, chunks, st));
-    PRG_TRY(upload(&k->seg_chunk, seg_chunk, st));
-    PRG_HIP(hipMalloc((void**)&k->pt, (size_t)m * sizeof(double4)));
-    PRG_HIP(hipMalloc((void**)&k->mu, (size_t)m * sizeof(double4)));
-    PRG_HIP(hipMalloc((void**)&k->part, (size_t)k->n_chunks * kNrm * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&k->segsum, (size_t)k->S * kNrm * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&k->dq_inc, (size_t)k_nodes * 8 * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&k->tw, (size_t)k_nodes * 6 * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&k->moved, (size_t)m * 4 * sizeof(double)));
     k->dq_host.assign((size_t)k_nodes * 8, 0.0);
     for (int i = 0; i < k_nodes; ++i) k->dq_host[(size_t)i * 8] = 1.0;
-    PRG_TRY(upload(&k->dq, k->dq_host, st));
+    PRG_HIP(prg::reset_group(k->ord_plan, slots(ord_plan), k->ord_caller, slots(order), k->kp, slots(kp), k->kw, slots(kw), k->chunks,
+                             slots(chunks), k->seg_chunk, slots(seg_chunk), k->pt, m, k->mu, m, k->part, (int64_t)k->n_chunks * kNrm,
+                             k->segsum, (int64_t)k->S * kNrm, k->dq_inc, (int64_t)k_nodes * 8, k->tw, (int64_t)k_nodes * 6, k->moved,
+                             m * 4, k->dq, slots(k->dq_host)));
+    PRG_TRY(upload(k->ord_plan, ord_plan, st));
+    PRG_TRY(upload(k->ord_caller, order, st));
+    PRG_TRY(upload(k->kp, kp, st));
+    PRG_TRY(upload(k->kw, kw, st));
+    PRG_TRY(upload(k->chunks, chunks, st));
+    PRG_TRY(upload(k->seg_chunk, seg_chunk, st));
+    PRG_TRY(upload(k->dq, k->dq_host, st));
     PRG_HIP(hipStreamSynchronize(st));  // the host vectors go out of scope
     return PRG_OK;
 }
@@ -326,9 +322,9 @@ Kin* kin_of(const prg::FrView& v) { return (Kin*)*v.kin; }
 
 // segment sums [S][nc] of chunk partials -> host
 int seg_sums_to_host(Kin* k, int nc, hipStream_t st, double* out_host) {
-    k_kin_segsum<<<k->S, 64, 0, st>>>(k->part, k->seg_chunk, nc, k->segsum);
+    k_kin_segsum<<<k->S, 64, 0, st>>>(k->part.p, k->seg_chunk.p, nc, k->segsum.p);
     PRG_HIP(hipGetLastError());
-    PRG_HIP(hipMemcpyAsync(out_host, k->segsum, (size_t)k->S * nc * sizeof(double), hipMemcpyDeviceToHost, st));
+    PRG_HIP(hipMemcpyAsync(out_host, k->segsum.p, (size_t)k->S * nc * sizeof(double), hipMemcpyDeviceToHost, st));
     PRG_HIP(hipStreamSynchronize(st));
     return PRG_OK;
 }
@@ -347,22 +343,19 @@ int prg_dq_skin(int device, void* hip_stream, const double* points_hd, int64_t m
     std::vector<int> pairs((size_t)m * 2);
     PRG_HIP(hipMemcpy(pairs.data(), pairs_hd, pairs.size() * sizeof(int), hipMemcpyDefault));
     PRG_TRY(check_pairs("prg_dq_skin", pairs, k_nodes));
-    struct Tmp {
-        void* p = nullptr;
-        ~Tmp() { if (p) (void)hipFree(p); }
-    } b_pts, b_pairs, b_w, b_dq, b_out;
-    PRG_HIP(hipMalloc(&b_pts.p, (size_t)m * 3 * sizeof(double)));
-    PRG_HIP(hipMalloc(&b_pairs.p, (size_t)m * 2 * sizeof(int)));
-    PRG_HIP(hipMalloc(&b_w.p, (size_t)m * 2 * sizeof(float)));
-    PRG_HIP(hipMalloc(&b_dq.p, (size_t)k_nodes * 8 * sizeof(double)));
-    PRG_HIP(hipMalloc(&b_out.p, (size_t)m * 3 * sizeof(double)));
+    prg::DevBuf<double> b_pts, b_dq, b_out;
+    prg::DevBuf<int> b_pairs;
+    prg::DevBuf<float> b_w;
+    PRG_HIP(b_pts.reset(m * 3));
+    PRG_HIP(b_pairs.reset(m * 2));
+    PRG_HIP(b_w.reset(m * 2));
+    PRG_HIP(b_dq.reset((int64_t)k_nodes * 8));
+    PRG_HIP(b_out.reset(m * 3));
     PRG_HIP(hipMemcpyAsync(b_pts.p, points_hd, (size_t)m * 3 * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(b_pairs.p, pairs.data(), (size_t)m * 2 * sizeof(int), hipMemcpyHostToDevice, st));
     PRG_HIP(hipMemcpyAsync(b_w.p, weights_hd, (size_t)m * 2 * sizeof(float), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(b_dq.p, dualquats_hd, (size_t)k_nodes * 8 * sizeof(double), hipMemcpyDefault, st));
-    k_dq_skin<<<(unsigned)prg::ceil_div(m, kBlock), kBlock, 0, st>>>((const double*)b_pts.p, (const int*)b_pairs.p,
-                                                                     (const float*)b_w.p, (const double*)b_dq.p, m,
-                                                                     (double*)b_out.p);
+    k_dq_skin<<<(unsigned)prg::ceil_div(m, kBlock), kBlock, 0, st>>>(b_pts.p, b_pairs.p, b_w.p, b_dq.p, m, b_out.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipMemcpyAsync(out_hd, b_out.p, (size_t)m * 3 * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipStreamSynchronize(st));
@@ -408,7 +401,7 @@ int prg_fr_set_dualquats(prg_filterreg* h, const double* dualquats_host, int k_n
     PRG_REQUIRE(k_nodes == k->K, PRG_ERR_INVALID, "prg_fr_set_dualquats: %d dual quaternions for %d nodes", k_nodes, k->K);
     prg::DeviceGuard g(v.device);
     k->dq_host.assign(dualquats_host, dualquats_host + (size_t)k_nodes * 8);
-    PRG_HIP(hipMemcpyAsync(k->dq, k->dq_host.data(), k->dq_host.size() * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    PRG_HIP(hipMemcpyAsync(k->dq.p, k->dq_host.data(), k->dq_host.size() * sizeof(double), hipMemcpyHostToDevice, v.stream));
     PRG_HIP(hipStreamSynchronize(v.stream));
     return PRG_OK;
 }
@@ -421,7 +414,7 @@ int prg_fr_get_dualquats(prg_filterreg* h, double* dualquats_host, int k_nodes) 
     PRG_REQUIRE(k, PRG_ERR_STATE, "prg_fr_get_dualquats: set the skinning weights first");
     PRG_REQUIRE(k_nodes == k->K, PRG_ERR_INVALID, "prg_fr_get_dualquats: %d dual quaternions for %d nodes", k_nodes, k->K);
     prg::DeviceGuard g(v.device);
-    PRG_HIP(hipMemcpyAsync(dualquats_host, k->dq, (size_t)k_nodes * 8 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    PRG_HIP(hipMemcpyAsync(dualquats_host, k->dq.p, (size_t)k_nodes * 8 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
     PRG_HIP(hipStreamSynchronize(v.stream));
     return PRG_OK;
 }
@@ -434,7 +427,7 @@ int prg_fr_kinematic_estep(prg_filterreg* h, double sigma2, double alpha, int* l
     Kin* k = kin_of(v);
     PRG_REQUIRE(k && v.have_src && v.have_tgt, PRG_ERR_STATE, "prg_fr_kinematic_estep: clouds or skinning weights not set");
     prg::DeviceGuard g(v.device);
-    k_kin_skin<<<(unsigned)prg::ceil_div(k->M, kBlock), kBlock, 0, v.stream>>>(v.src, k->ord_plan, k->kp, k->kw, k->dq, k->M, k->moved);
+    k_kin_skin<<<(unsigned)prg::ceil_div(k->M, kBlock), kBlock, 0, v.stream>>>(v.src, k->ord_plan.p, k->kp.p, k->kw.p, k->dq.p, k->M, k->moved.p);
     PRG_HIP(hipGetLastError());
     // the embedding applies the plan's rigid state to what it is given: the identity here, the skinned cloud passes unchanged
     const double st13[13] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, sigma2};
@@ -442,7 +435,7 @@ int prg_fr_kinematic_estep(prg_filterreg* h, double sigma2, double alpha, int* l
     PRG_HIP(hipStreamSynchronize(v.stream));
     k->use_arrays = false;
     k->have_normal = false;
-    return prg::fr_estep_moved(h, k->moved, alpha, lattice_size, with_blur);
+    return prg::fr_estep_moved(h, k->moved.p, alpha, lattice_size, with_blur);
 }
 
 int prg_fr_kinematic_set_arrays(prg_filterreg* h, const double* t_source_hd, const float* m0_hd, const float* m1_hd,
@@ -458,8 +451,8 @@ int prg_fr_kinematic_set_arrays(prg_filterreg* h, const double* t_source_hd, con
     // staging: t_source [m][3] f64 | m0 [m] | m1 [m][3] | m2 [m]
     const size_t o_m0 = m * 3 * sizeof(double), o_m1 = o_m0 + m * sizeof(float), o_m2 = o_m1 + m * 3 * sizeof(float),
                  total = o_m2 + m * sizeof(float);
-    if (!k->arrays) PRG_HIP(hipMalloc(&k->arrays, total));
-    char* a = (char*)k->arrays;
+    PRG_HIP(k->arrays.ensure((int64_t)total, (int64_t)total));
+    char* a = k->arrays.p;
     PRG_HIP(hipMemcpyAsync(a, t_source_hd, m * 3 * sizeof(double), hipMemcpyDefault, v.stream));
     PRG_HIP(hipMemcpyAsync(a + o_m0, m0_hd, m * sizeof(float), hipMemcpyDefault, v.stream));
     PRG_HIP(hipMemcpyAsync(a + o_m1, m1_hd, m * 3 * sizeof(float), hipMemcpyDefault, v.stream));
@@ -486,15 +479,15 @@ int prg_fr_kinematic_normal_sums(prg_filterreg* h, double sigma2, double w, int 
     PRG_REQUIRE(n_segments == k->S, PRG_ERR_INVALID, "prg_fr_kinematic_normal_sums: %d segments expected, the plan has %d", n_segments, k->S);
     prg::DeviceGuard g(v.device);
     EstepIn in = k->arr_in;
-    const int* ord = k->ord_caller;
+    const int* ord = k->ord_caller.p;
     int64_t n_target = k->arr_n_target;
     if (!k->use_arrays) {
         in = EstepIn{v.ts, 4, v.vout, v.ch, v.vout + 1, v.ch, v.vout + 4, v.ch};
-        ord = k->ord_plan;
+        ord = k->ord_plan.p;
         n_target = v.N;
     }
     const double c = w / (1.0 - w) * (double)n_target / (double)k->M;  // filterreg.py:222 (no (2 pi sigma2)^(3/2), sic)
-    k_kin_normal<<<k->n_chunks, kBlock, 0, v.stream>>>(k->chunks, ord, in, k->kw, c, sigma2, reference_form, k->pt, k->mu, k->part);
+    k_kin_normal<<<k->n_chunks, kBlock, 0, v.stream>>>(k->chunks.p, ord, in, k->kw.p, c, sigma2, reference_form, k->pt.p, k->mu.p, k->part.p);
     PRG_HIP(hipGetLastError());
     k->have_normal = true;
     return seg_sums_to_host(k, kNrm, v.stream, out_host);
@@ -509,9 +502,9 @@ int prg_fr_kinematic_grad_sums(prg_filterreg* h, const double* twists_host, int 
     PRG_REQUIRE(k && k->have_normal, PRG_ERR_STATE, "prg_fr_kinematic_grad_sums: run prg_fr_kinematic_normal_sums first");
     PRG_REQUIRE(n_segments == k->S, PRG_ERR_INVALID, "prg_fr_kinematic_grad_sums: %d segments expected, the plan has %d", n_segments, k->S);
     prg::DeviceGuard g(v.device);
-    PRG_HIP(hipMemcpyAsync(k->tw, twists_host, (size_t)k->K * 6 * sizeof(double), hipMemcpyHostToDevice, v.stream));
-    k_dq_from_twist<<<(unsigned)prg::ceil_div(k->K, 64), 64, 0, v.stream>>>(k->tw, k->K, k->dq_inc);
-    k_kin_grad<<<k->n_chunks, kBlock, 0, v.stream>>>(k->chunks, k->pt, k->mu, k->kp, k->kw, k->dq_inc, reference_form, k->part);
+    PRG_HIP(hipMemcpyAsync(k->tw.p, twists_host, (size_t)k->K * 6 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    k_dq_from_twist<<<(unsigned)prg::ceil_div(k->K, 64), 64, 0, v.stream>>>(k->tw.p, k->K, k->dq_inc.p);
+    k_kin_grad<<<k->n_chunks, kBlock, 0, v.stream>>>(k->chunks.p, k->pt.p, k->mu.p, k->kp.p, k->kw.p, k->dq_inc.p, reference_form, k->part.p);
     PRG_HIP(hipGetLastError());
     return seg_sums_to_host(k, kGrd, v.stream, out_host);
 }

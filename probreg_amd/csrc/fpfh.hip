@@ -33,6 +33,7 @@
 #include <new>
 #include <vector>
 
+#include "dev_buf.h"
 #include "prg_common.h"
 
 namespace prg {
@@ -471,16 +472,11 @@ __global__ __launch_bounds__(kWave) void k_fpfh(const double* __restrict__ spfh,
     }
 }
 
-template <typename T>
-void free_dev(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
+// one group (dev_buf.h: reset_group): idx and d2 are [n][k], cnt is [n]; k and valid are written once a search has filled them
 struct NeighbourLists {
-    int* idx = nullptr;
-    double* d2 = nullptr;
-    int* cnt = nullptr;
+    prg::DevBuf<int> idx;
+    prg::DevBuf<double> d2;
+    prg::DevBuf<int> cnt;
     int k = 0;
     bool valid = false;
 };
@@ -491,47 +487,21 @@ struct prg_fpfh {
     int device = 0;
     hipStream_t stream = nullptr;
     int64_t n = 0;
-    double4* pts = nullptr;
+    prg::DevBuf<double4> pts;  // the cloud group: pts [n], normals [n][3], spfh and fpfh [n][kBins]; n says whether it is there
     double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0};
     NeighbourLists nb[2];  // 0: normals, 1: features
-    double *normals = nullptr, *spfh = nullptr, *fpfh = nullptr;
+    prg::DevBuf<double> normals, spfh, fpfh;
     bool have_normals = false, have_spfh = false, have_fpfh = false;
 };
 
 namespace {
 
-void free_lists(NeighbourLists& l) {
-    free_dev(l.idx);
-    free_dev(l.d2);
-    free_dev(l.cnt);
-    l.k = 0;
-    l.valid = false;
-}
-
-void free_cloud(prg_fpfh* h) {
-    free_dev(h->pts);
-    free_lists(h->nb[0]);
-    free_lists(h->nb[1]);
-    free_dev(h->normals);
-    free_dev(h->spfh);
-    free_dev(h->fpfh);
-    h->have_normals = h->have_spfh = h->have_fpfh = false;
-    h->n = 0;
-}
-
 struct GridScratch {
-    unsigned* keys = nullptr;  // 2 n: unsorted, sorted
-    int* vals = nullptr;       // 2 n: iota, order
-    int* cells = nullptr;      // 2 table: begin, end
-    double4* sp = nullptr;
-    void* tmp = nullptr;
-    ~GridScratch() {
-        free_dev(keys);
-        free_dev(vals);
-        free_dev(cells);
-        free_dev(sp);
-        if (tmp) (void)hipFree(tmp);
-    }
+    prg::DevBuf<unsigned> keys;  // 2 n: unsorted, sorted
+    prg::DevBuf<int> vals;       // 2 n: iota, order
+    prg::DevBuf<int> cells;      // 2 table: begin, end
+    prg::DevBuf<double4> sp;
+    prg::DevBuf<char> tmp;
 };
 
 int run_search(prg_fpfh* h, NeighbourLists& out, double radius, int k) {
@@ -552,21 +522,24 @@ int run_search(prg_fpfh* h, NeighbourLists& out, double radius, int k) {
     g.dense = cells <= (double)table ? 1 : 0;
 
     GridScratch s;
-    PRG_HIP(hipMalloc((void**)&s.keys, 2 * (size_t)n * sizeof(unsigned)));
-    PRG_HIP(hipMalloc((void**)&s.vals, 2 * (size_t)n * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&s.cells, 2 * (size_t)table * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&s.sp, (size_t)n * sizeof(double4)));
+    PRG_HIP(s.keys.reset(2 * (int64_t)n));
+    PRG_HIP(s.vals.reset(2 * (int64_t)n));
+    PRG_HIP(s.cells.reset(2 * table));
+    PRG_HIP(s.sp.reset(n));
+    unsigned* const keys = s.keys.p;
+    int* const vals = s.vals.p;
+    int* const cbegin = s.cells.p;
     size_t need = 0;
-    PRG_TRY(prg::sort_pairs_u32(nullptr, &need, s.keys, s.keys + n, s.vals, s.vals + n, (unsigned)n, bits, st));
-    PRG_HIP(hipMalloc(&s.tmp, need + 256));
+    PRG_TRY(prg::sort_pairs_u32(nullptr, &need, keys, keys + n, vals, vals + n, (unsigned)n, bits, st));
+    PRG_HIP(s.tmp.reset((int64_t)need + 256));
     const unsigned nbk = (unsigned)prg::ceil_div(n, kBlock);
-    k_cell_keys<<<nbk, kBlock, 0, st>>>(h->pts, n, g, s.keys, s.vals);
+    k_cell_keys<<<nbk, kBlock, 0, st>>>(h->pts.p, n, g, keys, vals);
     PRG_HIP(hipGetLastError());
-    PRG_TRY(prg::sort_pairs_u32(s.tmp, &need, s.keys, s.keys + n, s.vals, s.vals + n, (unsigned)n, bits, st));
-    PRG_HIP(hipMemsetAsync(s.cells, 0, 2 * (size_t)table * sizeof(int), st));
-    k_cell_bounds<<<nbk, kBlock, 0, st>>>(h->pts, s.keys + n, s.vals + n, n, s.sp, s.cells, s.cells + table);
+    PRG_TRY(prg::sort_pairs_u32(s.tmp.p, &need, keys, keys + n, vals, vals + n, (unsigned)n, bits, st));
+    PRG_HIP(hipMemsetAsync(cbegin, 0, 2 * (size_t)table * sizeof(int), st));
+    k_cell_bounds<<<nbk, kBlock, 0, st>>>(h->pts.p, keys + n, vals + n, n, s.sp.p, cbegin, cbegin + table);
     PRG_HIP(hipGetLastError());
-    k_search<<<(unsigned)n, kWave, 0, st>>>(s.sp, s.cells, s.cells + table, g, radius, k, out.idx, out.d2, out.cnt);
+    k_search<<<(unsigned)n, kWave, 0, st>>>(s.sp.p, cbegin, cbegin + table, g, radius, k, out.idx.p, out.d2.p, out.cnt.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(st));  // the scratch goes away with this scope
     return PRG_OK;
@@ -593,7 +566,6 @@ int prg_fpfh_destroy(prg_fpfh* h) {
     if (!h) return PRG_OK;
     prg::DeviceGuard g(h->device);
     (void)hipStreamSynchronize(h->stream);
-    free_cloud(h);
     delete h;
     return PRG_OK;
 }
@@ -621,14 +593,17 @@ int prg_fpfh_set_data(prg_fpfh* h, const double* points_hd, int64_t n) {
             hi[a] = std::max(hi[a], v);
         }
     PRG_HIP(hipStreamSynchronize(h->stream));
-    free_cloud(h);
-    hipError_t e = hipMalloc((void**)&h->pts, (size_t)n * sizeof(double4));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->normals, (size_t)n * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->spfh, (size_t)n * kBins * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->fpfh, (size_t)n * kBins * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(h->pts, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    h->n = 0;
+    h->have_normals = h->have_spfh = h->have_fpfh = false;
+    for (NeighbourLists& l : h->nb) {
+        prg::release_all(l.idx, l.d2, l.cnt);
+        l.k = 0;
+        l.valid = false;
+    }
+    hipError_t e = prg::reset_group(h->pts, n, h->normals, n * 3, h->spfh, n * kBins, h->fpfh, n * kBins);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->pts.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) free_cloud(h);  // no half-built cloud: the handle is back to "no data"
+    if (e != hipSuccess) prg::release_all(h->pts, h->normals, h->spfh, h->fpfh);  // no half-built cloud: back to "no data"
     PRG_HIP(e);
     h->n = n;
     for (int a = 0; a < 3; ++a) {
@@ -644,24 +619,21 @@ int prg_fpfh_search(prg_fpfh* h, int which, double radius, int max_nn) {
     PRG_REQUIRE(radius > 0.0 && std::isfinite(radius), PRG_ERR_INVALID, "prg_fpfh_search: radius must be > 0 and finite");
     PRG_REQUIRE(max_nn >= 1 && max_nn <= kMaxNN, PRG_ERR_INVALID, "prg_fpfh_search: max_nn must lie in 1 .. %d, got %d",
                 kMaxNN, max_nn);
-    PRG_REQUIRE(h->pts != nullptr, PRG_ERR_STATE, "prg_fpfh_search: no data (prg_fpfh_set_data first)");
+    PRG_REQUIRE(h->pts.p != nullptr, PRG_ERR_STATE, "prg_fpfh_search: no data (prg_fpfh_set_data first)");
     prg::DeviceGuard g(h->device);
     NeighbourLists& l = h->nb[which];
     PRG_HIP(hipStreamSynchronize(h->stream));
-    free_lists(l);
+    l.k = 0;
+    l.valid = false;
     if (which == 1) h->have_spfh = h->have_fpfh = false;
-    const size_t slots = (size_t)h->n * (size_t)max_nn;
-    hipError_t e = hipMalloc((void**)&l.idx, slots * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&l.d2, slots * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&l.cnt, (size_t)h->n * sizeof(int));
-    if (e != hipSuccess) free_lists(l);
-    PRG_HIP(e);
-    l.k = max_nn;
+    const int64_t slots = h->n * max_nn;
+    PRG_HIP(prg::reset_group(l.idx, slots, l.d2, slots, l.cnt, h->n));
     const int st = run_search(h, l, radius, max_nn);
     if (st != PRG_OK) {
-        free_lists(l);
+        prg::release_all(l.idx, l.d2, l.cnt);
         return st;
     }
+    l.k = max_nn;
     l.valid = true;
     return PRG_OK;
 }
@@ -674,9 +646,9 @@ int prg_fpfh_get_neighbours(prg_fpfh* h, int which, int* idx_host, double* d2_ho
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     const size_t slots = (size_t)h->n * (size_t)l.k;
-    if (idx_host) PRG_HIP(hipMemcpy(idx_host, l.idx, slots * sizeof(int), hipMemcpyDeviceToHost));
-    if (d2_host) PRG_HIP(hipMemcpy(d2_host, l.d2, slots * sizeof(double), hipMemcpyDeviceToHost));
-    if (count_host) PRG_HIP(hipMemcpy(count_host, l.cnt, (size_t)h->n * sizeof(int), hipMemcpyDeviceToHost));
+    if (idx_host) PRG_HIP(hipMemcpy(idx_host, l.idx.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+    if (d2_host) PRG_HIP(hipMemcpy(d2_host, l.d2.p, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (count_host) PRG_HIP(hipMemcpy(count_host, l.cnt.p, (size_t)h->n * sizeof(int), hipMemcpyDeviceToHost));
     return PRG_OK;
 }
 
@@ -684,7 +656,7 @@ int prg_fpfh_normals(prg_fpfh* h) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_normals: NULL argument");
     PRG_REQUIRE(h->nb[0].valid, PRG_ERR_STATE, "prg_fpfh_normals: prg_fpfh_search(0, ...) first");
     prg::DeviceGuard g(h->device);
-    k_normals<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts, h->nb[0].idx, h->nb[0].cnt, h->nb[0].k, h->normals);
+    k_normals<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts.p, h->nb[0].idx.p, h->nb[0].cnt.p, h->nb[0].k, h->normals.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_normals = true;
@@ -694,10 +666,10 @@ int prg_fpfh_normals(prg_fpfh* h) {
 
 int prg_fpfh_set_normals(prg_fpfh* h, const double* normals_hd) {
     PRG_REQUIRE(h && normals_hd, PRG_ERR_INVALID, "prg_fpfh_set_normals: NULL argument");
-    PRG_REQUIRE(h->pts != nullptr, PRG_ERR_STATE, "prg_fpfh_set_normals: no data (prg_fpfh_set_data first)");
+    PRG_REQUIRE(h->pts.p != nullptr, PRG_ERR_STATE, "prg_fpfh_set_normals: no data (prg_fpfh_set_data first)");
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(h->normals, normals_hd, (size_t)h->n * 3 * sizeof(double), hipMemcpyDefault));
+    PRG_HIP(hipMemcpy(h->normals.p, normals_hd, (size_t)h->n * 3 * sizeof(double), hipMemcpyDefault));
     h->have_normals = true;
     h->have_spfh = h->have_fpfh = false;
     return PRG_OK;
@@ -708,7 +680,7 @@ int prg_fpfh_get_normals(prg_fpfh* h, double* normals_host) {
     PRG_REQUIRE(h->have_normals, PRG_ERR_STATE, "prg_fpfh_get_normals: prg_fpfh_normals or prg_fpfh_set_normals first");
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(normals_host, h->normals, (size_t)h->n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_HIP(hipMemcpy(normals_host, h->normals.p, (size_t)h->n * 3 * sizeof(double), hipMemcpyDeviceToHost));
     return PRG_OK;
 }
 
@@ -717,7 +689,7 @@ int prg_fpfh_spfh(prg_fpfh* h) {
     PRG_REQUIRE(h->nb[1].valid, PRG_ERR_STATE, "prg_fpfh_spfh: prg_fpfh_search(1, ...) first");
     PRG_REQUIRE(h->have_normals, PRG_ERR_STATE, "prg_fpfh_spfh: prg_fpfh_normals or prg_fpfh_set_normals first");
     prg::DeviceGuard g(h->device);
-    k_spfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts, h->normals, h->nb[1].idx, h->nb[1].cnt, h->nb[1].k, h->spfh);
+    k_spfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts.p, h->normals.p, h->nb[1].idx.p, h->nb[1].cnt.p, h->nb[1].k, h->spfh.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_spfh = true;
@@ -730,7 +702,7 @@ int prg_fpfh_get_spfh(prg_fpfh* h, double* spfh_host) {
     PRG_REQUIRE(h->have_spfh, PRG_ERR_STATE, "prg_fpfh_get_spfh: prg_fpfh_spfh first");
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(spfh_host, h->spfh, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_HIP(hipMemcpy(spfh_host, h->spfh.p, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
     return PRG_OK;
 }
 
@@ -738,7 +710,7 @@ int prg_fpfh_fpfh(prg_fpfh* h) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_fpfh: NULL argument");
     PRG_REQUIRE(h->have_spfh && h->nb[1].valid, PRG_ERR_STATE, "prg_fpfh_fpfh: prg_fpfh_spfh first");
     prg::DeviceGuard g(h->device);
-    k_fpfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->spfh, h->nb[1].idx, h->nb[1].d2, h->nb[1].cnt, h->nb[1].k, h->fpfh);
+    k_fpfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->spfh.p, h->nb[1].idx.p, h->nb[1].d2.p, h->nb[1].cnt.p, h->nb[1].k, h->fpfh.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_fpfh = true;
@@ -750,7 +722,7 @@ int prg_fpfh_get_fpfh(prg_fpfh* h, double* fpfh_host) {
     PRG_REQUIRE(h->have_fpfh, PRG_ERR_STATE, "prg_fpfh_get_fpfh: prg_fpfh_fpfh first");
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(fpfh_host, h->fpfh, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_HIP(hipMemcpy(fpfh_host, h->fpfh.p, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
     return PRG_OK;
 }
 

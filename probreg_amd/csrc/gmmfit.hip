@@ -25,6 +25,7 @@
 #include <new>
 #include <vector>
 
+#include "dev_buf.h"
 #include "prg_common.h"
 
 namespace {
@@ -406,38 +407,18 @@ struct prg_gmmfit {
     int dim = 0;
     int k = 0;            // components of the current parameters / centres
     bool have_centers = false, have_labels = false, have_params = false, have_cov = false;
-    double4* xs = nullptr;
-    double *lse = nullptr, *mind2 = nullptr, *qpart = nullptr, *seed_part = nullptr, *seed_pre = nullptr;
-    int* labels = nullptr;
-    // per component (capacity k_cap)
-    int k_cap = 0;
-    int64_t part_cap = 0;
-    double *w = nullptr, *mu = nullptr, *cov = nullptr, *nk = nullptr, *rec = nullptr, *mom = nullptr, *shift = nullptr;
-    double *part = nullptr, *unif = nullptr;
-    int *centers = nullptr, *cand = nullptr;
-    double* scal = nullptr;  // [0] lower-bound sum, [1] sum nk, [2] centre shift
-    int* n_changed = nullptr;
+    // the points group (dev_buf.h: reset_group), sized by n: all there or none, and n, dim say which
+    prg::DevBuf<double4> xs;
+    prg::DevBuf<double> lse, mind2, qpart, seed_part, seed_pre;
+    prg::DevBuf<int> labels;
+    // the component group, sized together: the capacity in components is w.cap, that of the moment partials part.cap
+    prg::DevBuf<double> w, mu, cov, nk, rec, mom, shift, part, unif;
+    prg::DevBuf<int> centers, cand;
+    prg::DevBuf<double> scal;  // [0] lower-bound sum, [1] sum nk, [2] centre shift; allocated once, as is n_changed
+    prg::DevBuf<int> n_changed;
 };
 
 namespace {
-
-template <typename T>
-void free_dev(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-void free_points(prg_gmmfit* h) {
-    free_dev(h->xs); free_dev(h->lse); free_dev(h->mind2); free_dev(h->qpart); free_dev(h->seed_part);
-    free_dev(h->seed_pre); free_dev(h->labels);
-}
-
-void free_comps(prg_gmmfit* h) {
-    free_dev(h->w); free_dev(h->mu); free_dev(h->cov); free_dev(h->nk); free_dev(h->rec); free_dev(h->mom);
-    free_dev(h->shift); free_dev(h->part); free_dev(h->unif); free_dev(h->centers); free_dev(h->cand);
-    h->k_cap = 0;
-    h->part_cap = 0;
-}
 
 // points per chunk of the moment sweep: a multiple of kCompBlock, at most kMaxMomChunks chunks
 int mom_chunk(int64_t n) {
@@ -448,56 +429,48 @@ int mom_chunk(int64_t n) {
 int ensure_comps(prg_gmmfit* h, int k) {
     const int64_t n_chunks = prg::ceil_div(h->n, mom_chunk(h->n));
     const int64_t need = n_chunks * kMom * (int64_t)k;
-    if (k <= h->k_cap && need <= h->part_cap) return PRG_OK;
+    if (k <= h->w.cap && need <= h->part.cap) return PRG_OK;
     PRG_HIP(hipStreamSynchronize(h->stream));
-    free_comps(h);
-    PRG_HIP(hipMalloc((void**)&h->w, (size_t)k * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->mu, (size_t)k * 3 * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->cov, (size_t)k * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->nk, (size_t)k * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->rec, (size_t)k * kRec * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->mom, (size_t)k * kMom * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->shift, (size_t)k * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->part, (size_t)need * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->unif, (size_t)k * kMaxTrials * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->centers, (size_t)k * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&h->cand, kMaxTrials * sizeof(int)));
-    h->k_cap = k;
-    h->part_cap = need;
-    h->have_centers = h->have_params = h->have_cov = false;
+    // what the group held goes, whether its successor arrives or not - and with it the labels' use: the moments of the labels
+    // are written into this group (both callers drop the labels on success as well)
+    h->have_centers = h->have_labels = h->have_params = h->have_cov = false;
+    h->k = 0;
+    const int64_t kk = k;
+    PRG_HIP(prg::reset_group(h->w, kk, h->mu, kk * 3, h->cov, kk, h->nk, kk, h->rec, kk * kRec, h->mom, kk * kMom, h->shift, kk,
+                             h->part, need, h->unif, kk * kMaxTrials, h->centers, kk, h->cand, kMaxTrials));
     return PRG_OK;
 }
 
-// label (ONE_HOT) or responsibility moments of all components -> h->mom
+// label (ONE_HOT) or responsibility moments of all components -> h->mom.p
 template <bool ONE_HOT>
 int moments(prg_gmmfit* h) {
     const int chunk = mom_chunk(h->n);
     const int n_chunks = (int)prg::ceil_div(h->n, chunk);
     const dim3 grid((unsigned)n_chunks, (unsigned)prg::ceil_div(h->k, kCompBlock));
-    k_moments<ONE_HOT><<<grid, kCompBlock, 0, h->stream>>>(h->xs, h->n, chunk, h->rec, h->lse, h->labels, h->k, h->part);
+    k_moments<ONE_HOT><<<grid, kCompBlock, 0, h->stream>>>(h->xs.p, h->n, chunk, h->rec.p, h->lse.p, h->labels.p, h->k, h->part.p);
     PRG_HIP(hipGetLastError());
-    k_moments_sum<<<(unsigned)prg::ceil_div((int64_t)h->k * 7, kBlock), kBlock, 0, h->stream>>>(h->part, n_chunks, h->k,
-                                                                                              h->mom);
+    k_moments_sum<<<(unsigned)prg::ceil_div((int64_t)h->k * 7, kBlock), kBlock, 0, h->stream>>>(h->part.p, n_chunks, h->k,
+                                                                                              h->mom.p);
     PRG_HIP(hipGetLastError());
     return PRG_OK;
 }
 
-// M-step from h->mom: parameters and records
+// M-step from h->mom.p: parameters and records
 int mstep(prg_gmmfit* h, double reg_covar, int mode) {
     const unsigned kb = (unsigned)prg::ceil_div(h->k, kBlock);
-    k_mstep<<<kb, kBlock, 0, h->stream>>>(h->mom, h->k, h->dim, reg_covar, h->nk, h->mu, h->cov);
+    k_mstep<<<kb, kBlock, 0, h->stream>>>(h->mom.p, h->k, h->dim, reg_covar, h->nk.p, h->mu.p, h->cov.p);
     PRG_HIP(hipGetLastError());
-    k_sum<<<1, kChooseThreads, 0, h->stream>>>(h->nk, h->k, h->scal + 1);
+    k_sum<<<1, kChooseThreads, 0, h->stream>>>(h->nk.p, h->k, h->scal.p + 1);
     PRG_HIP(hipGetLastError());
-    k_records<<<kb, kBlock, 0, h->stream>>>(h->nk, h->scal + 1, (double)h->n, mode, h->mu, h->cov, h->k, h->dim, h->w,
-                                            h->rec);
+    k_records<<<kb, kBlock, 0, h->stream>>>(h->nk.p, h->scal.p + 1, (double)h->n, mode, h->mu.p, h->cov.p, h->k, h->dim, h->w.p,
+                                            h->rec.p);
     PRG_HIP(hipGetLastError());
     h->have_params = h->have_cov = true;
     return PRG_OK;
 }
 
 int check_k(prg_gmmfit* h, int k, const char* who) {
-    PRG_REQUIRE(h->xs != nullptr, PRG_ERR_STATE, "%s: no data (prg_gmmfit_set_data first)", who);
+    PRG_REQUIRE(h->xs.p != nullptr, PRG_ERR_STATE, "%s: no data (prg_gmmfit_set_data first)", who);
     PRG_REQUIRE(k >= 1, PRG_ERR_INVALID, "%s: need at least one component", who);
     PRG_REQUIRE((int64_t)k <= h->n, PRG_ERR_INVALID, "%s: %d components for %lld points (need n_components <= n_samples)",
                 who, k, (long long)h->n);
@@ -525,10 +498,6 @@ int prg_gmmfit_destroy(prg_gmmfit* h) {
     if (!h) return PRG_OK;
     prg::DeviceGuard g(h->device);
     (void)hipStreamSynchronize(h->stream);
-    free_points(h);
-    free_comps(h);
-    free_dev(h->scal);
-    free_dev(h->n_changed);
     delete h;
     return PRG_OK;
 }
@@ -539,29 +508,28 @@ int prg_gmmfit_set_data(prg_gmmfit* h, const double* data_hd, int64_t n, int dim
     PRG_REQUIRE(n >= 1 && n < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_gmmfit_set_data: need 1 <= n < 2^31 points");
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
-    free_points(h);
-    free_comps(h);
-    h->n = n;
-    h->dim = dim;
+    h->n = 0;
+    h->dim = 0;
     h->k = 0;
     h->have_centers = h->have_labels = h->have_params = h->have_cov = false;
+    prg::release_all(h->w, h->mu, h->cov, h->nk, h->rec, h->mom, h->shift, h->part, h->unif, h->centers, h->cand);
     const int64_t nb = prg::ceil_div(n, kBlock);
-    PRG_HIP(hipMalloc((void**)&h->xs, (size_t)n * sizeof(double4)));
-    PRG_HIP(hipMalloc((void**)&h->lse, (size_t)n * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->mind2, (size_t)n * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->labels, (size_t)n * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&h->qpart, (size_t)nb * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->seed_part, (size_t)nb * kMaxTrials * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->seed_pre, (size_t)nb * sizeof(double)));
-    if (!h->scal) PRG_HIP(hipMalloc((void**)&h->scal, 4 * sizeof(double)));
-    if (!h->n_changed) PRG_HIP(hipMalloc((void**)&h->n_changed, sizeof(int)));
+    hipError_t e = prg::reset_group(h->xs, n, h->lse, n, h->mind2, n, h->labels, n, h->qpart, nb, h->seed_part, nb * kMaxTrials,
+                                    h->seed_pre, nb);
+    if (e == hipSuccess) e = h->scal.ensure(4, 4);
+    if (e == hipSuccess) e = h->n_changed.ensure(1, 1);
     // padded layout (x, y, z or 0, 0): 2-D clouds run through the same kernels with z = 0 on both sides
     std::vector<double> raw((size_t)n * dim), pad((size_t)n * 4, 0.0);
-    PRG_HIP(hipMemcpy(raw.data(), data_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    if (e == hipSuccess) e = hipMemcpy(raw.data(), data_hd, raw.size() * sizeof(double), hipMemcpyDefault);
     for (int64_t i = 0; i < n; ++i)
         for (int d = 0; d < dim; ++d) pad[(size_t)i * 4 + d] = raw[(size_t)i * dim + d];
-    PRG_HIP(hipMemcpyAsync(h->xs, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PRG_HIP(hipStreamSynchronize(h->stream));
+    if (e == hipSuccess) e = hipMemcpyAsync(h->xs.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess)  // no half-built cloud: the handle is back to "no data"
+        prg::release_all(h->xs, h->lse, h->mind2, h->labels, h->qpart, h->seed_part, h->seed_pre);
+    PRG_HIP(e);
+    h->n = n;
+    h->dim = dim;
     return PRG_OK;
 }
 
@@ -580,21 +548,21 @@ int prg_gmmfit_seed(prg_gmmfit* h, int k, const double* uniforms_host, int n_tri
     const unsigned nb = (unsigned)prg::ceil_div(n, kBlock);
     // the first centre is uniform over the points
     const int first = (int)std::min<int64_t>((int64_t)(uniforms_host[0] * (double)n), n - 1);
-    PRG_HIP(hipMemcpyAsync(h->centers, &first, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    PRG_HIP(hipMemcpyAsync(h->unif, uniforms_host, (size_t)k * n_trials * sizeof(double), hipMemcpyHostToDevice,
+    PRG_HIP(hipMemcpyAsync(h->centers.p, &first, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    PRG_HIP(hipMemcpyAsync(h->unif.p, uniforms_host, (size_t)k * n_trials * sizeof(double), hipMemcpyHostToDevice,
                            h->stream));
-    k_fill<<<nb, kBlock, 0, h->stream>>>(h->mind2, n, INFINITY);
+    k_fill<<<nb, kBlock, 0, h->stream>>>(h->mind2.p, n, INFINITY);
     PRG_HIP(hipGetLastError());
     for (int s = 0; s < k; ++s) {
         const int ncand = s == 0 ? 0 : n_trials;
-        k_seed_sweep<<<nb, kBlock, 0, h->stream>>>(h->xs, n, h->centers, s == 0 ? 0 : s - 1, h->cand, ncand, h->mind2,
-                                                   h->seed_part);
+        k_seed_sweep<<<nb, kBlock, 0, h->stream>>>(h->xs.p, n, h->centers.p, s == 0 ? 0 : s - 1, h->cand.p, ncand, h->mind2.p,
+                                                   h->seed_part.p);
         PRG_HIP(hipGetLastError());
-        k_seed_choose<<<1, kChooseThreads, 0, h->stream>>>(h->xs, n, h->mind2, h->seed_part, (int)nb, ncand, h->cand,
-                                                           h->centers, s, k, h->unif, n_trials, h->seed_pre);
+        k_seed_choose<<<1, kChooseThreads, 0, h->stream>>>(h->xs.p, n, h->mind2.p, h->seed_part.p, (int)nb, ncand, h->cand.p,
+                                                           h->centers.p, s, k, h->unif.p, n_trials, h->seed_pre.p);
         PRG_HIP(hipGetLastError());
     }
-    k_gather_centers<<<(unsigned)prg::ceil_div(k, kBlock), kBlock, 0, h->stream>>>(h->xs, h->centers, k, h->mu);
+    k_gather_centers<<<(unsigned)prg::ceil_div(k, kBlock), kBlock, 0, h->stream>>>(h->xs.p, h->centers.p, k, h->mu.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));  // uniforms_host and `first` may be released
     h->have_centers = true;
@@ -604,9 +572,9 @@ int prg_gmmfit_seed(prg_gmmfit* h, int k, const double* uniforms_host, int n_tri
 
 int prg_gmmfit_get_seeds(prg_gmmfit* h, int* index_host) {
     PRG_REQUIRE(h && index_host, PRG_ERR_INVALID, "prg_gmmfit_get_seeds: NULL argument");
-    PRG_REQUIRE(h->have_centers && h->centers, PRG_ERR_STATE, "prg_gmmfit_get_seeds: prg_gmmfit_seed first");
+    PRG_REQUIRE(h->have_centers && h->centers.p, PRG_ERR_STATE, "prg_gmmfit_get_seeds: prg_gmmfit_seed first");
     prg::DeviceGuard g(h->device);
-    PRG_HIP(hipMemcpyAsync(index_host, h->centers, (size_t)h->k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipMemcpyAsync(index_host, h->centers.p, (size_t)h->k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }
@@ -618,23 +586,23 @@ int prg_gmmfit_lloyd(prg_gmmfit* h, int max_iter, double tol, int* n_iter_host) 
     prg::DeviceGuard g(h->device);
     const int64_t n = h->n;
     const unsigned nb = (unsigned)prg::ceil_div(n, kBlock), kb = (unsigned)prg::ceil_div(h->k, kBlock);
-    PRG_HIP(hipMemsetAsync(h->labels, 0xFF, (size_t)n * sizeof(int), h->stream));  // -1: every label changes first
+    PRG_HIP(hipMemsetAsync(h->labels.p, 0xFF, (size_t)n * sizeof(int), h->stream));  // -1: every label changes first
     bool strict = false;
     int it = 0;
     while (it < max_iter) {
         ++it;
-        PRG_HIP(hipMemsetAsync(h->n_changed, 0, sizeof(int), h->stream));
-        k_assign<<<nb, kBlock, 0, h->stream>>>(h->xs, n, h->mu, h->k, h->labels, h->n_changed);
+        PRG_HIP(hipMemsetAsync(h->n_changed.p, 0, sizeof(int), h->stream));
+        k_assign<<<nb, kBlock, 0, h->stream>>>(h->xs.p, n, h->mu.p, h->k, h->labels.p, h->n_changed.p);
         PRG_HIP(hipGetLastError());
         PRG_TRY(moments<true>(h));
-        k_lloyd_update<<<kb, kBlock, 0, h->stream>>>(h->mom, h->k, h->mu, h->shift);
+        k_lloyd_update<<<kb, kBlock, 0, h->stream>>>(h->mom.p, h->k, h->mu.p, h->shift.p);
         PRG_HIP(hipGetLastError());
-        k_sum<<<1, kChooseThreads, 0, h->stream>>>(h->shift, h->k, h->scal + 2);
+        k_sum<<<1, kChooseThreads, 0, h->stream>>>(h->shift.p, h->k, h->scal.p + 2);
         PRG_HIP(hipGetLastError());
         int changed = 0;
         double shift = 0.0;
-        PRG_HIP(hipMemcpyAsync(&changed, h->n_changed, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        PRG_HIP(hipMemcpyAsync(&shift, h->scal + 2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(&changed, h->n_changed.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(&shift, h->scal.p + 2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
         if (changed == 0) {
             strict = true;
@@ -643,8 +611,8 @@ int prg_gmmfit_lloyd(prg_gmmfit* h, int max_iter, double tol, int* n_iter_host) 
         if (shift <= tol) break;
     }
     if (!strict) {  // labels of the final centres
-        PRG_HIP(hipMemsetAsync(h->n_changed, 0, sizeof(int), h->stream));
-        k_assign<<<nb, kBlock, 0, h->stream>>>(h->xs, n, h->mu, h->k, h->labels, h->n_changed);
+        PRG_HIP(hipMemsetAsync(h->n_changed.p, 0, sizeof(int), h->stream));
+        k_assign<<<nb, kBlock, 0, h->stream>>>(h->xs.p, n, h->mu.p, h->k, h->labels.p, h->n_changed.p);
         PRG_HIP(hipGetLastError());
         PRG_HIP(hipStreamSynchronize(h->stream));
     }
@@ -678,11 +646,11 @@ int prg_gmmfit_set_params(prg_gmmfit* h, int k, const double* weights_host, cons
     std::vector<double> mu((size_t)k * 3, 0.0);
     for (int j = 0; j < k; ++j)
         for (int d = 0; d < h->dim; ++d) mu[(size_t)j * 3 + d] = means_host[(size_t)j * h->dim + d];
-    PRG_HIP(hipMemcpyAsync(h->w, weights_host, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PRG_HIP(hipMemcpyAsync(h->mu, mu.data(), mu.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PRG_HIP(hipMemcpyAsync(h->nk, precisions_host, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    k_records_explicit<<<(unsigned)prg::ceil_div(k, kBlock), kBlock, 0, h->stream>>>(h->w, h->mu, h->nk, k, h->dim,
-                                                                                    h->rec);
+    PRG_HIP(hipMemcpyAsync(h->w.p, weights_host, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PRG_HIP(hipMemcpyAsync(h->mu.p, mu.data(), mu.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PRG_HIP(hipMemcpyAsync(h->nk.p, precisions_host, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    k_records_explicit<<<(unsigned)prg::ceil_div(k, kBlock), kBlock, 0, h->stream>>>(h->w.p, h->mu.p, h->nk.p, k, h->dim,
+                                                                                    h->rec.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_params = true;
@@ -704,12 +672,12 @@ int prg_gmmfit_em(prg_gmmfit* h, double tol, int max_iter, double reg_covar, int
     int it = 0, conv = 0;
     while (it < max_iter) {
         ++it;
-        k_normaliser<<<nb, kBlock, 0, h->stream>>>(h->xs, n, h->rec, h->k, h->lse, h->qpart);
+        k_normaliser<<<nb, kBlock, 0, h->stream>>>(h->xs.p, n, h->rec.p, h->k, h->lse.p, h->qpart.p);
         PRG_HIP(hipGetLastError());
-        k_sum<<<1, kChooseThreads, 0, h->stream>>>(h->qpart, (int64_t)nb, h->scal);
+        k_sum<<<1, kChooseThreads, 0, h->stream>>>(h->qpart.p, (int64_t)nb, h->scal.p);
         PRG_HIP(hipGetLastError());
         double q = 0.0;
-        PRG_HIP(hipMemcpyAsync(&q, h->scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(&q, h->scal.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         PRG_TRY(moments<false>(h));
         PRG_TRY(mstep(h, reg_covar, kFinNormalise));
         PRG_HIP(hipStreamSynchronize(h->stream));
@@ -735,10 +703,10 @@ int prg_gmmfit_get_params(prg_gmmfit* h, double* weights_host, double* means_hos
     const int k = h->k;
     std::vector<double> mu((size_t)k * 3);
     if (weights_host)
-        PRG_HIP(hipMemcpyAsync(weights_host, h->w, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(weights_host, h->w.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (covariances_host)
-        PRG_HIP(hipMemcpyAsync(covariances_host, h->cov, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipMemcpyAsync(mu.data(), h->mu, mu.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(covariances_host, h->cov.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipMemcpyAsync(mu.data(), h->mu.p, mu.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     if (means_host)
         for (int j = 0; j < k; ++j)

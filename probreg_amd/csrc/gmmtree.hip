@@ -18,6 +18,7 @@
 #include <new>
 #include <vector>
 
+#include "dev_buf.h"
 #include "prg_common.h"
 
 namespace prg {
@@ -445,94 +446,66 @@ __global__ __launch_bounds__(kBlock) void k_reg_final(const double* __restrict__
 struct prg_gmmtree {
     int device = 0;
     hipStream_t stream = nullptr;
+    // the tree group (dev_buf.h: reset_group), sized by n_nodes: all four arrays or none; levels, n_nodes say which
     int levels = 0;
     int64_t n_nodes = 0;
-    double* nodes = nullptr;  // n_nodes x 10
-    double* pre = nullptr;    // n_nodes x 12
+    prg::DevBuf<double> nodes;    // n_nodes x 10
+    prg::DevBuf<double> pre;      // n_nodes x 12
+    prg::DevBuf<double> m01, m2;  // n_nodes x 4, n_nodes x 6
     // target of the registration E-step
     int64_t n_tgt = 0;
-    double* tgt = nullptr;  // n x 3
-    // workspaces (grown on demand)
-    int64_t ws_n = 0, ws_seg = 0, ws_part = 0;
+    prg::DevBuf<double> tgt;  // n x 3
+    // the workspace group (grown on demand, as a whole): keys.cap points, seg_start.cap - 1 segments, part.cap partials
     size_t sort_bytes = 0;
-    unsigned *keys = nullptr, *keys2 = nullptr;
-    int *vals = nullptr, *vals2 = nullptr, *cur = nullptr, *seg_choff = nullptr;
-    int64_t* seg_start = nullptr;
-    double4 *xa = nullptr, *xb = nullptr;
-    double *part = nullptr, *m01 = nullptr, *m2 = nullptr, *q = nullptr;
-    void* sort_tmp = nullptr;
+    prg::DevBuf<unsigned> keys, keys2;
+    prg::DevBuf<int> vals, vals2, cur, seg_choff;
+    prg::DevBuf<int64_t> seg_start;
+    prg::DevBuf<double4> xa, xb;
+    prg::DevBuf<double> part;
+    prg::DevBuf<char> sort_tmp;
+    prg::DevBuf<double> q;  // allocated once
 };
 
 namespace {
 
-void free_ws(prg_gmmtree* h) {
-    for (void* p : {(void*)h->keys, (void*)h->keys2, (void*)h->vals, (void*)h->vals2, (void*)h->cur, (void*)h->seg_choff,
-                    (void*)h->seg_start, (void*)h->xa, (void*)h->xb, (void*)h->part, (void*)h->sort_tmp})
-        if (p) (void)hipFree(p);
-    h->keys = h->keys2 = nullptr;
-    h->vals = h->vals2 = h->cur = h->seg_choff = nullptr;
-    h->seg_start = nullptr;
-    h->xa = h->xb = nullptr;
-    h->part = nullptr;
-    h->sort_tmp = nullptr;
-    h->ws_n = h->ws_seg = h->ws_part = 0;
-    h->sort_bytes = 0;
-}
-
 // Workspaces for n points, n_seg segments and partials of `width` doubles per chunk.
 int ensure_ws(prg_gmmtree* h, int64_t n, int64_t n_seg, int width) {
     const int64_t max_chunks = prg::ceil_div(n, kChunk) + n_seg;
-    if (n <= h->ws_n && n_seg <= h->ws_seg && max_chunks * width <= h->ws_part) return PRG_OK;
+    if (n <= h->keys.cap && n_seg < h->seg_start.cap && max_chunks * width <= h->part.cap) return PRG_OK;
     PRG_HIP(hipStreamSynchronize(h->stream));
-    free_ws(h);
     const int64_t nn = std::max<int64_t>(n, 1), ns = std::max<int64_t>(n_seg, 8 * 585);  // 585 = level(3) / 8 + 1
     const int64_t np = (prg::ceil_div(nn, kChunk) + ns) * 80;
-    PRG_HIP(hipMalloc((void**)&h->keys, nn * sizeof(unsigned)));
-    PRG_HIP(hipMalloc((void**)&h->keys2, nn * sizeof(unsigned)));
-    PRG_HIP(hipMalloc((void**)&h->vals, nn * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&h->vals2, nn * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&h->cur, nn * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&h->xa, nn * sizeof(double4)));
-    PRG_HIP(hipMalloc((void**)&h->xb, nn * sizeof(double4)));
-    PRG_HIP(hipMalloc((void**)&h->seg_start, (ns + 1) * sizeof(int64_t)));
-    PRG_HIP(hipMalloc((void**)&h->seg_choff, (ns + 1) * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&h->part, np * sizeof(double)));
     size_t bytes = 0;
     PRG_TRY(prg::sort_pairs_u32(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, (unsigned)nn, 32u, h->stream));
-    PRG_HIP(hipMalloc(&h->sort_tmp, std::max<size_t>(bytes, 16)));
+    h->sort_bytes = 0;
+    PRG_HIP(prg::reset_group(h->keys, nn, h->keys2, nn, h->vals, nn, h->vals2, nn, h->cur, nn, h->xa, nn, h->xb, nn, h->seg_start,
+                             ns + 1, h->seg_choff, ns + 1, h->part, np, h->sort_tmp, (int64_t)std::max<size_t>(bytes, 16)));
     h->sort_bytes = bytes;
-    h->ws_n = nn;
-    h->ws_seg = ns;
-    h->ws_part = np;
     return PRG_OK;
 }
 
 int alloc_tree(prg_gmmtree* h, int levels) {
     const int64_t n_nodes = level_begin(levels);
-    if (h->levels == levels && h->nodes) return PRG_OK;
+    if (h->levels == levels && h->nodes.p) return PRG_OK;
     PRG_HIP(hipStreamSynchronize(h->stream));
-    for (void* p : {(void*)h->nodes, (void*)h->pre, (void*)h->m01, (void*)h->m2})
-        if (p) (void)hipFree(p);
-    h->nodes = h->pre = h->m01 = h->m2 = nullptr;
-    PRG_HIP(hipMalloc((void**)&h->nodes, n_nodes * kNodeD * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->pre, n_nodes * kPreD * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->m01, n_nodes * 4 * sizeof(double)));
-    PRG_HIP(hipMalloc((void**)&h->m2, n_nodes * 6 * sizeof(double)));
+    h->levels = 0;
+    h->n_nodes = 0;
+    PRG_HIP(prg::reset_group(h->nodes, n_nodes * kNodeD, h->pre, n_nodes * kPreD, h->m01, n_nodes * 4, h->m2, n_nodes * 6));
     h->levels = levels;
     h->n_nodes = n_nodes;
     return PRG_OK;
 }
 
 int upload_nodes(prg_gmmtree* h, const double* nodes_host) {
-    PRG_HIP(hipMemcpyAsync(h->nodes, nodes_host, h->n_nodes * kNodeD * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    k_gmm_precompute<<<(unsigned)prg::ceil_div(h->n_nodes, kBlock), kBlock, 0, h->stream>>>(h->nodes, h->pre, 0, h->n_nodes);
+    PRG_HIP(hipMemcpyAsync(h->nodes.p, nodes_host, h->n_nodes * kNodeD * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    k_gmm_precompute<<<(unsigned)prg::ceil_div(h->n_nodes, kBlock), kBlock, 0, h->stream>>>(h->nodes.p, h->pre.p, 0, h->n_nodes);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));  // nodes_host may be released by the caller
     return PRG_OK;
 }
 
 int seg_table(prg_gmmtree* h, const unsigned* keys, int64_t n, int n_seg) {
-    k_seg_table<<<1, kSegThreads, 0, h->stream>>>(keys, n, n_seg, h->seg_start, h->seg_choff);
+    k_seg_table<<<1, kSegThreads, 0, h->stream>>>(keys, n, n_seg, h->seg_start.p, h->seg_choff.p);
     PRG_HIP(hipGetLastError());
     return PRG_OK;
 }
@@ -604,9 +577,6 @@ int prg_gmm_destroy(prg_gmmtree* h) {
     if (!h) return PRG_OK;
     prg::DeviceGuard g(h->device);
     (void)hipStreamSynchronize(h->stream);
-    free_ws(h);
-    for (void* p : {(void*)h->nodes, (void*)h->pre, (void*)h->m01, (void*)h->m2, (void*)h->tgt, (void*)h->q})
-        if (p) (void)hipFree(p);
     delete h;
     return PRG_OK;
 }
@@ -625,13 +595,13 @@ int prg_gmm_build(prg_gmmtree* h, const double* points_hd, int64_t n, int tree_l
     prg::DeviceGuard g(h->device);
     PRG_TRY(alloc_tree(h, tree_level));
     PRG_TRY(ensure_ws(h, n, nl / 8, 80));
-    if (!h->q) PRG_HIP(hipMalloc((void**)&h->q, 8 * sizeof(double)));
+    PRG_HIP(h->q.ensure(8, 8));
     // host copy of the points: initialisation (not a hot path) and the padded device layout
     std::vector<double> pts((size_t)n * 3), pad((size_t)n * 4, 0.0), init;
     PRG_HIP(hipMemcpy(pts.data(), points_hd, pts.size() * sizeof(double), hipMemcpyDefault));
     for (int64_t i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) pad[(size_t)i * 4 + k] = pts[(size_t)i * 3 + k];
-    PRG_HIP(hipMemcpyAsync(h->xa, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PRG_HIP(hipMemcpyAsync(h->xa.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     init_nodes(pts.data(), n, tree_level, init_idx_host, init);
     PRG_TRY(upload_nodes(h, init.data()));
 
@@ -640,35 +610,35 @@ int prg_gmm_build(prg_gmmtree* h, const double* points_hd, int64_t n, int tree_l
         const int n_seg = (int)pow8(l);
         const int64_t lvl0 = level_begin(l), lvl1 = level_begin(l + 1);
         if (l == 0) {
-            PRG_HIP(hipMemsetAsync(h->keys, 0, n * sizeof(unsigned), h->stream));
+            PRG_HIP(hipMemsetAsync(h->keys.p, 0, n * sizeof(unsigned), h->stream));
         } else {
             // order the points by parent (= `current` of the previous level's last E-step, :120); stable
-            k_keys_from_cur<<<nbl, kBlock, 0, h->stream>>>(h->cur, n, level_begin(l - 1), h->keys2, h->vals2);
+            k_keys_from_cur<<<nbl, kBlock, 0, h->stream>>>(h->cur.p, n, level_begin(l - 1), h->keys2.p, h->vals2.p);
             PRG_HIP(hipGetLastError());
             size_t bytes = h->sort_bytes;
-            PRG_TRY(prg::sort_pairs_u32(h->sort_tmp, &bytes, h->keys2, h->keys, h->vals2, h->vals, (unsigned)n, 3u * l,
+            PRG_TRY(prg::sort_pairs_u32(h->sort_tmp.p, &bytes, h->keys2.p, h->keys.p, h->vals2.p, h->vals.p, (unsigned)n, 3u * l,
                                         h->stream));
-            k_gather4<<<nbl, kBlock, 0, h->stream>>>(h->xa, h->vals, n, h->xb);
+            k_gather4<<<nbl, kBlock, 0, h->stream>>>(h->xa.p, h->vals.p, n, h->xb.p);
             PRG_HIP(hipGetLastError());
-            std::swap(h->xa, h->xb);
+            h->xa.swap(h->xb);
         }
-        PRG_TRY(seg_table(h, h->keys, n, n_seg));
+        PRG_TRY(seg_table(h, h->keys.p, n, n_seg));
         const unsigned max_chunks = (unsigned)(prg::ceil_div(n, kChunk) + n_seg);
         double prev_q = 0.0, q = 0.0;
         int it = 0;
         while (true) {
             ++it;
-            k_build_estep<<<max_chunks, kBlock, 0, h->stream>>>(h->xa, h->pre, lvl0, h->seg_start, h->seg_choff, n_seg,
-                                                                h->cur, h->part);
+            k_build_estep<<<max_chunks, kBlock, 0, h->stream>>>(h->xa.p, h->pre.p, lvl0, h->seg_start.p, h->seg_choff.p, n_seg,
+                                                                h->cur.p, h->part.p);
             PRG_HIP(hipGetLastError());
-            k_build_mstep<<<(unsigned)n_seg, 128, 0, h->stream>>>(h->part, h->seg_choff, lvl0, (double)n, lambda_d,
-                                                                  h->nodes, h->pre);
+            k_build_mstep<<<(unsigned)n_seg, 128, 0, h->stream>>>(h->part.p, h->seg_choff.p, lvl0, (double)n, lambda_d,
+                                                                  h->nodes.p, h->pre.p);
             PRG_HIP(hipGetLastError());
-            k_build_loglik<<<nbl, kBlock, 0, h->stream>>>(h->xa, n, h->pre, lvl0, lvl1, h->part);
+            k_build_loglik<<<nbl, kBlock, 0, h->stream>>>(h->xa.p, n, h->pre.p, lvl0, lvl1, h->part.p);
             PRG_HIP(hipGetLastError());
-            k_sum_partials<<<1, kBlock, 0, h->stream>>>(h->part, (int64_t)nbl, h->q);
+            k_sum_partials<<<1, kBlock, 0, h->stream>>>(h->part.p, (int64_t)nbl, h->q.p);
             PRG_HIP(hipGetLastError());
-            PRG_HIP(hipMemcpyAsync(&q, h->q, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            PRG_HIP(hipMemcpyAsync(&q, h->q.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
             PRG_HIP(hipStreamSynchronize(h->stream));
             const double dq = fabs(q - prev_q);
             if (dq < lambda_s || it >= max_iter) {  // :116 (the cap is ours: the reference loops until convergence)
@@ -694,9 +664,9 @@ int prg_gmm_set_nodes(prg_gmmtree* h, const double* nodes_host, int tree_level) 
 
 int prg_gmm_get_nodes(prg_gmmtree* h, double* nodes_host) {
     PRG_REQUIRE(h && nodes_host, PRG_ERR_INVALID, "prg_gmm_get_nodes: NULL argument");
-    PRG_REQUIRE(h->nodes, PRG_ERR_STATE, "prg_gmm_get_nodes: no tree (build or set_nodes first)");
+    PRG_REQUIRE(h->nodes.p, PRG_ERR_STATE, "prg_gmm_get_nodes: no tree (build or set_nodes first)");
     prg::DeviceGuard g(h->device);
-    PRG_HIP(hipMemcpyAsync(nodes_host, h->nodes, h->n_nodes * kNodeD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipMemcpyAsync(nodes_host, h->nodes.p, h->n_nodes * kNodeD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }
@@ -706,11 +676,12 @@ int prg_gmm_set_target(prg_gmmtree* h, const double* target_hd, int64_t n) {
     PRG_REQUIRE(n >= 1 && n < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_gmm_set_target: need 1 <= n < 2^31 points");
     prg::DeviceGuard g(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
-    if (h->tgt) (void)hipFree(h->tgt);
-    h->tgt = nullptr;
-    PRG_HIP(hipMalloc((void**)&h->tgt, (size_t)n * 3 * sizeof(double)));
-    PRG_HIP(hipMemcpyAsync(h->tgt, target_hd, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, h->stream));
-    PRG_HIP(hipStreamSynchronize(h->stream));
+    h->n_tgt = 0;
+    hipError_t e = h->tgt.reset(n * 3);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->tgt.p, target_hd, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) h->tgt.release();  // no target rather than one whose contents never arrived
+    PRG_HIP(e);
     h->n_tgt = n;
     return PRG_OK;
 }
@@ -718,7 +689,7 @@ int prg_gmm_set_target(prg_gmmtree* h, const double* target_hd, int64_t n) {
 int prg_gmm_reg_estep(prg_gmmtree* h, const double* rot9, const double* t3, double scale, double lambda_c,
                       double* m01_host, double* m2_host) {
     PRG_REQUIRE(h && rot9 && t3 && m01_host, PRG_ERR_INVALID, "prg_gmm_reg_estep: NULL argument");
-    PRG_REQUIRE(h->nodes && h->tgt, PRG_ERR_STATE, "prg_gmm_reg_estep: need a tree and a target");
+    PRG_REQUIRE(h->nodes.p && h->tgt.p, PRG_ERR_STATE, "prg_gmm_reg_estep: need a tree and a target");
     prg::DeviceGuard g(h->device);
     const int64_t n = h->n_tgt;
     const int n_seg = (int)h->n_nodes;
@@ -728,21 +699,21 @@ int prg_gmm_reg_estep(prg_gmmtree* h, const double* rot9, const double* t3, doub
     const unsigned nbl = (unsigned)prg::ceil_div(n, kBlock);
     double r[9];
     for (int k = 0; k < 9; ++k) r[k] = scale * rot9[k];
-    k_reg_descend<<<nbl, kBlock, 0, h->stream>>>(h->tgt, n, h->pre, h->levels, r[0], r[1], r[2], r[3], r[4], r[5], r[6],
-                                                 r[7], r[8], t3[0], t3[1], t3[2], lambda_c, h->keys2, h->vals2, h->xb);
+    k_reg_descend<<<nbl, kBlock, 0, h->stream>>>(h->tgt.p, n, h->pre.p, h->levels, r[0], r[1], r[2], r[3], r[4], r[5], r[6],
+                                                 r[7], r[8], t3[0], t3[1], t3[2], lambda_c, h->keys2.p, h->vals2.p, h->xb.p);
     PRG_HIP(hipGetLastError());
     size_t bytes = h->sort_bytes;
-    PRG_TRY(prg::sort_pairs_u32(h->sort_tmp, &bytes, h->keys2, h->keys, h->vals2, h->vals, (unsigned)n, bits, h->stream));
-    PRG_TRY(seg_table(h, h->keys, n, n_seg));
+    PRG_TRY(prg::sort_pairs_u32(h->sort_tmp.p, &bytes, h->keys2.p, h->keys.p, h->vals2.p, h->vals.p, (unsigned)n, bits, h->stream));
+    PRG_TRY(seg_table(h, h->keys.p, n, n_seg));
     const unsigned max_chunks = (unsigned)(prg::ceil_div(n, kChunk) + n_seg);
-    k_reg_chunk<<<max_chunks, kBlock, 0, h->stream>>>(h->xb, h->vals, h->seg_start, h->seg_choff, n_seg, h->part);
+    k_reg_chunk<<<max_chunks, kBlock, 0, h->stream>>>(h->xb.p, h->vals.p, h->seg_start.p, h->seg_choff.p, n_seg, h->part.p);
     PRG_HIP(hipGetLastError());
-    k_reg_final<<<(unsigned)prg::ceil_div((int64_t)n_seg * 10, kBlock), kBlock, 0, h->stream>>>(h->part, h->seg_choff,
-                                                                                              n_seg, h->m01, h->m2);
+    k_reg_final<<<(unsigned)prg::ceil_div((int64_t)n_seg * 10, kBlock), kBlock, 0, h->stream>>>(h->part.p, h->seg_choff.p,
+                                                                                              n_seg, h->m01.p, h->m2.p);
     PRG_HIP(hipGetLastError());
-    PRG_HIP(hipMemcpyAsync(m01_host, h->m01, h->n_nodes * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipMemcpyAsync(m01_host, h->m01.p, h->n_nodes * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (m2_host)
-        PRG_HIP(hipMemcpyAsync(m2_host, h->m2, h->n_nodes * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(m2_host, h->m2.p, h->n_nodes * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     return PRG_OK;
 }

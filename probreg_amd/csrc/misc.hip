@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <stdarg.h>
 
+#include "dev_buf.h"
 #include "prg_common.h"
 #include "prg_device.h"
 
@@ -260,12 +261,7 @@ __global__ __launch_bounds__(kBlock) void k_nn_mean(const unsigned* __restrict__
     if (threadIdx.x == 0) out[0] = sh[0] / (double)m;
 }
 
-struct TmpBuf {
-    void* p = nullptr;
-    ~TmpBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
+using prg::DevBuf;
 
 }  // namespace
 
@@ -296,17 +292,18 @@ int prg_squared_kernel_sum(int device, void* hip_stream, const float* x_hd, int6
     PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_squared_kernel_sum: hipSetDevice(%d) failed", device);
     hipStream_t st = (hipStream_t)hip_stream;
     if (dim != 2 && dim != 3) {  // feature clouds (FilterReg with a feature_fn, filterreg.py:126-128)
-        TmpBuf fx, fy, fs;
-        PRG_HIP(hipMalloc(&fx.p, (size_t)m * dim * sizeof(float)));
-        PRG_HIP(hipMalloc(&fy.p, (size_t)n * dim * sizeof(float)));
-        PRG_HIP(hipMalloc(&fs.p, (size_t)(2 * (dim + 1) + 1) * sizeof(double)));
+        DevBuf<float> fx, fy;
+        DevBuf<double> fs;
+        PRG_HIP(fx.reset(m * dim));
+        PRG_HIP(fy.reset(n * dim));
+        PRG_HIP(fs.reset(2 * (dim + 1) + 1));
         PRG_HIP(hipMemcpyAsync(fx.p, x_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, st));
         PRG_HIP(hipMemcpyAsync(fy.p, y_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault, st));
         PRG_HIP(hipMemsetAsync(fs.p, 0, (size_t)(2 * (dim + 1) + 1) * sizeof(double), st));
-        double* sx = (double*)fs.p;
+        double* sx = fs.p;
         double* sy = sx + dim + 1;
-        k_sums_generic<<<(unsigned)std::min<int64_t>(prg::ceil_div(m, kBlock), 512), kBlock, 0, st>>>((const float*)fx.p, m, dim, sx);
-        k_sums_generic<<<(unsigned)std::min<int64_t>(prg::ceil_div(n, kBlock), 512), kBlock, 0, st>>>((const float*)fy.p, n, dim, sy);
+        k_sums_generic<<<(unsigned)std::min<int64_t>(prg::ceil_div(m, kBlock), 512), kBlock, 0, st>>>(fx.p, m, dim, sx);
+        k_sums_generic<<<(unsigned)std::min<int64_t>(prg::ceil_div(n, kBlock), 512), kBlock, 0, st>>>(fy.p, n, dim, sy);
         k_sks_final_generic<<<1, 64, 0, st>>>(sx, sy, (double)m, (double)n, dim, sy + dim + 1);
         PRG_HIP(hipGetLastError());
         PRG_HIP(hipMemcpyAsync(out_host, sy + dim + 1, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -315,17 +312,18 @@ int prg_squared_kernel_sum(int device, void* hip_stream, const float* x_hd, int6
     }
     const int nbx = (int)(prg::ceil_div(m, kBlock) < 256 ? prg::ceil_div(m, kBlock) : 256);
     const int nby = (int)(prg::ceil_div(n, kBlock) < 256 ? prg::ceil_div(n, kBlock) : 256);
-    TmpBuf bx, by, bp;
-    PRG_HIP(hipMalloc(&bx.p, (size_t)m * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&by.p, (size_t)n * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&bp.p, (size_t)(nbx + nby) * 4 * sizeof(double) + sizeof(double)));
+    DevBuf<float> bx, by;
+    DevBuf<double> bp;
+    PRG_HIP(bx.reset(m * dim));
+    PRG_HIP(by.reset(n * dim));
+    PRG_HIP(bp.reset((int64_t)(nbx + nby) * 4 + 1));
     PRG_HIP(hipMemcpyAsync(bx.p, x_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(by.p, y_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault, st));
-    double* px = (double*)bp.p;
+    double* px = bp.p;
     double* py = px + (size_t)nbx * 4;
     double* res = py + (size_t)nby * 4;
-    k_sums_rowmajor<<<nbx, kBlock, 0, st>>>((const float*)bx.p, m, dim, px);
-    k_sums_rowmajor<<<nby, kBlock, 0, st>>>((const float*)by.p, n, dim, py);
+    k_sums_rowmajor<<<nbx, kBlock, 0, st>>>(bx.p, m, dim, px);
+    k_sums_rowmajor<<<nby, kBlock, 0, st>>>(by.p, n, dim, py);
     k_sks_final<<<1, 64, 0, st>>>(px, nbx, py, nby, (double)m, (double)n, dim, res);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipMemcpyAsync(out_host, res, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -341,15 +339,14 @@ int prg_rbf_kernel(int device, void* hip_stream, const float* x_hd, int64_t m, c
     prg::DeviceGuard g(device);
     PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_rbf_kernel: hipSetDevice(%d) failed", device);
     hipStream_t st = (hipStream_t)hip_stream;
-    TmpBuf bx, by, bo;
-    PRG_HIP(hipMalloc(&bx.p, (size_t)m * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&by.p, (size_t)n * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&bo.p, (size_t)m * n * sizeof(float)));
+    DevBuf<float> bx, by, bo;
+    PRG_HIP(bx.reset(m * dim));
+    PRG_HIP(by.reset(n * dim));
+    PRG_HIP(bo.reset(m * n));
     PRG_HIP(hipMemcpyAsync(bx.p, x_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(by.p, y_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault, st));
     dim3 grid((unsigned)prg::ceil_div(n, kBlock), (unsigned)prg::ceil_div(m, 16));
-    k_rbf<<<grid, kBlock, 0, st>>>((const float*)bx.p, m, (const float*)by.p, n, dim, (float)(2.0 * beta),
-                                   (float*)bo.p);
+    k_rbf<<<grid, kBlock, 0, st>>>(bx.p, m, by.p, n, dim, (float)(2.0 * beta), bo.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipMemcpyAsync(out_hd, bo.p, (size_t)m * n * sizeof(float), hipMemcpyDefault, st));
     PRG_HIP(hipStreamSynchronize(st));
@@ -364,14 +361,14 @@ int prg_inverse_multiquadric_kernel(int device, void* hip_stream, const float* x
     prg::DeviceGuard g(device);
     PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_inverse_multiquadric_kernel: hipSetDevice(%d) failed", device);
     hipStream_t st = (hipStream_t)hip_stream;
-    TmpBuf bx, by, bo;
-    PRG_HIP(hipMalloc(&bx.p, (size_t)m * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&by.p, (size_t)n * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&bo.p, (size_t)m * n * sizeof(float)));
+    DevBuf<float> bx, by, bo;
+    PRG_HIP(bx.reset(m * dim));
+    PRG_HIP(by.reset(n * dim));
+    PRG_HIP(bo.reset(m * n));
     PRG_HIP(hipMemcpyAsync(bx.p, x_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(by.p, y_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault, st));
     dim3 grid((unsigned)prg::ceil_div(n, kBlock), (unsigned)prg::ceil_div(m, 16));
-    k_imq<<<grid, kBlock, 0, st>>>((const float*)bx.p, m, (const float*)by.p, n, dim, (float)c, (float*)bo.p);
+    k_imq<<<grid, kBlock, 0, st>>>(bx.p, m, by.p, n, dim, (float)c, bo.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipMemcpyAsync(out_hd, bo.p, (size_t)m * n * sizeof(float), hipMemcpyDefault, st));
     PRG_HIP(hipStreamSynchronize(st));
@@ -391,20 +388,20 @@ int prg_nn_mean_distance(int device, void* hip_stream, const float* a_hd, int64_
     int nseg = (int)std::min<int64_t>(std::max<int64_t>(1, 2048 / nbx), prg::ceil_div(n, 256));
     const int seg_len = (int)prg::round_up(prg::ceil_div(n, nseg), 4);
     const int64_t cap = (int64_t)seg_len * nseg;
-    TmpBuf ba, bb, b4, bd;
-    PRG_HIP(hipMalloc(&ba.p, (size_t)m * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&bb.p, (size_t)n * dim * sizeof(float)));
-    PRG_HIP(hipMalloc(&b4.p, (size_t)cap * sizeof(float4)));
-    PRG_HIP(hipMalloc(&bd.p, (size_t)m * sizeof(unsigned) + sizeof(double) * 2));
+    DevBuf<float> ba, bb;
+    DevBuf<float4> b4;
+    DevBuf<unsigned> bd;  // [m] nearest squared distances, then two doubles (16 bytes) for the result
+    PRG_HIP(ba.reset(m * dim));
+    PRG_HIP(bb.reset(n * dim));
+    PRG_HIP(b4.reset(cap));
+    PRG_HIP(bd.reset(m + 4));
     PRG_HIP(hipMemcpyAsync(ba.p, a_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(bb.p, b_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault, st));
     double* res = reinterpret_cast<double*>((char*)bd.p + prg::round_up((int64_t)m * sizeof(unsigned), 8));
-    k_pack_weighted<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>((const float*)bb.p, nullptr, n, dim, cap,
-                                                                            (float4*)b4.p);
-    k_nn_fill<<<(unsigned)nbx, kBlock, 0, st>>>((unsigned*)bd.p, m);
-    k_nn_min<<<dim3((unsigned)nbx, (unsigned)nseg), kBlock, 0, st>>>((const float*)ba.p, m, dim, (const float4*)b4.p,
-                                                                    seg_len, (unsigned*)bd.p);
-    k_nn_mean<<<1, kBlock, 0, st>>>((const unsigned*)bd.p, m, res);
+    k_pack_weighted<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>(bb.p, nullptr, n, dim, cap, b4.p);
+    k_nn_fill<<<(unsigned)nbx, kBlock, 0, st>>>(bd.p, m);
+    k_nn_min<<<dim3((unsigned)nbx, (unsigned)nseg), kBlock, 0, st>>>(ba.p, m, dim, b4.p, seg_len, bd.p);
+    k_nn_mean<<<1, kBlock, 0, st>>>(bd.p, m, res);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipMemcpyAsync(out_host, res, sizeof(double), hipMemcpyDeviceToHost, st));
     PRG_HIP(hipStreamSynchronize(st));
@@ -423,31 +420,30 @@ int prg_gauss_transform_direct(int device, void* hip_stream, const double* sourc
     hipStream_t st = (hipStream_t)hip_stream;
     const int64_t cap = prg::round_up(s, 256);
     const int rows = n_weight_rows;
-    TmpBuf bs, bt, bw, b3, bwr, bo;
-    PRG_HIP(hipMalloc(&bs.p, (size_t)s * dim * sizeof(double)));
-    PRG_HIP(hipMalloc(&bt.p, (size_t)t * dim * sizeof(double)));
-    PRG_HIP(hipMalloc(&bw.p, (size_t)s * rows * sizeof(double)));
-    PRG_HIP(hipMalloc(&b3.p, (size_t)cap * 3 * sizeof(double)));
-    PRG_HIP(hipMalloc(&bwr.p, (size_t)cap * rows * sizeof(double)));
-    PRG_HIP(hipMalloc(&bo.p, (size_t)t * rows * sizeof(double)));
+    DevBuf<double> bs, bt, bw, b3, bwr, bo;
+    PRG_HIP(bs.reset(s * dim));
+    PRG_HIP(bt.reset(t * dim));
+    PRG_HIP(bw.reset(s * rows));
+    PRG_HIP(b3.reset(cap * 3));
+    PRG_HIP(bwr.reset(cap * rows));
+    PRG_HIP(bo.reset(t * rows));
     PRG_HIP(hipMemcpyAsync(bs.p, source_hd, (size_t)s * dim * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(bt.p, target_hd, (size_t)t * dim * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(bw.p, weights_hd, (size_t)s * rows * sizeof(double), hipMemcpyDefault, st));
     const float kk = (float)(-1.4426950408889634 / (h * h));
-    k_pack_gauss<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>((const double*)bs.p, (const double*)bw.p, s, dim, rows, cap,
-                                                                         (double*)b3.p, (double*)bwr.p);
+    k_pack_gauss<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>(bs.p, bw.p, s, dim, rows, cap, b3.p, bwr.p);
     const unsigned grid = (unsigned)prg::ceil_div(t, kBlock);
     for (int c = 0; c < rows;) {  // four weight rows per sweep (compute_l2_dist: 1 + D rows = one sweep), then 2, then 1
-        const double* w = (const double*)bwr.p + (size_t)c * cap;
-        double* o = (double*)bo.p + (size_t)c * t;
+        const double* w = bwr.p + (size_t)c * cap;
+        double* o = bo.p + (size_t)c * t;
         if (rows - c >= 4) {
-            k_gauss_direct<4><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            k_gauss_direct<4><<<grid, kBlock, 0, st>>>(b3.p, cap, w, bt.p, t, dim, kk, o);
             c += 4;
         } else if (rows - c >= 2) {
-            k_gauss_direct<2><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            k_gauss_direct<2><<<grid, kBlock, 0, st>>>(b3.p, cap, w, bt.p, t, dim, kk, o);
             c += 2;
         } else {
-            k_gauss_direct<1><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            k_gauss_direct<1><<<grid, kBlock, 0, st>>>(b3.p, cap, w, bt.p, t, dim, kk, o);
             c += 1;
         }
     }
@@ -469,31 +465,30 @@ int prg_gauss_transform_direct_f64(int device, void* hip_stream, const double* s
     hipStream_t st = (hipStream_t)hip_stream;
     const int64_t cap = prg::round_up(s, 256);
     const int rows = n_weight_rows;
-    TmpBuf bs, bt, bw, b3, bwr, bo;
-    PRG_HIP(hipMalloc(&bs.p, (size_t)s * dim * sizeof(double)));
-    PRG_HIP(hipMalloc(&bt.p, (size_t)t * dim * sizeof(double)));
-    PRG_HIP(hipMalloc(&bw.p, (size_t)s * rows * sizeof(double)));
-    PRG_HIP(hipMalloc(&b3.p, (size_t)cap * 3 * sizeof(double)));
-    PRG_HIP(hipMalloc(&bwr.p, (size_t)cap * rows * sizeof(double)));
-    PRG_HIP(hipMalloc(&bo.p, (size_t)t * rows * sizeof(double)));
+    DevBuf<double> bs, bt, bw, b3, bwr, bo;
+    PRG_HIP(bs.reset(s * dim));
+    PRG_HIP(bt.reset(t * dim));
+    PRG_HIP(bw.reset(s * rows));
+    PRG_HIP(b3.reset(cap * 3));
+    PRG_HIP(bwr.reset(cap * rows));
+    PRG_HIP(bo.reset(t * rows));
     PRG_HIP(hipMemcpyAsync(bs.p, source_hd, (size_t)s * dim * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(bt.p, target_hd, (size_t)t * dim * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(bw.p, weights_hd, (size_t)s * rows * sizeof(double), hipMemcpyDefault, st));
     const double kk = -1.0 / (h * h);
-    k_pack_gauss<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>((const double*)bs.p, (const double*)bw.p, s, dim, rows, cap,
-                                                                         (double*)b3.p, (double*)bwr.p);
+    k_pack_gauss<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>(bs.p, bw.p, s, dim, rows, cap, b3.p, bwr.p);
     const unsigned grid = (unsigned)prg::ceil_div(t, kBlock);
     for (int c = 0; c < rows;) {  // four weight rows per sweep (compute_l2_dist: 1 + D rows = one sweep), then 2, then 1
-        const double* w = (const double*)bwr.p + (size_t)c * cap;
-        double* o = (double*)bo.p + (size_t)c * t;
+        const double* w = bwr.p + (size_t)c * cap;
+        double* o = bo.p + (size_t)c * t;
         if (rows - c >= 4) {
-            k_gauss_direct_f64<4><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            k_gauss_direct_f64<4><<<grid, kBlock, 0, st>>>(b3.p, cap, w, bt.p, t, dim, kk, o);
             c += 4;
         } else if (rows - c >= 2) {
-            k_gauss_direct_f64<2><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            k_gauss_direct_f64<2><<<grid, kBlock, 0, st>>>(b3.p, cap, w, bt.p, t, dim, kk, o);
             c += 2;
         } else {
-            k_gauss_direct_f64<1><<<grid, kBlock, 0, st>>>((const double*)b3.p, cap, w, (const double*)bt.p, t, dim, kk, o);
+            k_gauss_direct_f64<1><<<grid, kBlock, 0, st>>>(b3.p, cap, w, bt.p, t, dim, kk, o);
             c += 1;
         }
     }

@@ -33,6 +33,7 @@
 #include <new>
 #include <vector>
 
+#include "dev_buf.h"
 #include "prg_common.h"
 
 namespace {
@@ -222,10 +223,13 @@ struct prg_ocsvm {
     int dim = 0;
     bool solved = false, profile = false;
     double gamma = 0.0, rho = 0.0, objective = 0.0;
-    double4* xs = nullptr;
-    double *alpha = nullptr, *grad = nullptr, *d_val = nullptr, *sv_coef = nullptr;
-    int *ws = nullptr, *d_idx = nullptr, *sv_idx = nullptr;
-    Rec* rec = nullptr;
+    prg::DevBuf<double4> xs;          // the points group: xs, alpha, grad are [n], all there or none (n, dim say which)
+    prg::DevBuf<double> alpha, grad;
+    prg::DevBuf<int> sv_idx;          // the support list of the last solve and its coefficients
+    prg::DevBuf<double> sv_coef;
+    prg::DevBuf<int> ws, d_idx;       // [kQ] each, allocated once
+    prg::DevBuf<double> d_val;
+    prg::DevBuf<Rec> rec;
     std::vector<double> alpha_host;
     std::vector<int> support;
     double prof_ms[4] = {0.0, 0.0, 0.0, 0.0};  // initial gradient, select, subproblem, sweep
@@ -233,17 +237,6 @@ struct prg_ocsvm {
 };
 
 namespace {
-
-template <typename T>
-void free_dev(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-void free_points(prg_ocsvm* h) {
-    free_dev(h->xs); free_dev(h->alpha); free_dev(h->grad); free_dev(h->sv_coef); free_dev(h->sv_idx);
-    h->solved = false;
-}
 
 // Host copy of k x dim doubles that live on the host or the device, padded to (x, y, z or 0, 0)
 int padded_points(const double* pts_hd, int64_t k, int dim, std::vector<double>& pad) {
@@ -280,8 +273,6 @@ int prg_ocsvm_destroy(prg_ocsvm* h) {
     if (!h) return PRG_OK;
     prg::DeviceGuard g(h->device);
     (void)hipStreamSynchronize(h->stream);
-    free_points(h);
-    free_dev(h->ws); free_dev(h->d_idx); free_dev(h->d_val); free_dev(h->rec);
     for (hipEvent_t& e : h->ev)
         if (e) (void)hipEventDestroy(e);
     delete h;
@@ -304,24 +295,21 @@ int prg_ocsvm_set_data(prg_ocsvm* h, const double* data_hd, int64_t n, int dim) 
     PRG_REQUIRE(st != PRG_ERR_INVALID, PRG_ERR_INVALID, "prg_ocsvm_set_data: data contains NaN or infinity");
     PRG_TRY(st);
     PRG_HIP(hipStreamSynchronize(h->stream));
-    free_points(h);
+    h->solved = false;
+    h->n = 0;
+    h->dim = 0;
+    prg::release_all(h->sv_coef, h->sv_idx);
+    hipError_t e = prg::reset_group(h->xs, n, h->alpha, n, h->grad, n);
+    if (e == hipSuccess) e = h->ws.ensure(kQ, kQ);
+    if (e == hipSuccess) e = h->d_idx.ensure(kQ, kQ);
+    if (e == hipSuccess) e = h->d_val.ensure(kQ, kQ);
+    if (e == hipSuccess) e = h->rec.ensure(1, 1);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->xs.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) prg::release_all(h->xs, h->alpha, h->grad);  // no half-built cloud: the handle is back to "no data"
+    PRG_HIP(e);
     h->n = n;
     h->dim = dim;
-    hipError_t e = hipMalloc((void**)&h->xs, (size_t)n * sizeof(double4));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->alpha, (size_t)n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->grad, (size_t)n * sizeof(double));
-    if (e == hipSuccess && !h->ws) e = hipMalloc((void**)&h->ws, kQ * sizeof(int));
-    if (e == hipSuccess && !h->d_idx) e = hipMalloc((void**)&h->d_idx, kQ * sizeof(int));
-    if (e == hipSuccess && !h->d_val) e = hipMalloc((void**)&h->d_val, kQ * sizeof(double));
-    if (e == hipSuccess && !h->rec) e = hipMalloc((void**)&h->rec, sizeof(Rec));
-    if (e == hipSuccess) e = hipMemcpyAsync(h->xs, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {  // no half-built cloud: the handle is back to "no data"
-        free_points(h);
-        h->n = 0;
-        h->dim = 0;
-    }
-    PRG_HIP(e);
     return PRG_OK;
 }
 
@@ -344,7 +332,7 @@ int prg_ocsvm_get_profile(prg_ocsvm* h, double* ms4_host) {
 int prg_ocsvm_solve(prg_ocsvm* h, double gamma, double nu, double tol, int max_iter, int inner_cap, int* n_iter_host,
                     int* n_inner_host, int* converged_host, double* gap_host) {
     PRG_REQUIRE(h && n_iter_host && converged_host && gap_host, PRG_ERR_INVALID, "prg_ocsvm_solve: NULL argument");
-    PRG_REQUIRE(h->xs != nullptr, PRG_ERR_STATE, "prg_ocsvm_solve: no data (prg_ocsvm_set_data first)");
+    PRG_REQUIRE(h->xs.p != nullptr, PRG_ERR_STATE, "prg_ocsvm_solve: no data (prg_ocsvm_set_data first)");
     PRG_REQUIRE(gamma > 0.0 && std::isfinite(gamma), PRG_ERR_INVALID, "prg_ocsvm_solve: gamma must be > 0 and finite");
     PRG_REQUIRE(nu > 0.0 && nu <= 1.0, PRG_ERR_INVALID, "prg_ocsvm_solve: nu must lie in (0, 1]");
     PRG_REQUIRE(tol > 0.0 && std::isfinite(tol), PRG_ERR_INVALID, "prg_ocsvm_solve: tol must be > 0 and finite");
@@ -362,9 +350,9 @@ int prg_ocsvm_solve(prg_ocsvm* h, double gamma, double nu, double tol, int max_i
     for (int64_t i = 0; i < n_full; ++i) h->alpha_host[(size_t)i] = 1.0;
     if (n_full < n) h->alpha_host[(size_t)n_full] = nu * (double)n - (double)n_full;
     const int64_t n_start = std::min<int64_t>(n_full + 1, n);
-    PRG_HIP(hipMemcpyAsync(h->alpha, h->alpha_host.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PRG_HIP(hipMemcpyAsync(h->alpha.p, h->alpha_host.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (h->profile) PRG_HIP(hipEventRecord(h->ev[0], h->stream));
-    k_sweep<false><<<nb, kBlock, 0, h->stream>>>(h->xs, n, h->xs, nullptr, h->alpha, n_start, gamma, h->grad, nullptr);
+    k_sweep<false><<<nb, kBlock, 0, h->stream>>>(h->xs.p, n, h->xs.p, nullptr, h->alpha.p, n_start, gamma, h->grad.p, nullptr);
     PRG_HIP(hipGetLastError());
     if (h->profile) {
         PRG_HIP(hipEventRecord(h->ev[1], h->stream));
@@ -379,19 +367,19 @@ int prg_ocsvm_solve(prg_ocsvm* h, double gamma, double nu, double tol, int max_i
     for (;;) {  // at most max_iter rounds, then one evaluation of the gap that changes nothing
         const bool step = rounds < max_iter;
         if (h->profile) PRG_HIP(hipEventRecord(h->ev[0], h->stream));
-        k_select<<<kGroups, kBlock, 0, h->stream>>>(h->alpha, h->grad, n, h->ws);
+        k_select<<<kGroups, kBlock, 0, h->stream>>>(h->alpha.p, h->grad.p, n, h->ws.p);
         PRG_HIP(hipGetLastError());
         if (h->profile) PRG_HIP(hipEventRecord(h->ev[1], h->stream));
-        k_subproblem<<<1, kQ, 0, h->stream>>>(h->xs, h->alpha, h->grad, h->ws, gamma, tol, step ? inner_cap : 0, h->d_idx,
-                                              h->d_val, h->rec);
+        k_subproblem<<<1, kQ, 0, h->stream>>>(h->xs.p, h->alpha.p, h->grad.p, h->ws.p, gamma, tol, step ? inner_cap : 0, h->d_idx.p,
+                                              h->d_val.p, h->rec.p);
         PRG_HIP(hipGetLastError());
         if (h->profile) PRG_HIP(hipEventRecord(h->ev[2], h->stream));
         if (step) {
-            k_sweep<true><<<nb, kBlock, 0, h->stream>>>(h->xs, n, h->xs, h->d_idx, h->d_val, kQ, gamma, h->grad, h->rec);
+            k_sweep<true><<<nb, kBlock, 0, h->stream>>>(h->xs.p, n, h->xs.p, h->d_idx.p, h->d_val.p, kQ, gamma, h->grad.p, h->rec.p);
             PRG_HIP(hipGetLastError());
         }
         if (h->profile) PRG_HIP(hipEventRecord(h->ev[3], h->stream));
-        PRG_HIP(hipMemcpyAsync(&rec, h->rec, sizeof(Rec), hipMemcpyDeviceToHost, h->stream));
+        PRG_HIP(hipMemcpyAsync(&rec, h->rec.p, sizeof(Rec), hipMemcpyDeviceToHost, h->stream));
         PRG_HIP(hipStreamSynchronize(h->stream));
         if (h->profile)
             for (int i = 0; i < 3; ++i) {
@@ -409,8 +397,8 @@ int prg_ocsvm_solve(prg_ocsvm* h, double gamma, double nu, double tol, int max_i
     }
     // rho (libsvm Solver::calculate_rho with y = +1), the objective and the support list, on the host in index order
     std::vector<double> grad((size_t)n);
-    PRG_HIP(hipMemcpyAsync(h->alpha_host.data(), h->alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipMemcpyAsync(grad.data(), h->grad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipMemcpyAsync(h->alpha_host.data(), h->alpha.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PRG_HIP(hipMemcpyAsync(grad.data(), h->grad.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     double ub = std::numeric_limits<double>::infinity(), lb = -ub, sum_free = 0.0, obj = 0.0;
     int64_t n_free = 0;
@@ -434,12 +422,9 @@ int prg_ocsvm_solve(prg_ocsvm* h, double gamma, double nu, double tol, int max_i
     }
     h->rho = n_free > 0 ? sum_free / (double)n_free : 0.5 * (ub + lb);
     h->objective = 0.5 * obj;
-    free_dev(h->sv_idx);
-    free_dev(h->sv_coef);
-    PRG_HIP(hipMalloc((void**)&h->sv_idx, h->support.size() * sizeof(int)));
-    PRG_HIP(hipMalloc((void**)&h->sv_coef, coef.size() * sizeof(double)));
-    PRG_HIP(hipMemcpyAsync(h->sv_idx, h->support.data(), h->support.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    PRG_HIP(hipMemcpyAsync(h->sv_coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PRG_HIP(prg::reset_group(h->sv_idx, (int64_t)h->support.size(), h->sv_coef, (int64_t)coef.size()));
+    PRG_HIP(hipMemcpyAsync(h->sv_idx.p, h->support.data(), h->support.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    PRG_HIP(hipMemcpyAsync(h->sv_coef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->solved = true;
     *n_iter_host = rounds;
@@ -475,25 +460,19 @@ int prg_ocsvm_decision(prg_ocsvm* h, const double* points_hd, int64_t k, double*
     const int st = padded_points(points_hd, k, h->dim, pad);
     PRG_REQUIRE(st != PRG_ERR_INVALID, PRG_ERR_INVALID, "prg_ocsvm_decision: points contain NaN or infinity");
     PRG_TRY(st);
-    double4* tg = nullptr;
-    double* out = nullptr;
-    PRG_HIP(hipMalloc((void**)&tg, (size_t)k * sizeof(double4)));
-    if (hipMalloc((void**)&out, (size_t)k * sizeof(double)) != hipSuccess) {
-        free_dev(tg);
+    prg::DevBuf<double4> tg;
+    prg::DevBuf<double> out;
+    PRG_HIP(tg.reset(k));
+    if (out.reset(k) != hipSuccess) {
         prg::set_error("prg_ocsvm_decision: out of device memory");
         return PRG_ERR_HIP;
     }
-    hipError_t e = hipMemcpyAsync(tg, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-        k_sweep<false><<<(unsigned)prg::ceil_div(k, kBlock), kBlock, 0, h->stream>>>(
-            tg, k, h->xs, h->sv_idx, h->sv_coef, (int64_t)h->support.size(), h->gamma, out, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(out_hd, out, (size_t)k * sizeof(double), hipMemcpyDefault);
-    free_dev(tg);
-    free_dev(out);
-    PRG_HIP(e);
+    PRG_HIP(hipMemcpyAsync(tg.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    k_sweep<false><<<(unsigned)prg::ceil_div(k, kBlock), kBlock, 0, h->stream>>>(
+        tg.p, k, h->xs.p, h->sv_idx.p, h->sv_coef.p, (int64_t)h->support.size(), h->gamma, out.p, nullptr);
+    PRG_HIP(hipGetLastError());
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(out_hd, out.p, (size_t)k * sizeof(double), hipMemcpyDefault));
     return PRG_OK;
 }
 

@@ -195,8 +195,9 @@ int device_kd_order(const float* pts_dev, int64_t n64, int dim, int* perm_dev, h
     const size_t off_keys = 0, off_keys2 = off_keys + round_up((int64_t)n * 8, 256), off_perm2 = off_keys2 + round_up((int64_t)n * 8, 256),
                  off_start = off_perm2 + round_up((int64_t)n * 4, 256), off_split = off_start + round_up((int64_t)max_seg * 4, 256),
                  off_bbox = off_split + round_up((int64_t)max_seg, 256), off_sort = off_bbox + round_up((int64_t)max_seg * 24, 256);
-    char* scratch = nullptr;
-    PRG_HIP(hipMalloc((void**)&scratch, off_sort + sort_bytes + 256));
+    DevBuf<char> scratch_buf;
+    PRG_HIP(scratch_buf.reset((int64_t)(off_sort + sort_bytes + 256)));
+    char* const scratch = scratch_buf.p;
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(scratch + off_keys);
     unsigned long long* keys2 = reinterpret_cast<unsigned long long*>(scratch + off_keys2);
     int* perm_a = perm_dev;
@@ -232,8 +233,7 @@ int device_kd_order(const float* pts_dev, int64_t n64, int dim, int* perm_dev, h
     if (st_code == PRG_OK && perm_a != perm_dev)
         check(hipMemcpyAsync(perm_dev, perm_a, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
     check(hipGetLastError());
-    check(hipStreamSynchronize(st));  // (the host vectors above were the sources of asynchronous copies; the scratch goes now)
-    (void)hipFree(scratch);
+    check(hipStreamSynchronize(st));  // (the host vectors above were the sources of asynchronous copies; the scratch goes on return)
     return st_code;
 }
 
@@ -253,19 +253,16 @@ extern "C" int prg_spatial_order(const float* points_hd, int64_t n, int dim, int
         std::copy(perm.begin(), perm.end(), perm_host);
         return PRG_OK;
     }
-    float* pts = nullptr;
-    int* perm = nullptr;
-    PRG_HIP(hipMalloc((void**)&pts, (size_t)n * dim * sizeof(float)));
+    prg::DevBuf<float> pts;
+    prg::DevBuf<int> perm;
+    PRG_HIP(pts.reset(n * dim));
     int st = PRG_OK;
-    if (hipMalloc((void**)&perm, (size_t)n * sizeof(int)) != hipSuccess) {
-        (void)hipFree(pts);
+    if (perm.reset(n) != hipSuccess) {
         prg::set_error("prg_spatial_order: out of device memory");
         return PRG_ERR_NOMEM;
     }
-    if (hipMemcpy(pts, points_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault) != hipSuccess) st = PRG_ERR_HIP;
-    if (st == PRG_OK) st = prg::device_kd_order(pts, n, dim, perm, nullptr);
-    if (st == PRG_OK && hipMemcpy(perm_host, perm, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) st = PRG_ERR_HIP;
-    (void)hipFree(pts);
-    (void)hipFree(perm);
+    if (hipMemcpy(pts.p, points_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault) != hipSuccess) st = PRG_ERR_HIP;
+    if (st == PRG_OK) st = prg::device_kd_order(pts.p, n, dim, perm.p, nullptr);
+    if (st == PRG_OK && hipMemcpy(perm_host, perm.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) st = PRG_ERR_HIP;
     return st;
 }

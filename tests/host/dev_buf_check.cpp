@@ -131,6 +131,48 @@ static void check_groups() {
     CHECK(g_live.empty() && g_bad_frees == 0 && g_allocs == g_frees);
 }
 
+// reset_group (dev_buf.h): buffers of different element types that are sized together.  For every position k of the failing
+// allocation, on a group that already holds blocks of another size: the first error comes back, every buffer is empty, the old
+// blocks were freed exactly once, nothing is live - and the same call succeeds afterwards.
+static void check_reset_group() {
+    using prg::DevBuf;
+    for (int k = 1; k <= 4; ++k) {
+        DevBuf<double> a;
+        DevBuf<int> b;
+        DevBuf<float4> c;
+        DevBuf<char> d;
+        CHECK(prg::reset_group(a, 10, b, 20, c, 30, d, 40) == hipSuccess && g_live.size() == 4 && g_last_bytes == 40);
+        CHECK(a.p && b.p && c.p && d.p && a.cap == 10 && b.cap == 20 && c.cap == 30 && d.cap == 40);
+        a.p[9] = 1.0, b.p[19] = 1, c.p[29].w = 1.f, d.p[39] = 1;  // (the sanitizer checks the extents)
+        const int allocs = g_allocs, frees = g_frees;
+        g_fail_in = k;
+        CHECK(prg::reset_group(a, 11, b, 21, c, 31, d, 41) == hipErrorOutOfMemory);
+        CHECK(empty(a) && empty(b) && empty(c) && empty(d));
+        // the four old blocks and the k - 1 new ones, each freed once
+        CHECK(g_allocs == allocs + k - 1 && g_frees == frees + 4 + k - 1 && g_live.empty() && g_bad_frees == 0);
+        CHECK(prg::reset_group(a, 11, b, 21, c, 31, d, 41) == hipSuccess && g_live.size() == 4);
+        CHECK(a.cap == 11 && b.cap == 21 && c.cap == 31 && d.cap == 41 && g_last_bytes == 41);
+        c.p[30].x = 1.f;
+    }
+    CHECK(g_live.empty() && g_bad_frees == 0 && g_allocs == g_frees);
+    {
+        // a count of 0 inside a group: that buffer is empty, which is no failure, and allocates nothing
+        DevBuf<double> a;
+        DevBuf<int> b;
+        DevBuf<float4> c;
+        CHECK(prg::reset_group(a, 5, b, 5, c, 5) == hipSuccess && g_live.size() == 3);
+        const int allocs = g_allocs;
+        CHECK(prg::reset_group(a, 7, b, 0, c, 9) == hipSuccess && a.cap == 7 && empty(b) && c.cap == 9);
+        CHECK(g_allocs == allocs + 2 && g_live.size() == 2);
+        g_fail_in = 2;  // c's allocation, the second one
+        CHECK(prg::reset_group(a, 8, b, 0, c, 10) == hipErrorOutOfMemory && empty(a) && empty(b) && empty(c) && g_live.empty());
+        CHECK(prg::reset_group(a, 8, b, 0, c, 10) == hipSuccess && a.cap == 8 && empty(b) && c.cap == 10 && g_live.size() == 2);
+        prg::release_all(a, b, c);
+        CHECK(empty(a) && empty(b) && empty(c) && g_live.empty());
+    }
+    CHECK(g_bad_frees == 0 && g_allocs == g_frees);
+}
+
 int main() {
     using prg::DevBuf;
     using prg::HostBuf;
@@ -201,6 +243,7 @@ int main() {
     }
     CHECK(g_live.empty() && g_bad_frees == 0);
     check_groups();
+    check_reset_group();
     {
         HostBuf<double> pinned;
         CHECK(pinned.ensure(64, hipHostMallocDefault) == hipSuccess && pinned.p && !pinned.dev);
