@@ -2,11 +2,7 @@
 // (radius + max_nn) neighbour search, PCA normals, the simplified point feature histograms and their 1 / d^2 weighted
 // gather.  Everything in fp64; DESIGN.md section 3.9 is the definition with every tie rule.  One stage per entry point:
 //
-//   grid     cell edge = search radius.  Cell coordinates are clamped to [0, 2^30); the cell key is the row-major index
-//            while the whole box has at most `table` cells and a multiplicative hash of the coordinates into `table`
-//            buckets otherwise, so a far outlier costs no memory.  table = the power of two >= 2 n in [2^10, 2^26].
-//            Points are sorted by key (stable radix sort: ascending point index inside a bucket) and gathered, buckets
-//            get (begin, end).  A bucket may hold several cells; the search filters by distance, so that only costs time.
+//   grid     the cell grid of cell_grid.h with cell edge = search radius, built anew for every search.
 //   search   one wave per query.  The cells that meet [p - r, p + r] (2 to 4 per axis) are dealt to the lanes, keys that
 //            repeat (hash collisions) are dropped, then the wave walks the buckets 64 candidates at a time.  Pass 1 counts
 //            the candidates.  If they do not fit the list, an MSB-first radix select (8 bits per pass, 256 counters in
@@ -33,70 +29,20 @@
 #include <new>
 #include <vector>
 
+#include "cell_grid.h"
 #include "dev_buf.h"
 #include "prg_common.h"
-
-namespace prg {
-int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
-                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream);  // lattice_sort.hip
-}
 
 namespace {
 
 constexpr int kWave = 64;              // every per-point kernel is one wave per workgroup: __syncthreads is wave-local
-constexpr int kBlock = 256;            // point-parallel helper kernels
 constexpr int kMaxNN = 512;            // longest neighbour list (LDS of the search, normals and spfh kernels)
 constexpr int kBins = 33;              // 3 groups of 11
-constexpr double kCellMax = 1073741823.0;  // cell coordinates are clamped to [0, 2^30)
 constexpr double kReach = 1.0 + 1.0e-12;   // the scanned box is a hair wider than r: covers the rounding of d2 <= r * r
-constexpr unsigned kMinTableBits = 10, kMaxTableBits = 26;
 
-struct Grid {
-    double lo[3];
-    double edge;
-    int dim[3];
-    unsigned mask;  // table - 1
-    int dense;
-};
-
-// Monotone in x, clamped: neighbours within one edge stay within one cell whatever the magnitudes.
-__host__ __device__ inline int cell_of(double x, double lo, double edge) {
-    double c = floor((x - lo) / edge);
-    c = c > 0.0 ? c : 0.0;  // (also NaN -> 0)
-    c = c < kCellMax ? c : kCellMax;
-    return (int)c;
-}
-
-__device__ inline unsigned cell_key(int cx, int cy, int cz, const Grid& g) {
-    if (g.dense) return ((unsigned)cz * (unsigned)g.dim[1] + (unsigned)cy) * (unsigned)g.dim[0] + (unsigned)cx;
-    // Teschner et al. 2003, "Optimized spatial hashing for collision detection of deformable objects"
-    const uint64_t h = ((uint64_t)cx * 73856093ull) ^ ((uint64_t)cy * 19349663ull) ^ ((uint64_t)cz * 83492791ull);
-    return (unsigned)(h ^ (h >> 29)) & g.mask;
-}
-
-__global__ __launch_bounds__(kBlock) void k_cell_keys(const double4* __restrict__ pts, int n, Grid g,
-                                                      unsigned* __restrict__ keys, int* __restrict__ vals) {
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n) return;
-    const double4 p = pts[t];
-    keys[t] = cell_key(cell_of(p.x, g.lo[0], g.edge), cell_of(p.y, g.lo[1], g.edge), cell_of(p.z, g.lo[2], g.edge), g);
-    vals[t] = t;
-}
-
-// sorted points with the point index in .w, and (begin, end) of every bucket (both zeroed before)
-__global__ __launch_bounds__(kBlock) void k_cell_bounds(const double4* __restrict__ pts, const unsigned* __restrict__ skeys,
-                                                        const int* __restrict__ order, int n, double4* __restrict__ sp,
-                                                        int* __restrict__ cbegin, int* __restrict__ cend) {
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n) return;
-    const int i = order[t];
-    double4 p = pts[i];
-    p.w = (double)i;
-    sp[t] = p;
-    const unsigned key = skeys[t];
-    if (t == 0 || skeys[t - 1] != key) cbegin[key] = t;
-    if (t == n - 1 || skeys[t + 1] != key) cend[key] = t + 1;
-}
+using prg::CellGrid;
+using prg::cell_key;
+using prg::cell_of;
 
 __device__ inline int wave_sum(int v) {
 #pragma unroll
@@ -146,9 +92,8 @@ __device__ inline void for_candidates(const double4* __restrict__ sp, int my_b, 
 
 // One wave per query (workgroup q handles the q-th point in cell order).  Row `self` of out_idx / out_d2 (k entries) gets
 // the query first, then its neighbours by ascending (d2, index), cut to k; unused entries are (-1, 0).
-__global__ __launch_bounds__(kWave) void k_search(const double4* __restrict__ sp, const int* __restrict__ cbegin,
-                                                  const int* __restrict__ cend, Grid g, double r, int k,
-                                                  int* __restrict__ out_idx, double* __restrict__ out_d2,
+__global__ __launch_bounds__(kWave) void k_search(const double4* __restrict__ sp, const int2* __restrict__ cells, CellGrid g,
+                                                  double r, int k, int* __restrict__ out_idx, double* __restrict__ out_d2,
                                                   int* __restrict__ out_cnt) {
     __shared__ int hist[256];
     __shared__ double l_d2[kMaxNN];
@@ -179,7 +124,8 @@ __global__ __launch_bounds__(kWave) void k_search(const double4* __restrict__ sp
         dup = dup || (c < lane && kc == key);
     }
     const bool live = lane < ncell && !dup;
-    const int my_b = live ? cbegin[key] : 0, my_e = live ? cend[key] : 0;
+    const int2 be = live ? cells[key] : make_int2(0, 0);
+    const int my_b = be.x, my_e = be.y;
 
     int cand = 0;
     for_candidates(sp, my_b, my_e, ncell, p, self, r2, [&](bool v, int, double) { cand += v ? 1 : 0; });
@@ -496,52 +442,20 @@ struct prg_fpfh {
 
 namespace {
 
-struct GridScratch {
-    prg::DevBuf<unsigned> keys;  // 2 n: unsorted, sorted
-    prg::DevBuf<int> vals;       // 2 n: iota, order
-    prg::DevBuf<int> cells;      // 2 table: begin, end
-    prg::DevBuf<double4> sp;
-    prg::DevBuf<char> tmp;
-};
-
 int run_search(prg_fpfh* h, NeighbourLists& out, double radius, int k) {
-    const int n = (int)h->n;
-    hipStream_t st = h->stream;
-    Grid g;
-    unsigned bits = kMinTableBits;
-    while (bits < kMaxTableBits && ((int64_t)1 << bits) < 2 * (int64_t)n) ++bits;
-    const int64_t table = (int64_t)1 << bits;
-    g.edge = radius;
-    g.mask = (unsigned)(table - 1);
-    double cells = 1.0;
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = h->lo[a];
-        g.dim[a] = cell_of(h->hi[a], h->lo[a], radius) + 1;
-        cells *= (double)g.dim[a];
-    }
-    g.dense = cells <= (double)table ? 1 : 0;
-
-    GridScratch s;
-    PRG_HIP(s.keys.reset(2 * (int64_t)n));
-    PRG_HIP(s.vals.reset(2 * (int64_t)n));
-    PRG_HIP(s.cells.reset(2 * table));
-    PRG_HIP(s.sp.reset(n));
-    unsigned* const keys = s.keys.p;
-    int* const vals = s.vals.p;
-    int* const cbegin = s.cells.p;
-    size_t need = 0;
-    PRG_TRY(prg::sort_pairs_u32(nullptr, &need, keys, keys + n, vals, vals + n, (unsigned)n, bits, st));
-    PRG_HIP(s.tmp.reset((int64_t)need + 256));
-    const unsigned nbk = (unsigned)prg::ceil_div(n, kBlock);
-    k_cell_keys<<<nbk, kBlock, 0, st>>>(h->pts.p, n, g, keys, vals);
+    const int64_t n = h->n;
+    const unsigned bits = prg::cell_table_bits(n);
+    const CellGrid g = prg::make_cell_grid(h->lo, h->hi, radius, bits);
+    prg::CellGridScratch s;
+    prg::DevBuf<double4> sp;
+    prg::DevBuf<int2> cells;
+    PRG_TRY(s.size(n, bits));
+    PRG_HIP(sp.reset(n));
+    PRG_HIP(cells.reset(prg::cell_entries(g)));
+    PRG_TRY(prg::build_cell_grid(g, bits, h->pts.p, n, s, sp.p, cells.p, h->stream));
+    k_search<<<(unsigned)n, kWave, 0, h->stream>>>(sp.p, cells.p, g, radius, k, out.idx.p, out.d2.p, out.cnt.p);
     PRG_HIP(hipGetLastError());
-    PRG_TRY(prg::sort_pairs_u32(s.tmp.p, &need, keys, keys + n, vals, vals + n, (unsigned)n, bits, st));
-    PRG_HIP(hipMemsetAsync(cbegin, 0, 2 * (size_t)table * sizeof(int), st));
-    k_cell_bounds<<<nbk, kBlock, 0, st>>>(h->pts.p, keys + n, vals + n, n, s.sp.p, cbegin, cbegin + table);
-    PRG_HIP(hipGetLastError());
-    k_search<<<(unsigned)n, kWave, 0, st>>>(s.sp.p, cbegin, cbegin + table, g, radius, k, out.idx.p, out.d2.p, out.cnt.p);
-    PRG_HIP(hipGetLastError());
-    PRG_HIP(hipStreamSynchronize(st));  // the scratch goes away with this scope
+    PRG_HIP(hipStreamSynchronize(h->stream));  // the scratch goes away with this scope
     return PRG_OK;
 }
 
@@ -580,18 +494,9 @@ int prg_fpfh_set_data(prg_fpfh* h, const double* points_hd, int64_t n) {
     PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_fpfh_set_data: NULL argument");
     PRG_REQUIRE(n >= 1 && n <= (int64_t)1 << 30, PRG_ERR_INVALID, "prg_fpfh_set_data: need 1 <= n <= 2^30 points");
     prg::DeviceGuard g(h->device);
-    std::vector<double> raw((size_t)n * 3), pad((size_t)n * 4, 0.0);
-    PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    std::vector<double> raw, pad;
     double lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = raw[a];
-    for (int64_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const double v = raw[(size_t)i * 3 + a];
-            PRG_REQUIRE(std::isfinite(v), PRG_ERR_INVALID, "prg_fpfh_set_data: data contains NaN or infinity");
-            pad[(size_t)i * 4 + a] = v;
-            lo[a] = std::min(lo[a], v);
-            hi[a] = std::max(hi[a], v);
-        }
+    PRG_TRY(prg::load_cloud3(points_hd, n, "prg_fpfh_set_data: data contains NaN or infinity", raw, pad, lo, hi));
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->n = 0;
     h->have_normals = h->have_spfh = h->have_fpfh = false;

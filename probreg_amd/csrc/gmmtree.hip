@@ -19,12 +19,8 @@
 #include <vector>
 
 #include "dev_buf.h"
+#include "lattice_sort.h"
 #include "prg_common.h"
-
-namespace prg {
-int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
-                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream);
-}
 
 namespace {
 

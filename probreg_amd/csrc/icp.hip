@@ -2,9 +2,7 @@
 // generalized ICP (plane-to-plane) on the same search, sums and loop.  All in fp64 with fixed-order sums and
 // no floating-point atomics.
 //
-//   grid     built once per target: cell key per point (row-major while the box has at most `table` cells, a multiplicative
-//            hash of the clamped cell coordinates otherwise - the scheme of fpfh.hip), stable radix sort, bucket bounds, points
-//            gathered in cell order with the original index in .w.  The cell edge comes from the cloud (a few points per
+//   grid     the cell grid of cell_grid.h, built once per target.  The cell edge comes from the cloud (a few points per
 //            occupied cell), never from the search radius.  Coarser levels (edge x kLevelStep each, until the box is one or
 //            two cells wide - always reached, see floor_edge) are built the same way: they carry a query that is far from the cloud
 //            over the empty space, and the last one bounds every search.
@@ -34,23 +32,18 @@
 #include <new>
 #include <vector>
 
+#include "cell_grid.h"
 #include "dev_buf.h"
 #include "kabsch_pose.h"
+#include "lattice_sort.h"
 #include "prg_common.h"
-
-namespace prg {
-int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
-                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream);  // lattice_sort.hip
-}
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kRun = 64;                   // source points per run of the ordered sums (part of the definition)
 constexpr int kSlots = 32;                 // sums per run: 8 / 9 (point-to-point, two passes), 29 (point-to-plane), 30 (generalized)
-constexpr double kCellMax = 1073741823.0;  // cell coordinates are clamped to [0, 2^30)
 constexpr double kReach = 1.0 + 1.0e-12;   // the stop bound is a hair smaller than (s h)^2 + D^2: covers the rounding of d2
-constexpr unsigned kMinTableBits = 10, kMaxTableBits = 26;
 constexpr int kOrderBits = 10;             // per axis, of the Morton key that orders the queries
 constexpr double kPivot = 1.0e-12;         // a Cholesky pivot <= kPivot max diag(A) is degenerate (part of the definition)
 constexpr int kSample = 16384;             // points that choose the cell edge
@@ -66,61 +59,16 @@ constexpr int kStatusOk = 0, kStatusTooFew = 1, kStatusDegenerate = 2;
 constexpr int kPointToPoint = 0, kPointToPlane = 1, kGeneralized = 2;
 constexpr int kCov = 6;  // doubles per covariance: xx, xy, xz, yy, yz, zz
 
-struct Grid {
-    double lo[3], hi[3];  // the target's box
-    double edge;
-    double slack;         // cells: what the rounding of (x - lo) / edge can move a cell difference by
-    int dim[3];
-    unsigned mask;        // table - 1
-    int dense;
-};
+using prg::CellGrid;
+using prg::cell_key;
+using prg::cell_of;
 
 struct Levels {
     int count;
-    Grid g[kMaxLevels];
+    CellGrid g[kMaxLevels];
     const double4* sp[kMaxLevels];  // the points in the cell order of the level, original index in .w
     const int2* cells[kMaxLevels];  // (begin, end) of every bucket
 };
-
-// Monotone in x and clamped, so a difference of clamped cells never exceeds the difference of the unclamped ones.
-__host__ __device__ inline int cell_of(double x, double lo, double edge) {
-    double c = floor((x - lo) / edge);
-    c = c > 0.0 ? c : 0.0;
-    c = c < kCellMax ? c : kCellMax;
-    return (int)c;
-}
-
-__device__ inline unsigned cell_key(int cx, int cy, int cz, const Grid& g) {
-    if (g.dense) return ((unsigned)cz * (unsigned)g.dim[1] + (unsigned)cy) * (unsigned)g.dim[0] + (unsigned)cx;
-    // Teschner et al. 2003, "Optimized spatial hashing for collision detection of deformable objects"
-    const uint64_t h = ((uint64_t)cx * 73856093ull) ^ ((uint64_t)cy * 19349663ull) ^ ((uint64_t)cz * 83492791ull);
-    return (unsigned)(h ^ (h >> 29)) & g.mask;
-}
-
-// ----------------------------------------------------------------------------------------------------------------- grid
-__global__ __launch_bounds__(kBlock) void k_icp_cell_keys(const double4* __restrict__ pts, int64_t n, Grid g,
-                                                          unsigned* __restrict__ keys, int* __restrict__ vals) {
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n) return;
-    const double4 p = pts[t];
-    keys[t] = cell_key(cell_of(p.x, g.lo[0], g.edge), cell_of(p.y, g.lo[1], g.edge), cell_of(p.z, g.lo[2], g.edge), g);
-    vals[t] = (int)t;
-}
-
-// points (index in .w) in cell order, and (begin, end) of every bucket (zeroed before)
-__global__ __launch_bounds__(kBlock) void k_icp_cell_bounds(const double4* __restrict__ pts, const unsigned* __restrict__ skeys,
-                                                            const int* __restrict__ order, int64_t n, double4* __restrict__ sp,
-                                                            int2* __restrict__ cells) {
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n) return;
-    const int i = order[t];
-    double4 p = pts[i];
-    p.w = (double)i;
-    sp[t] = p;
-    const unsigned key = skeys[t];
-    if (t == 0 || skeys[t - 1] != key) cells[key].x = (int)t;
-    if (t == n - 1 || skeys[t + 1] != key) cells[key].y = (int)(t + 1);
-}
 
 // q_a = ((R_a0 p_0 + R_a1 p_1) + R_a2 p_2) + t_a
 __device__ __forceinline__ void moved(const double (&m)[12], const double* __restrict__ p, double (&q)[3]) {
@@ -139,7 +87,7 @@ __device__ __forceinline__ unsigned spread10(unsigned v) {  // 10 bits -> every 
 
 // Morton key of the moved source point on a 2^kOrderBits grid over the target's box (clamped): orders the queries only
 __global__ __launch_bounds__(kBlock) void k_icp_query_keys(const double* __restrict__ src, int64_t M,
-                                                           const double* __restrict__ state, Grid g, double scale,
+                                                           const double* __restrict__ state, CellGrid g, double scale,
                                                            unsigned* __restrict__ keys, int* __restrict__ vals) {
     const int64_t m = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (m >= M) return;
@@ -166,7 +114,7 @@ struct Best {
 };
 
 // every point of the bucket of cell (cx, cy, cz): d2 = (dx dx + dy dy) + dz dz, minimum of (d2, index)
-__device__ __forceinline__ void visit(const double4* __restrict__ sp, const int2* __restrict__ cells, const Grid& g, int cx,
+__device__ __forceinline__ void visit(const double4* __restrict__ sp, const int2* __restrict__ cells, const CellGrid& g, int cx,
                                       int cy, int cz, const double (&q)[3], Best& b) {
     const int2 be = cells[cell_key(cx, cy, cz, g)];
     for (int t = be.x; t < be.y; ++t) {
@@ -185,7 +133,7 @@ __device__ __forceinline__ void visit(const double4* __restrict__ sp, const int2
 // (a hair more) from it: cell_of is monotone, so a point in a cell below lo[a] has y_a < q_a - rho and d2 > rho^2.  Returns
 // true when the search is over: the best d2 is strictly below what anything unvisited can have, that bound exceeds r, or every
 // cell that matters has been visited.  false: `shells` shells were not enough (never on the last level).
-__device__ inline bool walk_level(const Grid& g, const double4* __restrict__ sp, const int2* __restrict__ cells,
+__device__ inline bool walk_level(const CellGrid& g, const double4* __restrict__ sp, const int2* __restrict__ cells,
                                   const double (&q)[3], double box2, double r2, int shells, double& rho, Best& b) {
     int c[3], lo[3], hi[3];
 #pragma unroll
@@ -681,7 +629,7 @@ int ensure_order(prg_icp* h) {
     if (h->have_order) return PRG_OK;
     const int64_t M = h->M;
     hipStream_t st = h->stream;
-    const Grid& g = h->lv.g[0];
+    const CellGrid& g = h->lv.g[0];
     const double ext = std::max(g.hi[0] - g.lo[0], std::max(g.hi[1] - g.lo[1], g.hi[2] - g.lo[2]));
     const double scale = ext > 0.0 ? (double)(1 << kOrderBits) / ext : 0.0;
     size_t need = 0;
@@ -761,75 +709,35 @@ int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normal
     PRG_HIP(hipStreamSynchronize(st));
     h->N = 0;
     h->have_normals = h->have_order = h->have_matches = h->have_cov[1] = false;
-    std::vector<double> raw((size_t)n * 3), pad((size_t)n * 4, 0.0);
-    PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
+    std::vector<double> raw, pad;
     double lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = raw[a];
-    for (int64_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const double v = raw[(size_t)i * 3 + a];
-            PRG_REQUIRE(std::isfinite(v), PRG_ERR_INVALID, "prg_icp_set_target: the points contain NaN or infinity");
-            pad[(size_t)i * 4 + a] = v;
-            lo[a] = std::min(lo[a], v);
-            hi[a] = std::max(hi[a], v);
-        }
+    PRG_TRY(prg::load_cloud3(points_hd, n, "prg_icp_set_target: the points contain NaN or infinity", raw, pad, lo, hi));
     const double edge0 = floor_edge(cell_edge > 0.0 ? cell_edge : choose_edge(raw, n, lo, hi), lo, hi);
-    unsigned bits = kMinTableBits;
-    while (bits < kMaxTableBits && ((int64_t)1 << bits) < 2 * n) ++bits;
-    const int64_t table = (int64_t)1 << bits;
+    const unsigned bits = prg::cell_table_bits(n);
 
     PRG_HIP(h->tp.ensure(n, n));
     PRG_HIP(hipMemcpy(h->tp.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
     if (normals_hd) {
-        PRG_HIP(hipMemcpy(raw.data(), normals_hd, raw.size() * sizeof(double), hipMemcpyDefault));
-        for (int64_t i = 0; i < n; ++i)
-            for (int a = 0; a < 3; ++a) {
-                PRG_REQUIRE(std::isfinite(raw[(size_t)i * 3 + a]), PRG_ERR_INVALID,
-                            "prg_icp_set_target: the normals contain NaN or infinity");
-                pad[(size_t)i * 4 + a] = raw[(size_t)i * 3 + a];
-            }
+        PRG_TRY(prg::load_cloud3(normals_hd, n, "prg_icp_set_target: the normals contain NaN or infinity", raw, pad, nullptr,
+                                 nullptr));
         PRG_HIP(h->tn.ensure(n, n));
         PRG_HIP(hipMemcpy(h->tn.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    prg::DevBuf<unsigned> keys;
-    prg::DevBuf<int> vals;
-    PRG_HIP(keys.reset(2 * n));
-    PRG_HIP(vals.reset(2 * n));
-    size_t need = 0;
-    PRG_TRY(prg::sort_pairs_u32(nullptr, &need, keys.p, keys.p + n, vals.p, vals.p + n, (unsigned)n, bits, st));
-    PRG_HIP(h->sort_tmp.ensure((int64_t)need + 256, (int64_t)need + 256));
-    const unsigned nb = (unsigned)prg::ceil_div(n, kBlock);
+    prg::CellGridScratch scratch;
+    PRG_TRY(scratch.size(n, bits));
     Levels& lv = h->lv;
     lv.count = 0;
     double edge = edge0;
     for (int k = 0; k < kMaxLevels; ++k, edge *= kLevelStep) {  // ends at a level at most two cells wide (floor_edge)
-        Grid& gr = lv.g[k];
-        gr.edge = edge;
-        gr.mask = (unsigned)(table - 1);
-        double cells = 1.0;
-        int dim_max = 1;
-        for (int a = 0; a < 3; ++a) {
-            gr.lo[a] = lo[a];
-            gr.hi[a] = hi[a];
-            gr.dim[a] = cell_of(hi[a], lo[a], edge) + 1;
-            cells *= (double)gr.dim[a];
-            dim_max = std::max(dim_max, gr.dim[a]);
-        }
-        gr.dense = cells <= (double)table ? 1 : 0;
-        gr.slack = std::ldexp((double)dim_max + 1.0, -48);
-        const int64_t entries = gr.dense ? (int64_t)cells : table;  // a dense level needs one entry per cell, no more
+        const CellGrid gr = lv.g[k] = prg::make_cell_grid(lo, hi, edge, bits);
+        const int64_t entries = prg::cell_entries(gr);
         PRG_HIP(h->sp[k].ensure(n, n));
         PRG_HIP(h->cells[k].ensure(entries, entries));
-        k_icp_cell_keys<<<nb, kBlock, 0, st>>>(h->tp.p, n, gr, keys.p, vals.p);
-        PRG_HIP(hipGetLastError());
-        PRG_TRY(prg::sort_pairs_u32(h->sort_tmp.p, &need, keys.p, keys.p + n, vals.p, vals.p + n, (unsigned)n, bits, st));
-        PRG_HIP(hipMemsetAsync(h->cells[k].p, 0, (size_t)entries * sizeof(int2), st));
-        k_icp_cell_bounds<<<nb, kBlock, 0, st>>>(h->tp.p, keys.p + n, vals.p + n, n, h->sp[k].p, h->cells[k].p);
-        PRG_HIP(hipGetLastError());
+        PRG_TRY(prg::build_cell_grid(gr, bits, h->tp.p, n, scratch, h->sp[k].p, h->cells[k].p, st));
         lv.sp[k] = h->sp[k].p;
         lv.cells[k] = h->cells[k].p;
         lv.count = k + 1;
-        if (dim_max <= 2) break;  // at most 27 cells hold every point: whatever the query, this level ends its search
+        if (std::max(gr.dim[0], std::max(gr.dim[1], gr.dim[2])) <= 2) break;  // 27 cells hold every point: this level ends any search
     }
     PRG_HIP(hipStreamSynchronize(st));  // the scratch goes away with this scope
     PRG_TRY(ensure_state(h));

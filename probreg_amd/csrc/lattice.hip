@@ -22,11 +22,8 @@
 #include "prg_device.h"
 #include "prg_common.h"
 #include "lattice.h"
+#include "lattice_sort.h"
 
-namespace prg {
-int sort_pairs_u32(void* tmp, size_t* tmp_bytes, const unsigned* keys_in, unsigned* keys_out, const int* vals_in,
-                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream);  // lattice_sort.hip
-}
 using prg::FrFeat;
 using prg::LatticeMail;
 

@@ -17,12 +17,8 @@
 
 #include "block_scan.h"
 #include "dev_buf.h"
+#include "lattice_sort.h"
 #include "prg_common.h"
-
-namespace prg {
-int sort_pairs_u64(void* tmp, size_t* tmp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const int* vals_in,
-                   int* vals_out, unsigned n, unsigned bits, hipStream_t stream);
-}
 
 namespace {
 

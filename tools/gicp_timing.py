@@ -92,7 +92,7 @@ def short(name):
         if "k_icp_sums<%s>" % mode in name or "k_icp_sumsILi%sE" % mode in name:
             return "k_icp_sums<%s>" % mode
     for key in ("k_icp_search", "k_icp_sums", "k_icp_finish", "k_icp_step", "k_icp_reset", "k_icp_query_keys",
-                "k_icp_cov_from_normals", "k_icp_cell_keys", "k_icp_cell_bounds"):
+                "k_icp_cov_from_normals", "k_cell_keys", "k_cell_bounds"):
         if key in name:
             return key
     return "sort (rocPRIM)"

@@ -97,7 +97,7 @@ def worker(mode, n, radii, work, rounds):
 
 
 def short(name):
-    for key in ("k_icp_search", "k_icp_sums", "k_icp_finish", "k_icp_step", "k_icp_reset", "k_icp_cell_keys", "k_icp_cell_bounds",
+    for key in ("k_icp_search", "k_icp_sums", "k_icp_finish", "k_icp_step", "k_icp_reset", "k_cell_keys", "k_cell_bounds",
                 "k_icp_query_keys", "k_nn_min", "k_nn_fill", "k_nn_mean"):
         if key in name:
             return key
