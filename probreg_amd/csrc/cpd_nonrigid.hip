@@ -454,10 +454,7 @@ int build_kernel_matrix(prg_cpd* h, int kind, double param) {
 }
 
 int nonrigid_free(prg_cpd* h) {
-    for (hipEvent_t e : h->nr_events) (void)hipEventDestroy(e);
-    h->nr_events.clear();
-    if (h->nr_stream2) (void)hipStreamDestroy(h->nr_stream2);
-    h->nr_stream2 = nullptr;
+    prg::spd_release(h->nr_queues);
     h->nr_prior.release();
     h->nr_alpha = 0.0;
     h->nr_solve.release();

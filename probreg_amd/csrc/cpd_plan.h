@@ -5,6 +5,7 @@
 
 #include "cpd_buffers.h"
 #include "prg_common.h"
+#include "spd_solve.h"
 
 // Which engine an E-step's sweeps run on while a registration is in the dense regime.  The decision needs
 // sigma2, the source motion of this E-step's transform and the previous E-step's largest column minimum - all of them on
@@ -220,8 +221,7 @@ struct prg_cpd : prg::SourceBuffers, prg::TargetBuffers {
     int* nr_info = nullptr;      // -> into nr_solve (cleared whenever that is re-created): first non-positive pivot + 1 of a low-rank M-step since the last report (0: none)
     prg::DevBuf<double> nr_prior;          // [4][M]: p1_tilde, px_tilde (3 planes) of ConstrainedNonRigidCPD
     double nr_alpha = 0.0;                 // 0 = no correspondence priors
-    hipStream_t nr_stream2 = nullptr;      // side stream of the look-ahead Cholesky
-    std::vector<hipEvent_t> nr_events;
+    prg::SpdQueues nr_queues;              // the plan stream + side stream and events of the look-ahead Cholesky (spd_solve.h)
 
     // per-source log-weights (BCPD E-step, bcpd.py:53-72): srcw[m] = ln a_m <= 0 in kernel (sorted) order; the
     // transform kernel turns it into the additive squared distance q_m = -2 sigma2 ln a_m carried in z4.w

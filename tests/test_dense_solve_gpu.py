@@ -1,4 +1,5 @@
-"""The blocked fp64 Cholesky solves of cpd_nonrigid_solve.hip, one M-step / one solve at a time, against LAPACK on the same
+"""The blocked fp64 Cholesky solves of spd_solve.hip through their drivers (cpd_nonrigid_solve.hip, cpd_bcpd_solve.hip), one
+M-step / one solve at a time, against LAPACK on the same
 matrix - per class of the look-ahead schedule (which kernels and streams run depends on ceil(M / 128) alone):
 
   block rows   M             what runs

@@ -126,7 +126,7 @@ def summarise(db, m, rank):
     rows = sqlite3.connect(db).cursor().execute("select name, count(*), sum(end-start) from kernels group by name").fetchall()
     per = {}
     for name, calls, total in rows:
-        short = name.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0].split("<")[0]
+        short = name.replace("(anonymous namespace)::", "").replace("prg::", "").replace("void ", "").split("(")[0].split("<")[0]
         per[short] = (calls, total / 1e3 / WORKER_SOLVES)   # us per M-step
     print("# low-rank M-step at M = %d (rank %d): device time per M-step by kernel group, us (kernel trace, %d M-steps)"
           % (m, rank, WORKER_SOLVES))

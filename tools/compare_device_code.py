@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the device code of two source trees the same, kernel by kernel?  (No GPU needed.)
 
-    python tools/compare_device_code.py OLD_TREE NEW_TREE [--work DIR] [-j N]
+    python tools/compare_device_code.py OLD_TREE NEW_TREE [--work DIR] [-j N] [--rename OLD_NAME=NEW_NAME ...]
 
 For each tree every .hip of probreg_amd/csrc is compiled with exactly the command its Makefile would run (taken from
 `make -n -B`) plus `--cuda-device-only --no-gpu-bundle-output`, which leaves one plain gfx950 ELF per file.  The kernels of an
@@ -56,8 +56,11 @@ def instructions(elf, name):
     for line in out.splitlines():
         line = re.sub(r"\s*//.*$", "", line).strip()  # "// 0000000012A4: ..." address / encoding comments
         # ("...": zero padding objdump skips behind the last symbol of a section - no instruction)
-        if line and line != "..." and not line.startswith(("Disassembly", elf)) and "file format" not in line:
+        # (the kernel's own label goes too: a kernel compared under --rename differs in nothing else)
+        if line and line not in ("...", "<%s>:" % name) and not line.startswith(("Disassembly", elf)) and "file format" not in line:
             body.append(line)
+    while body and body[-1] == "s_nop 0":  # alignment padding behind the program's end: s_nop before another kernel, zeros at
+        body.pop()                         # the end of the section - which of the two depends on the kernel's place in the file
     return body
 
 
@@ -81,9 +84,17 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--work", default="/tmp/compare_device_code")
     ap.add_argument("-j", type=int, default=8)
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="a kernel whose mangled name changed on purpose (say, it left an anonymous namespace to be declared "
+                         "in a header): OLD of the old tree is compared with NEW of the new one")
     a = ap.parse_args()
     old = tree_kernels(a.old, os.path.join(a.work, "old"), a.j)
     new = tree_kernels(a.new, os.path.join(a.work, "new"), a.j)
+    for pair in a.rename:
+        was, now = pair.split("=")
+        if was in old and was not in new and now in new and now not in old:
+            print("renamed  %s -> %s" % (was, now))
+            old[now] = old.pop(was)
     bad = 0
     files = lambda defs: ", ".join(src for _, src in defs)
     for name in sorted(set(old) | set(new)):
