@@ -5,7 +5,37 @@
 
 namespace prg {
 
+// Columns G + 1 and G + 2 (cyclic) of m from its unit column G: the coordinate axis least aligned with that column,
+// Gram-Schmidt, cross product.  m is then orthonormal with determinant +1.  Compile-time indices only (see jacobi_svd).
+template <int G>
+__device__ inline void complete_basis(double m[3][3]) {
+    constexpr int p = (G + 1) % 3, q = (G + 2) % 3;
+    const double a0 = fabs(m[0][G]), a1 = fabs(m[1][G]), a2 = fabs(m[2][G]);
+    const int ax = (a0 <= a1 && a0 <= a2) ? 0 : ((a1 <= a2) ? 1 : 2);
+    const double dp = (ax == 0) ? m[0][G] : ((ax == 1) ? m[1][G] : m[2][G]);
+    double v[3], nn = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        v[i] = ((i == ax) ? 1.0 : 0.0) - dp * m[i][G];
+        nn += v[i] * v[i];
+    }
+    nn = 1.0 / sqrt(nn);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) m[i][p] = v[i] * nn;
+    m[0][q] = m[1][G] * m[2][p] - m[2][G] * m[1][p];
+    m[1][q] = m[2][G] * m[0][p] - m[0][G] * m[2][p];
+    m[2][q] = m[0][G] * m[1][p] - m[1][G] * m[0][p];
+}
+
 // One-sided Jacobi SVD of a d x d (d <= 3) matrix: a = U diag(sv) V^T.  Returns U, V, sv (unsorted).
+// A column whose norm is at most 1e-14 of the largest one counts as zero: U is then completed to an orthonormal basis (one
+// such column: cross product; two: Gram-Schmidt against the least aligned axis, for U and for V; all: the identity), so U
+// and V are orthonormal for every rank.
+// Supported range: the column norms are plain sums of squares, so the entries must keep their squares inside fp64 -
+// roughly 1e-150 <= |a| <= 1e150 for the entries that matter.  Below that the squares underflow, alpha / beta / gamma
+// become 0 and the result is silently the identity (a rank-0 answer); above it they overflow to inf and U is no longer
+// orthonormal (|U U^T - I| of about 0.7 has been seen).  No point cloud gets near either end; tests/oracle_pose.py keeps
+// its scaled families inside 2^-80 .. 2^80.
 __device__ inline void jacobi_svd(const double a[3][3], int d, double U[3][3], double V[3][3], double sv[3]) {
     double g[3][3];
     for (int i = 0; i < 3; ++i)
@@ -90,28 +120,14 @@ __device__ inline void jacobi_svd(const double a[3][3], int d, double U[3][3], d
 #pragma unroll
                 for (int j = 0; j < 3; ++j) U[i][j] = (i == j) ? 1.0 : 0.0;
         } else if (nbad == 2) {
-#pragma unroll
-            for (int gcol = 0; gcol < 3; ++gcol) {
-                if (!ok[gcol]) continue;
-                constexpr int nxt[3] = {1, 2, 0}, nx2[3] = {2, 0, 1};
-                const int p = nxt[gcol], q = nx2[gcol];
-                // coordinate axis least aligned with the good column, Gram-Schmidt, cross product
-                const double a0 = fabs(U[0][gcol]), a1 = fabs(U[1][gcol]), a2 = fabs(U[2][gcol]);
-                const int ax = (a0 <= a1 && a0 <= a2) ? 0 : ((a1 <= a2) ? 1 : 2);
-                const double dp = (ax == 0) ? U[0][gcol] : ((ax == 1) ? U[1][gcol] : U[2][gcol]);
-                double v[3], nn = 0.0;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    v[i] = ((i == ax) ? 1.0 : 0.0) - dp * U[i][gcol];
-                    nn += v[i] * v[i];
-                }
-                nn = 1.0 / sqrt(nn);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) U[i][p] = v[i] * nn;
-                U[0][q] = U[1][gcol] * U[2][p] - U[2][gcol] * U[1][p];
-                U[1][q] = U[2][gcol] * U[0][p] - U[0][gcol] * U[2][p];
-                U[2][q] = U[0][gcol] * U[1][p] - U[1][gcol] * U[0][p];
-            }
+            // V gets the same completion as U.  The sweeps leave its two null columns as some orthonormal basis of the null
+            // space, turned by an angle that round-off decides (the two g columns they belong to are noise), and with them
+            // the rotation U diag V^T about the one direction the data fix: two runs whose rank-1 matrices differ in the last
+            // bit returned rotations half a turn apart.  With both completions taken from the good column alone the rotation
+            // is a continuous function of the matrix (the sign of the good pair (u, v) cancels in every u_k v_k^T).
+            if (ok[0]) { complete_basis<0>(U); complete_basis<0>(V); }
+            else if (ok[1]) { complete_basis<1>(U); complete_basis<1>(V); }
+            else { complete_basis<2>(U); complete_basis<2>(V); }
         }
     }
 }
