@@ -830,6 +830,38 @@ int prg_icp_set_covariances(prg_icp* h, int which, const double* cov_hd, int64_t
 int prg_icp_set_covariances_from_normals(prg_icp* h, int which, const double* normals_hd, int64_t n, double epsilon);
 /* The covariances of a cloud as they are stored, n x 6 float64 to the host.  Synchronises. */
 int prg_icp_get_covariances(prg_icp* h, int which, double* cov_host);
+/* ---- Exact k-nearest-neighbour lists, radius counts and the two outlier filters on the same grid, levels and query order
+ * (none of this is in the reference, whose examples leave cleaning a cloud to Open3D).  The queries
+ * are the source points moved by the pose, the cloud is the target; fp64, no floating-point atomics, byte-identical from run
+ * to run and independent of the grid.  Setting a cloud or the pose, a step and the loop drop the lists, counts and filter
+ * results; new lists drop the result of the statistical filter and new counts that of the radius filter, whose keep masks
+ * were made from the ones before. */
+/* The largest k of prg_icp_knn and prg_icp_outlier_statistical (64: one list entry per lane of a wave). */
+int prg_icp_max_k(int* out);
+/* For every moved source point the targets with d2 <= r * r in ascending (d2, index), cut to k entries; 1 <= k <= 64, r > 0,
+ * infinity allowed.  k = 1 is prg_icp_search.  A query that is itself a target point is an ordinary candidate with d2 = 0.
+ * Replaces: a kd-tree's search_knn / search_hybrid.  Enqueues only. */
+int prg_icp_knn(prg_icp* h, int k, double r);
+/* The lists of the last prg_icp_knn (or prg_icp_outlier_statistical): index_host m x k int32 and d2_host m x k float64, the
+ * slots past a list's length -1 and +inf; count_host m int32, the lengths.  Each may be NULL.  Synchronises. */
+int prg_icp_get_knn(prg_icp* h, int* index_host, double* d2_host, int* count_host);
+/* For every moved source point the number of targets with d2 <= r * r; r finite and > 0.  Replaces: the length of a kd-tree's
+ * search_radius.  Enqueues only. */
+int prg_icp_radius_count(prg_icp* h, double r);
+/* The counts of the last prg_icp_radius_count (or prg_icp_outlier_radius), m int32.  Synchronises. */
+int prg_icp_get_counts(prg_icp* h, int* count_host);
+/* Open3D's remove_statistical_outlier on the source, which the caller has also set as the target: the lists of k = nb_neighbors
+ * with r = infinity (the point itself is one of them), a_i the mean of their distances, mu and s the mean and the sample
+ * standard deviation of the a_i in runs of 64, thr = mu + std_ratio * s; point i is kept iff a_i <= thr (Open3D: <, and a_i > 0).
+ * std_ratio finite and >= 0.  Enqueues only. */
+int prg_icp_outlier_statistical(prg_icp* h, int k, double std_ratio);
+/* Open3D's remove_radius_outlier, source and target set alike: point i is kept iff its radius count, itself included, is
+ * > nb_points; r finite and > 0, nb_points >= 0.  Enqueues only. */
+int prg_icp_outlier_radius(prg_icp* h, double r, int nb_points);
+/* The last filter: keep_host m bytes (1 kept, 0 removed); after the statistical filter also score_host m float64 (a_i) and
+ * stat_host 3 float64 (mu, s, thr), which must be NULL after the radius filter (its scores are prg_icp_get_counts).  Each may
+ * be NULL.  Synchronises. */
+int prg_icp_get_outlier(prg_icp* h, unsigned char* keep_host, double* score_host, double* stat_host);
 
 #ifdef __cplusplus
 }

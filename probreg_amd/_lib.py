@@ -247,6 +247,14 @@ SIGNATURES = {
     "prg_icp_set_covariances": [_vp, _i, _vp, _i64],
     "prg_icp_set_covariances_from_normals": [_vp, _i, _vp, _i64, _d],
     "prg_icp_get_covariances": [_vp, _i, _vp],
+    "prg_icp_max_k": [_c.POINTER(_i)],
+    "prg_icp_knn": [_vp, _i, _d],
+    "prg_icp_get_knn": [_vp, _vp, _vp, _vp],
+    "prg_icp_radius_count": [_vp, _d],
+    "prg_icp_get_counts": [_vp, _vp],
+    "prg_icp_outlier_statistical": [_vp, _i, _d],
+    "prg_icp_outlier_radius": [_vp, _d, _i],
+    "prg_icp_get_outlier": [_vp, _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -19,6 +19,8 @@
 //   step     one lane: Kabsch (kabsch_pose.h) or the 6 x 6 Cholesky solve, then the pose update.
 //   gicp     a covariance per point (6 doubles, given or from a unit normal in closed form); per matched pair the 3 x 3
 //            M = C_target + R C_source R^T is inverted by its adjugate and weights the pair's 6 x 6 system (MODE 3 of the sums).
+//   knn      the k best instead of the best: one wave per query, the sorted list one entry per lane, on the
+//            same levels, shells, bound and clipping; a radius count; and the two outlier filters on top of them.
 // The loop "search, sums, step" stays on the device: its state (pose, stop flag, counters) is a device array, every kernel
 // returns at once when the stop flag is set, and the host looks at the flag once per chunk of iterations.
 //
@@ -203,6 +205,261 @@ __global__ __launch_bounds__(kBlock) void k_icp_search(Levels lv, const double* 
     const bool hit = b.idx >= 0 && b.d2 <= r2;
     out_idx[m] = hit ? b.idx : -1;
     out_d2[m] = hit ? b.d2 : INFINITY;
+}
+
+// ---------------------------------------------------------------------------------------------------- k nearest (3.17)
+// The k smallest (d2, index) among d2 <= r r, ascending: one wave per query, entry t of the sorted list in lane t.  `cnt`,
+// `kd2` and `kidx` (the last key of a full list: the pruning key) are the same in every lane.
+constexpr int kWave = 64;
+constexpr int kMaxK = kWave;   // one list entry per lane
+constexpr int kCountSpan = 4;  // the radius count walks the finest level on which the cube around r spans <= kCountSpan + 1 cells an axis
+
+struct KList {
+    double d2;
+    int idx;
+    int cnt;
+    double kd2;
+    int kidx;
+};
+
+__device__ __forceinline__ bool key_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
+
+// One candidate (the same values in every lane) into the wave's list.  A key that is in the list already is a second visit
+// of that point - a coarser level after the hand-over, two cells of one hashed bucket - and is dropped: d2 of a point is the
+// same bits on every visit, and the last key only shrinks, so a point that was once refused or pushed out stays out.
+__device__ __forceinline__ void knn_insert(KList& b, int k, int lane, double cd2, int cidx) {
+    const bool mine = lane < b.cnt;
+    const unsigned long long below = __ballot(mine && key_less(b.d2, b.idx, cd2, cidx));
+    const unsigned long long same = __ballot(mine && b.d2 == cd2 && b.idx == cidx);
+    const int pos = __popcll(below);  // the list is sorted: `below` is its first pos lanes
+    if (same != 0ull || pos >= k) return;
+    const double ud2 = __shfl_up(b.d2, 1);
+    const int uidx = __shfl_up(b.idx, 1);
+    if (lane > pos) {
+        b.d2 = ud2;
+        b.idx = uidx;
+    } else if (lane == pos) {
+        b.d2 = cd2;
+        b.idx = cidx;
+    }
+    b.cnt = min(b.cnt + 1, k);
+}
+
+// walk_level for a list.  The cells of the clipped shell are dealt to the lanes, every lane walks its bucket, and each round
+// of one point per lane goes into the list in lane order.  The stop test and the clipping use the k-th d2, and only when the
+// list is full; a shorter list ends by bound > r r or with the last cell that matters.  All control flow is wave-uniform.
+__device__ inline bool knn_level(const CellGrid& g, const double4* __restrict__ sp, const int2* __restrict__ cells,
+                                 const double (&q)[3], double box2, double r2, int shells, int k, int lane, double& rho,
+                                 KList& b) {
+    int c[3], lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = min(cell_of(q[a], g.lo[a], g.edge), g.dim[a] - 1);
+    for (int s = 0;; ++s) {
+        int smax = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double wide = rho + (fabs(q[a]) + rho) * 0x1p-50;  // the rounding of q_a -+ rho
+            lo[a] = min(cell_of(q[a] - wide, g.lo[a], g.edge), g.dim[a] - 1);
+            hi[a] = min(cell_of(q[a] + wide, g.lo[a], g.edge), g.dim[a] - 1);
+            smax = max(smax, max(c[a] - lo[a], hi[a] - c[a]));
+        }
+        if (s > smax) return true;
+        if (s > shells) return false;
+        const int x0 = max(c[0] - s, lo[0]), y0 = max(c[1] - s, lo[1]), z0 = max(c[2] - s, lo[2]);
+        const int nx = min(c[0] + s, hi[0]) - x0 + 1, ny = min(c[1] + s, hi[1]) - y0 + 1, nz = min(c[2] + s, hi[2]) - z0 + 1;
+        // lo <= c <= hi: every extent is >= 1, and at most 2 s + 1 <= 5 - s <= kLevelShells below the last level, which is at
+        // most two cells wide (run_knn checks it) - so the clipped cube has at most 125 cells and 32-bit arithmetic deals it.
+        // Every shell enumerates the whole cube and leaves out the cells that are not at Chebyshev distance s: 35 of 125 at most.
+        const int nxy = nx * ny, total = nxy * nz;
+        for (int base = 0; base < total; base += kWave) {
+            const int i = base + lane;
+            int2 be = make_int2(0, 0);
+            if (i < total) {
+                const int z = z0 + i / nxy, y = y0 + (i % nxy) / nx, x = x0 + i % nx;
+                if (max(abs(x - c[0]), max(abs(y - c[1]), abs(z - c[2]))) == s) be = cells[cell_key(x, y, z, g)];
+            }
+            for (int t = be.x; __ballot(t < be.y) != 0ull; ++t) {
+                double d2 = INFINITY;
+                int idx = 0x7fffffff;
+                bool cand = false;
+                if (t < be.y) {
+                    const double4 y = sp[t];
+                    const double dx = y.x - q[0], dy = y.y - q[1], dz = y.z - q[2];
+                    d2 = (dx * dx + dy * dy) + dz * dz;
+                    idx = (int)y.w;
+                    cand = d2 <= r2 && (b.cnt < k || key_less(d2, idx, b.kd2, b.kidx));
+                }
+                for (unsigned long long todo = __ballot(cand); todo != 0ull; todo &= todo - 1ull) {
+                    const int j = __builtin_ctzll(todo);
+                    knn_insert(b, k, lane, __shfl(d2, j), __shfl(idx, j));
+                }
+                if (b.cnt == k) {
+                    b.kd2 = __shfl(b.d2, k - 1);
+                    b.kidx = __shfl(b.idx, k - 1);
+                }
+            }
+        }
+        // what is not visited yet lies in cells at Chebyshev distance > s of the clamped cell: farther than the bound
+        const double reach = fmax((double)s - g.slack, 0.0) * g.edge / kReach;
+        const double bound = reach * reach + box2;
+        const bool full = b.cnt == k;
+        if ((full && b.kd2 < bound) || bound > r2) return true;
+        if (full) rho = fmin(rho, sqrt(b.kd2) * kReach);
+    }
+}
+
+// Wave w serves source point qorder[w] and writes its k slots by that index: the list, then (-1, +inf); out_cnt its length.
+__global__ __launch_bounds__(kBlock) void k_icp_knn(Levels lv, const double* __restrict__ src, const int* __restrict__ qorder,
+                                                    int64_t M, const double* __restrict__ state, int k, double r, double r2,
+                                                    int* __restrict__ out_idx, double* __restrict__ out_d2,
+                                                    int* __restrict__ out_cnt) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t w = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x / kWave);
+    if (w >= M) return;  // the whole wave
+    const int m = qorder[w];
+    double pose[12], q[3];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) pose[i] = state[kStPose + i];
+    moved(pose, src + (int64_t)m * 3, q);
+    double box2 = 0.0;  // squared distance of the query to the target's box
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double lo = lv.g[0].lo[a], hi = lv.g[0].hi[a];
+        const double out = q[a] < lo ? lo - q[a] : (q[a] > hi ? q[a] - hi : 0.0);
+        box2 += out * out;
+    }
+    box2 = box2 / kReach;
+    KList b = {INFINITY, -1, 0, INFINITY, 0x7fffffff};
+    double rho = r * kReach;
+    bool done = false;
+    for (int v = 0; v < lv.count; ++v)
+        if (!done)
+            done = knn_level(lv.g[v], lv.sp[v], lv.cells[v], q, box2, r2, v + 1 < lv.count ? kLevelShells : 0x7fffffff, k,
+                             lane, rho, b);
+    if (lane < k) {
+        const bool held = lane < b.cnt;
+        out_idx[(int64_t)m * k + lane] = held ? b.idx : -1;
+        out_d2[(int64_t)m * k + lane] = held ? b.d2 : INFINITY;
+    }
+    if (lane == 0) out_cnt[m] = b.cnt;
+}
+
+// c(q) = #{n : d2 <= r r}, r finite: one query per lane, on the finest level on which the cells that can hold such a point
+// span at most kCountSpan + 1 an axis (the last level otherwise).  Every point is in one cell of a level and every cell of the
+// cube is visited once; on a hashed level a bucket may hold points of other cells, which are left to their own cell.
+__global__ __launch_bounds__(kBlock) void k_icp_radius_count(Levels lv, const double* __restrict__ src,
+                                                             const int* __restrict__ qorder, int64_t M,
+                                                             const double* __restrict__ state, double r, double r2,
+                                                             int* __restrict__ out_cnt) {
+    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (l >= M) return;
+    const int m = qorder[l];
+    double pose[12], q[3];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) pose[i] = state[kStPose + i];
+    moved(pose, src + (int64_t)m * 3, q);
+    const double rho = r * kReach;
+    int count = 0;
+    bool done = false;
+    for (int v = 0; v < lv.count; ++v) {
+        if (done) continue;
+        const CellGrid& g = lv.g[v];
+        int lo[3], hi[3], span = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double wide = rho + (fabs(q[a]) + rho) * 0x1p-50;  // the rounding of q_a -+ rho
+            lo[a] = min(cell_of(q[a] - wide, g.lo[a], g.edge), g.dim[a] - 1);
+            hi[a] = min(cell_of(q[a] + wide, g.lo[a], g.edge), g.dim[a] - 1);
+            span = max(span, hi[a] - lo[a]);
+        }
+        if (span > kCountSpan && v + 1 < lv.count) continue;
+        done = true;
+        const double4* __restrict__ sp = lv.sp[v];
+        const int2* __restrict__ cells = lv.cells[v];
+        for (int z = lo[2]; z <= hi[2]; ++z)
+            for (int y = lo[1]; y <= hi[1]; ++y)
+                for (int x = lo[0]; x <= hi[0]; ++x) {
+                    const int2 be = cells[cell_key(x, y, z, g)];
+                    for (int t = be.x; t < be.y; ++t) {
+                        const double4 p = sp[t];
+                        if (!g.dense && (cell_of(p.x, g.lo[0], g.edge) != x || cell_of(p.y, g.lo[1], g.edge) != y ||
+                                         cell_of(p.z, g.lo[2], g.edge) != z))
+                            continue;
+                        const double dx = p.x - q[0], dy = p.y - q[1], dz = p.z - q[2];
+                        count += (dx * dx + dy * dy) + dz * dz <= r2 ? 1 : 0;
+                    }
+                }
+    }
+    out_cnt[m] = count;
+}
+
+// ------------------------------------------------------------------------------------------------- outlier filters (3.17)
+constexpr int kOutMean = 0, kOutDev = 1, kOutThr = 2, kOutLen = 4;  // stat: mu, s, thr
+
+// a_i = (sum of sqrt(d2) over the list, in list order from 0.0) / its length
+__global__ __launch_bounds__(kBlock) void k_knn_mean_distance(const double* __restrict__ d2, const int* __restrict__ cnt, int k,
+                                                              int64_t M, double* __restrict__ a) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M) return;
+    const int len = cnt[i];
+    double acc = 0.0;
+    for (int t = 0; t < len; ++t) acc += sqrt(d2[i * k + t]);
+    a[i] = len > 0 ? acc / (double)len : 0.0;
+}
+
+// One run of kRun consecutive i per lane, ascending from 0.0: a_i (dev 0) or (a_i - mu) (a_i - mu) (dev 1).  part: [run]
+__global__ __launch_bounds__(kBlock) void k_outlier_runs(const double* __restrict__ a, int64_t M, int dev,
+                                                         const double* __restrict__ stat, double* __restrict__ part) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t i0 = r * kRun;
+    if (i0 >= M) return;
+    const int64_t i1 = i0 + kRun < M ? i0 + kRun : M;
+    const double mu = dev ? stat[kOutMean] : 0.0;
+    double acc = 0.0;
+    for (int64_t i = i0; i < i1; ++i) {
+        const double e = a[i] - mu;
+        acc += dev ? e * e : a[i];
+    }
+    part[r] = acc;
+}
+
+// One lane: the run sums in ascending run order from 0.0, then mu = sum / M (dev 0), or s = sqrt(sum / (M - 1)), 0 when
+// M = 1, and thr = mu + (std_ratio s) (dev 1).
+__global__ void k_outlier_finish(const double* __restrict__ part, int64_t nruns, int dev, double m_total, double std_ratio,
+                                 double* __restrict__ stat) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double acc = 0.0;
+    int64_t r = 0;
+    for (; r + 16 <= nruns; r += 16) {  // sixteen loads in flight; the additions stay in ascending run order
+        double v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = part[r + u];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc += v[u];
+    }
+    for (; r < nruns; ++r) acc += part[r];
+    if (!dev) {
+        stat[kOutMean] = acc / m_total;
+        return;
+    }
+    const double s = m_total > 1.0 ? sqrt(acc / (m_total - 1.0)) : 0.0;
+    const double scaled = std_ratio * s;
+    stat[kOutDev] = s;
+    stat[kOutThr] = stat[kOutMean] + scaled;
+}
+
+// keep i iff a_i <= thr
+__global__ __launch_bounds__(kBlock) void k_outlier_mask_score(const double* __restrict__ a, int64_t M,
+                                                               const double* __restrict__ stat, unsigned char* __restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < M) keep[i] = a[i] <= stat[kOutThr] ? 1 : 0;
+}
+
+// keep i iff c_i > nb_points
+__global__ __launch_bounds__(kBlock) void k_outlier_mask_count(const int* __restrict__ c, int64_t M, int nb_points,
+                                                               unsigned char* __restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < M) keep[i] = c[i] > nb_points ? 1 : 0;
 }
 
 // ----------------------------------------------------------------------------------------------------------------- sums
@@ -553,6 +810,9 @@ struct prg_icp {
     hipStream_t stream = nullptr;
     int64_t N = 0, M = 0;
     bool have_normals = false, have_order = false, have_matches = false;
+    int have_knn = 0;                     // k of the lists in knn_*, 0: none
+    bool have_counts = false;
+    int have_outlier = 0;                 // 0 none, 1 statistical (score, stat, keep), 2 radius (counts, keep)
     bool have_cov[2] = {false, false};    // source, target
     Levels lv;
     prg::DevBuf<double4> tp, tn;          // target points and normals, padded to four doubles
@@ -567,6 +827,13 @@ struct prg_icp {
     prg::DevBuf<double> d2;               // [M]
     prg::DevBuf<double> part;             // [runs][kSlots]
     prg::DevBuf<double> state;            // [kStLen]
+    prg::DevBuf<int> knn_idx;             // [M][k]
+    prg::DevBuf<double> knn_d2;           // [M][k]
+    prg::DevBuf<int> knn_cnt;             // [M]
+    prg::DevBuf<int> counts;              // [M]: the radius count
+    prg::DevBuf<double> score;            // [M]: the mean neighbour distance
+    prg::DevBuf<double> stat;             // [kOutLen]
+    prg::DevBuf<unsigned char> keep;      // [M]
 };
 
 namespace {
@@ -577,6 +844,13 @@ int require_ready(prg_icp* h, const char* who, bool matches) {
     PRG_REQUIRE(h->M >= 1, PRG_ERR_STATE, "%s: no source (prg_icp_set_source first)", who);
     PRG_REQUIRE(!matches || h->have_matches, PRG_ERR_STATE, "%s: no matches (prg_icp_search first)", who);
     return PRG_OK;
+}
+
+// lists, counts and filter results belong to the clouds and the pose they were made with
+void drop_lists(prg_icp* h) {
+    h->have_knn = 0;
+    h->have_counts = false;
+    h->have_outlier = 0;
 }
 
 int check_kind(const char* who, prg_icp* h, int kind) {
@@ -672,6 +946,41 @@ void enqueue_step(prg_icp* h, int kind) {
     k_icp_step<<<1, 1, 0, h->stream>>>(kind, h->state.p);
 }
 
+// the k-best lists of every moved source point into knn_*; the buffers grow to M k
+int run_knn(prg_icp* h, const char* who, int k, double r) {
+    PRG_REQUIRE(k >= 1 && k <= kMaxK, PRG_ERR_INVALID, "%s: k must lie in 1 .. %d, got %d", who, kMaxK, k);
+    PRG_REQUIRE(r > 0.0, PRG_ERR_INVALID, "%s: r must be > 0 (infinity: no limit), got %g", who, r);
+    const CellGrid& last = h->lv.g[h->lv.count - 1];  // what prg_icp_set_target builds: the kernel deals at most 5^3 cells a shell
+    PRG_REQUIRE(std::max(last.dim[0], std::max(last.dim[1], last.dim[2])) <= 2, PRG_ERR_STATE,
+                "%s: the last grid level is more than two cells wide", who);
+    const int64_t M = h->M;
+    h->have_knn = 0;
+    if (h->have_outlier == 1) h->have_outlier = 0;  // its keep mask went with these lists
+    PRG_HIP(h->knn_idx.ensure(M * k, M * k));
+    PRG_HIP(h->knn_d2.ensure(M * k, M * k));
+    PRG_HIP(h->knn_cnt.ensure(M, M));
+    PRG_TRY(ensure_order(h));
+    k_icp_knn<<<(unsigned)prg::ceil_div(M, kBlock / kWave), kBlock, 0, h->stream>>>(
+        h->lv, h->src.p, h->qvals.p + M, M, h->state.p, k, r, r * r, h->knn_idx.p, h->knn_d2.p, h->knn_cnt.p);
+    PRG_HIP(hipGetLastError());
+    h->have_knn = k;
+    return PRG_OK;
+}
+
+int run_radius_count(prg_icp* h, const char* who, double r) {
+    PRG_REQUIRE(r > 0.0 && std::isfinite(r), PRG_ERR_INVALID, "%s: r must be finite and > 0, got %g", who, r);
+    const int64_t M = h->M;
+    h->have_counts = false;
+    if (h->have_outlier == 2) h->have_outlier = 0;  // its keep mask went with these counts
+    PRG_HIP(h->counts.ensure(M, M));
+    PRG_TRY(ensure_order(h));
+    k_icp_radius_count<<<(unsigned)prg::ceil_div(M, kBlock), kBlock, 0, h->stream>>>(h->lv, h->src.p, h->qvals.p + M, M,
+                                                                                     h->state.p, r, r * r, h->counts.p);
+    PRG_HIP(hipGetLastError());
+    h->have_counts = true;
+    return PRG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -709,6 +1018,7 @@ int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normal
     PRG_HIP(hipStreamSynchronize(st));
     h->N = 0;
     h->have_normals = h->have_order = h->have_matches = h->have_cov[1] = false;
+    drop_lists(h);
     std::vector<double> raw, pad;
     double lo[3], hi[3];
     PRG_TRY(prg::load_cloud3(points_hd, n, "prg_icp_set_target: the points contain NaN or infinity", raw, pad, lo, hi));
@@ -766,6 +1076,7 @@ int prg_icp_set_source(prg_icp* h, const double* points_hd, int64_t m) {
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->M = 0;
     h->have_order = h->have_matches = h->have_cov[0] = false;
+    drop_lists(h);
     std::vector<double> raw((size_t)m * 3);
     PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
     for (size_t i = 0; i < raw.size(); ++i)
@@ -861,6 +1172,7 @@ int prg_icp_set_pose(prg_icp* h, const double* pose_host) {
     PRG_HIP(hipStreamSynchronize(h->stream));
     PRG_HIP(hipMemcpy(h->state.p + kStPose, pose_host, 12 * sizeof(double), hipMemcpyHostToDevice));
     h->have_matches = false;
+    drop_lists(h);
     return PRG_OK;
 }
 
@@ -930,6 +1242,7 @@ int prg_icp_step(prg_icp* h, int kind) {
     enqueue_step(h, kind);
     PRG_HIP(hipGetLastError());
     h->have_matches = false;  // they belong to the pose before the step
+    drop_lists(h);
     return PRG_OK;
 }
 
@@ -946,6 +1259,7 @@ int prg_icp_iterate(prg_icp* h, int kind, double r, int max_iteration, double re
     PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_iterate: hipSetDevice(%d) failed", h->device);
     hipStream_t st = h->stream;
     PRG_TRY(ensure_order(h));
+    drop_lists(h);  // the loop moves the pose
     k_icp_reset<<<1, 1, 0, st>>>(1, h->state.p);
     enqueue_search(h, r);
     enqueue_eval(h, kind, 1, rel_fitness, rel_rmse);
@@ -984,6 +1298,105 @@ int prg_icp_get_state(prg_icp* h, double* pose_host, int64_t* count_host, double
     if (n_iter_host) *n_iter_host = (int)s[kStIter];
     if (converged_host) *converged_host = (int)s[kStConverged];
     if (status_host) *status_host = (int)s[kStStatus];
+    return PRG_OK;
+}
+
+int prg_icp_max_k(int* out) {
+    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_icp_max_k: NULL argument");
+    *out = kMaxK;
+    return PRG_OK;
+}
+
+int prg_icp_knn(prg_icp* h, int k, double r) {
+    PRG_TRY(require_ready(h, "prg_icp_knn", false));
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_knn: hipSetDevice(%d) failed", h->device);
+    return run_knn(h, "prg_icp_knn", k, r);
+}
+
+int prg_icp_get_knn(prg_icp* h, int* index_host, double* d2_host, int* count_host) {
+    PRG_TRY(require_ready(h, "prg_icp_get_knn", false));
+    PRG_REQUIRE(h->have_knn > 0, PRG_ERR_STATE, "prg_icp_get_knn: no lists (prg_icp_knn first)");
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_knn: hipSetDevice(%d) failed", h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    const size_t slots = (size_t)h->M * (size_t)h->have_knn;
+    if (index_host) PRG_HIP(hipMemcpy(index_host, h->knn_idx.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+    if (d2_host) PRG_HIP(hipMemcpy(d2_host, h->knn_d2.p, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (count_host) PRG_HIP(hipMemcpy(count_host, h->knn_cnt.p, (size_t)h->M * sizeof(int), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+int prg_icp_radius_count(prg_icp* h, double r) {
+    PRG_TRY(require_ready(h, "prg_icp_radius_count", false));
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_radius_count: hipSetDevice(%d) failed", h->device);
+    return run_radius_count(h, "prg_icp_radius_count", r);
+}
+
+int prg_icp_get_counts(prg_icp* h, int* count_host) {
+    PRG_TRY(require_ready(h, "prg_icp_get_counts", false));
+    PRG_REQUIRE(count_host != nullptr, PRG_ERR_INVALID, "prg_icp_get_counts: NULL argument");
+    PRG_REQUIRE(h->have_counts, PRG_ERR_STATE, "prg_icp_get_counts: no counts (prg_icp_radius_count first)");
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_counts: hipSetDevice(%d) failed", h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(count_host, h->counts.p, (size_t)h->M * sizeof(int), hipMemcpyDeviceToHost));
+    return PRG_OK;
+}
+
+int prg_icp_outlier_statistical(prg_icp* h, int k, double std_ratio) {
+    PRG_TRY(require_ready(h, "prg_icp_outlier_statistical", false));
+    PRG_REQUIRE(std_ratio >= 0.0 && std::isfinite(std_ratio), PRG_ERR_INVALID,
+                "prg_icp_outlier_statistical: std_ratio must be finite and >= 0, got %g", std_ratio);
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_outlier_statistical: hipSetDevice(%d) failed", h->device);
+    h->have_outlier = 0;
+    PRG_TRY(run_knn(h, "prg_icp_outlier_statistical", k, INFINITY));
+    const int64_t M = h->M, nruns = prg::ceil_div(M, kRun);  // part holds nruns kSlots doubles (prg_icp_set_source)
+    PRG_HIP(h->score.ensure(M, M));
+    PRG_HIP(h->keep.ensure(M, M));
+    PRG_HIP(h->stat.ensure(kOutLen, kOutLen));
+    hipStream_t st = h->stream;
+    const unsigned blocks = (unsigned)prg::ceil_div(M, kBlock), run_blocks = (unsigned)prg::ceil_div(nruns, kBlock);
+    k_knn_mean_distance<<<blocks, kBlock, 0, st>>>(h->knn_d2.p, h->knn_cnt.p, k, M, h->score.p);
+    for (int dev = 0; dev < 2; ++dev) {
+        k_outlier_runs<<<run_blocks, kBlock, 0, st>>>(h->score.p, M, dev, h->stat.p, h->part.p);
+        k_outlier_finish<<<1, 1, 0, st>>>(h->part.p, nruns, dev, (double)M, std_ratio, h->stat.p);
+    }
+    k_outlier_mask_score<<<blocks, kBlock, 0, st>>>(h->score.p, M, h->stat.p, h->keep.p);
+    PRG_HIP(hipGetLastError());
+    h->have_outlier = 1;
+    return PRG_OK;
+}
+
+int prg_icp_outlier_radius(prg_icp* h, double r, int nb_points) {
+    PRG_TRY(require_ready(h, "prg_icp_outlier_radius", false));
+    PRG_REQUIRE(nb_points >= 0, PRG_ERR_INVALID, "prg_icp_outlier_radius: nb_points must be >= 0, got %d", nb_points);
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_outlier_radius: hipSetDevice(%d) failed", h->device);
+    h->have_outlier = 0;
+    PRG_TRY(run_radius_count(h, "prg_icp_outlier_radius", r));
+    const int64_t M = h->M;
+    PRG_HIP(h->keep.ensure(M, M));
+    k_outlier_mask_count<<<(unsigned)prg::ceil_div(M, kBlock), kBlock, 0, h->stream>>>(h->counts.p, M, nb_points, h->keep.p);
+    PRG_HIP(hipGetLastError());
+    h->have_outlier = 2;
+    return PRG_OK;
+}
+
+int prg_icp_get_outlier(prg_icp* h, unsigned char* keep_host, double* score_host, double* stat_host) {
+    PRG_TRY(require_ready(h, "prg_icp_get_outlier", false));
+    PRG_REQUIRE(h->have_outlier != 0, PRG_ERR_STATE,
+                "prg_icp_get_outlier: no filter result (prg_icp_outlier_statistical or prg_icp_outlier_radius first)");
+    PRG_REQUIRE(h->have_outlier == 1 || (score_host == nullptr && stat_host == nullptr), PRG_ERR_STATE,
+                "prg_icp_get_outlier: the radius filter has no score or statistics (its counts: prg_icp_get_counts)");
+    prg::DeviceGuard g(h->device);
+    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_outlier: hipSetDevice(%d) failed", h->device);
+    PRG_HIP(hipStreamSynchronize(h->stream));
+    if (keep_host) PRG_HIP(hipMemcpy(keep_host, h->keep.p, (size_t)h->M, hipMemcpyDeviceToHost));
+    if (score_host) PRG_HIP(hipMemcpy(score_host, h->score.p, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost));
+    if (stat_host) PRG_HIP(hipMemcpy(stat_host, h->stat.p, 3 * sizeof(double), hipMemcpyDeviceToHost));
     return PRG_OK;
 }
 

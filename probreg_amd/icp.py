@@ -16,6 +16,9 @@ Open3D nor scikit-learn is imported.
 
 ``registration_gicp`` is generalized (plane-to-plane) ICP, Open3D's ``registration_generalized_icp``, on the same search, sums,
 step and loop: every point carries a covariance, given or ``I - (1 - epsilon) u u^T`` of its unit normal.
+
+``knn_search`` and ``radius_count`` are the exact k-nearest-neighbour lists (k <= 64) and the radius counts on the same grid
+(DESIGN.md section 3.17); ``preprocess.remove_statistical_outlier`` and ``remove_radius_outlier`` are built on them.
 """
 import collections
 import ctypes
@@ -40,6 +43,8 @@ IcpResult = collections.namedtuple("IcpResult", ["transformation", "fitness", "i
 IcpState = collections.namedtuple("IcpState", ["pose", "count", "sum", "n_iter", "converged", "status"])
 GicpResult = collections.namedtuple("GicpResult", ["transformation", "fitness", "inlier_rmse", "correspondences", "n_iter",
                                                    "converged", "objective"])
+KnnResult = collections.namedtuple("KnnResult", ["index", "d2", "count"])
+MAX_K = 64  # prg_icp_max_k: one list entry per lane of a wave
 
 
 def _check_r(r, name="max_correspondence_distance"):
@@ -47,6 +52,33 @@ def _check_r(r, name="max_correspondence_distance"):
     if not r > 0.0:  # also NaN
         raise ValueError("%s must be > 0 (infinity: no limit), got %r" % (name, r))
     return r
+
+
+def _number(v, name):
+    """float(v) of a real number; booleans, strings and whatever float() refuses raise ValueError (NaN passes: the range
+    tests of the callers refuse it)."""
+    if isinstance(v, (bool, np.bool_, str, bytes)):
+        raise ValueError("%s must be a number, got %r" % (name, v))
+    try:
+        return float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (name, v))
+
+
+def _check_k(k, name="k"):
+    """An integer in 1 .. MAX_K (an integral float passes)."""
+    v = _number(k, name)
+    if not (v == int(v) if np.isfinite(v) else False) or not 1 <= v <= MAX_K:
+        raise ValueError("%s must be an integer in 1 .. %d, got %r" % (name, MAX_K, k))
+    return int(v)
+
+
+def _check_radius(r, name, allow_inf):
+    v = _number(r, name)
+    if not v > 0.0 or (not allow_inf and not np.isfinite(v)):  # also NaN
+        raise ValueError("%s must be %s> 0%s, got %r" % (name, "" if allow_inf else "finite and ",
+                                                       " (infinity: no limit)" if allow_inf else "", r))
+    return v
 
 
 def _kind(estimation):
@@ -289,6 +321,47 @@ class IcpPlan(object):
         _lib.check(_lib.lib.prg_icp_get_matches(self._h, _lib.ptr(idx), _lib.ptr(d2)))
         return idx, d2
 
+    def knn(self, k, r=np.inf):
+        """``KnnResult(index (M, k) int32, d2 (M, k), count (M,) int32)``: for every moved source point the targets with
+        ``d2 <= r r`` in ascending ``(d2, index)``, cut to ``k`` (1 .. 64) entries; the slots past ``count`` hold -1 and
+        +inf.  ``k = 1`` is ``search`` + ``matches``."""
+        k, r = _check_k(k), _check_radius(r, "r", True)
+        _lib.check(_lib.lib.prg_icp_knn(self._h, k, r))
+        return self._lists(k)
+
+    def _lists(self, k):
+        idx = np.empty((self.n_source, k), dtype=np.int32)
+        d2 = np.empty((self.n_source, k))
+        cnt = np.empty(self.n_source, dtype=np.int32)
+        _lib.check(_lib.lib.prg_icp_get_knn(self._h, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(cnt)))
+        return KnnResult(idx, d2, cnt)
+
+    def radius_count(self, r):
+        """(M,) int32: for every moved source point the number of targets with ``d2 <= r r``; ``r`` finite."""
+        _lib.check(_lib.lib.prg_icp_radius_count(self._h, _check_radius(r, "r", False)))
+        return self._counts()
+
+    def _counts(self):
+        cnt = np.empty(self.n_source, dtype=np.int32)
+        _lib.check(_lib.lib.prg_icp_get_counts(self._h, _lib.ptr(cnt)))
+        return cnt
+
+    def _outlier_statistical(self, k, std_ratio):
+        """For ``preprocess.remove_statistical_outlier``, which has checked the arguments and set one cloud as source and as
+        target at the identity pose: (keep (M,) bool, a (M,), (mu, s, thr))."""
+        _lib.check(_lib.lib.prg_icp_outlier_statistical(self._h, k, std_ratio))
+        keep = np.empty(self.n_source, dtype=np.uint8)
+        score, stat = np.empty(self.n_source), np.empty(3)
+        _lib.check(_lib.lib.prg_icp_get_outlier(self._h, _lib.ptr(keep), _lib.ptr(score), _lib.ptr(stat)))
+        return keep.astype(bool), score, (float(stat[0]), float(stat[1]), float(stat[2]))
+
+    def _outlier_radius(self, nb_points, radius):
+        """For ``preprocess.remove_radius_outlier``, as ``_outlier_statistical``: (keep (M,) bool, counts (M,) int32)."""
+        _lib.check(_lib.lib.prg_icp_outlier_radius(self._h, radius, nb_points))
+        keep = np.empty(self.n_source, dtype=np.uint8)
+        _lib.check(_lib.lib.prg_icp_get_outlier(self._h, _lib.ptr(keep), None, None))
+        return keep.astype(bool), self._counts()
+
     def sums(self, estimation):
         """The raw ordered sums of a step over the current matches (32 doubles, laid out as ``prg_icp_sums`` documents).
         ``estimation``: as in ``registration_icp``, or ``GENERALIZED`` / "generalized" (here, in ``step`` and in ``iterate``)."""
@@ -470,5 +543,38 @@ def nearest_neighbour(query, cloud, max_distance=None, device=None):
         plan.set_source(q)
         plan.search(r)
         return plan.matches()
+    finally:
+        plan.close()
+
+
+def knn_search(query, cloud, k, max_distance=None, device=None):
+    """``KnnResult(index (Q, k) int32, d2 (Q, k), count (Q,) int32)``: for every row of ``query`` the ``k`` (1 .. 64) rows of
+    ``cloud`` of least squared distance ``(dx dx + dy dy) + dz dz``, ascending, ties to the smaller index; with
+    ``max_distance`` only rows within it (``d2 <= r r``) are listed.  Slots past ``count`` hold -1 and +inf.  Exact at any
+    size.  When ``query`` is ``cloud`` a point is an ordinary candidate at ``d2 = 0``: it comes
+    first unless a copy of it has a smaller index."""
+    q, c = _as_rows(query, "query", 3), _as_rows(cloud, "cloud", 3)
+    k = _check_k(k)
+    r = np.inf if max_distance is None else _check_radius(max_distance, "max_distance", True)
+    _single_process("knn_search")
+    plan = IcpPlan(device)
+    try:
+        plan.set_target(c)
+        plan.set_source(q)
+        return plan.knn(k, r)
+    finally:
+        plan.close()
+
+
+def radius_count(query, cloud, radius, device=None):
+    """(Q,) int32: for every row of ``query`` the number of rows of ``cloud`` with ``d2 <= radius radius``."""
+    q, c = _as_rows(query, "query", 3), _as_rows(cloud, "cloud", 3)
+    r = _check_radius(radius, "radius", False)
+    _single_process("radius_count")
+    plan = IcpPlan(device)
+    try:
+        plan.set_target(c)
+        plan.set_source(q)
+        return plan.radius_count(r)
     finally:
         plan.close()

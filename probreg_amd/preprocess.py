@@ -11,6 +11,11 @@ Differences from Open3D a caller can see (on purpose):
   * An axis may span at most 2^21 cells (Open3D: INT_MAX); a larger grid raises ``ValueError``.
   * Arrays go in and come out: ``VoxelDownSample(points, normals, attributes, counts, first, inverse)``.
 
+``remove_statistical_outlier`` and ``remove_radius_outlier`` are Open3D's filters of those names, which clean a cloud of the
+uniform outliers the reference's example set-up adds to every target (examples/utils.py: ``n_random``).  They run on the exact
+k-nearest-neighbour search and the radius count of ``probreg_amd.icp`` (``prg_icp_knn``, ``prg_icp_radius_count``, csrc/icp.hip;
+DESIGN.md section 3.17), in fp64 with every sum in a stated order.
+
 The result of a global registration on the down-sampled clouds starts a local one on the full clouds::
 
     from probreg_amd import cpd, global_reg
@@ -220,3 +225,105 @@ def voxel_down_sample(points, voxel_size, normals=None, attributes=None, unit_no
     if attributes is not None:
         out_attributes = np.ascontiguousarray(cm[:, cm.shape[1] - attributes.shape[1]:])
     return VoxelDownSample(means, out_normals, out_attributes, counts, first, inverse)
+
+
+# ------------------------------------------------------------------------------------------------------ outlier removal
+OutlierRemoval = collections.namedtuple("OutlierRemoval", ["points", "normals", "attributes", "index", "mask", "score",
+                                                           "threshold"])
+
+
+def _pad3(pts):
+    """(n, 3): a 2-D cloud gets z = 0, which leaves every squared distance as it is ((dx dx + dy dy) + 0 is exact)."""
+    if pts.shape[1] == 3:
+        return pts
+    return np.ascontiguousarray(np.concatenate([pts, np.zeros((pts.shape[0], 1))], axis=1))
+
+
+def _filter_inputs(points, normals, attributes):
+    pts = _as_cloud(points)
+    n, d = pts.shape
+    if normals is None and not isinstance(points, np.ndarray) and hasattr(points, "points"):
+        own = getattr(points, "normals", None)
+        if own is not None and np.ndim(own) == 2 and np.shape(own)[0] == n:
+            normals = own
+    if normals is not None:
+        normals = _as_channel(normals, "normals", n, d)
+    if attributes is not None:
+        attributes = _as_channel(attributes, "attributes", n, None)
+    return pts, normals, attributes
+
+
+def _kept(pts, normals, attributes, keep, score, threshold):
+    index = np.nonzero(keep)[0].astype(np.int32)
+    rows = [None if a is None else np.ascontiguousarray(a[index]) for a in (pts, normals, attributes)]
+    return OutlierRemoval(rows[0], rows[1], rows[2], index, keep, score, threshold)
+
+
+def remove_statistical_outlier(points, nb_neighbors=20, std_ratio=2.0, normals=None, attributes=None, device=None):
+    """Open3D's ``remove_statistical_outlier``: drop the points whose mean distance to their ``nb_neighbors`` nearest
+    neighbours is far above the cloud's average (the exact k-NN search and the sums run on the GPU).
+
+    ``a_i`` is the mean distance from point ``i`` to the ``min(nb_neighbors, n)`` nearest points of the cloud, the point
+    itself being one of them (Open3D's convention); ``mu`` and ``s`` are the mean and the sample standard deviation of the
+    ``a_i``; ``thr = mu + std_ratio s``; point ``i`` is kept iff ``a_i <= thr``.
+
+    Deviation from Open3D (as its behaviour is remembered, not verified against its source): Open3D keeps ``0 < a_i < thr``.
+    Under that rule a cloud whose ``a_i`` are all equal, or a point with ``nb_neighbors`` coincident copies, is removed
+    entirely; here such points are kept.
+
+    Args:
+        points: (n, 2) or (n, 3) array, or anything with ``.points`` (its ``.normals`` ride along when ``normals`` is None).
+        nb_neighbors: 1 .. 64.
+        std_ratio: >= 0, finite.
+        normals, attributes: (n, d) / (n, c) rows that follow the kept points.
+    Returns:
+        ``OutlierRemoval(points, normals, attributes, index (kept rows, int32), mask (n,) bool, score (n,): a_i,
+        threshold: (mu, s, thr))``.
+    """
+    from . import icp
+
+    pts, normals, attributes = _filter_inputs(points, normals, attributes)
+    k = icp._check_k(nb_neighbors, "nb_neighbors")
+    ratio = icp._number(std_ratio, "std_ratio")
+    if not (np.isfinite(ratio) and ratio >= 0.0):
+        raise ValueError("std_ratio must be a finite number >= 0, got %r" % (std_ratio,))
+    _single_process("remove_statistical_outlier")
+    cloud = _pad3(pts)
+    plan = icp.IcpPlan(device)
+    try:
+        plan.set_target(cloud)
+        plan.set_source(cloud)
+        keep, score, threshold = plan._outlier_statistical(k, ratio)
+    finally:
+        plan.close()
+    return _kept(pts, normals, attributes, keep, score, threshold)
+
+
+def remove_radius_outlier(points, nb_points, radius, normals=None, attributes=None, device=None):
+    """Open3D's ``remove_radius_outlier``: point ``i`` is kept iff more than ``nb_points`` points of the cloud, the point
+    itself included (Open3D's convention), lie within ``radius`` of it (``d2 <= radius radius``).
+
+    Args:
+        points, normals, attributes: as in ``remove_statistical_outlier``.
+        nb_points: integer >= 0.
+        radius: finite, > 0.
+    Returns:
+        ``OutlierRemoval(points, normals, attributes, index, mask, score (n,) int32: the counts, threshold: nb_points)``.
+    """
+    from . import icp
+
+    pts, normals, attributes = _filter_inputs(points, normals, attributes)
+    nb = icp._number(nb_points, "nb_points")
+    if not (np.isfinite(nb) and nb == int(nb) and 0 <= nb < 2 ** 31):
+        raise ValueError("nb_points must be an integer >= 0, got %r" % (nb_points,))
+    r = icp._check_radius(radius, "radius", False)
+    _single_process("remove_radius_outlier")
+    cloud = _pad3(pts)
+    plan = icp.IcpPlan(device)
+    try:
+        plan.set_target(cloud)
+        plan.set_source(cloud)
+        keep, counts = plan._outlier_radius(int(nb), r)
+    finally:
+        plan.close()
+    return _kept(pts, normals, attributes, keep, counts, int(nb))
