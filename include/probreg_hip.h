@@ -768,7 +768,7 @@ int prg_voxel_get_rows(prg_voxel* h, int* rows_host);
 
 /* ---- ICP: point-to-point and point-to-plane on a grid nearest-neighbour search ----------------------------------------------
  * None of this is in the reference: examples/time_measurement.py and examples/icp_test.py call Open3D's registration_icp.
- * These entry points restate it in fp64 on the device (csrc/icp.hip; the definition with the tie rule of the search, the
+ * These entry points restate it in fp64 on the device (csrc/icp.hip, the search in csrc/grid_search.hip; the definition with the tie rule of the search, the
  * order of every sum and the loop is DESIGN.md section 3.15).  Two runs on the same input give byte-identical results (no
  * floating-point atomics), whatever the launch geometry and the grid.  kind: 0 point-to-point, 1 point-to-plane, 2 generalized
  * (needs covariances, see the end of this section). */

@@ -1,5 +1,5 @@
 // The library's one cell grid (DESIGN.md section 3.9 is its definition), which the FPFH search (fpfh.hip) and the ICP search
-// (icp.hip) bin a cloud with: clamped cell coordinates, row-major keys while the box fits the table and hashed ones otherwise,
+// (grid_search.hip) bin a cloud with: clamped cell coordinates, row-major keys while the box fits the table and hashed ones otherwise,
 // points sorted stably by key, one (begin, end) per bucket.  The descriptor part (down to cell_entries) is host-compilable
 // against the HIP runtime API alone, as dev_buf.h is (tests/host/cell_grid_check.cpp); the builder is cell_grid.hip.
 #pragma once

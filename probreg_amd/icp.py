@@ -3,7 +3,8 @@ reference's examples time every method against.
 
 The reference has no counterpart; its examples call Open3D's ``registration_icp`` (``examples/time_measurement.py``,
 ``examples/icp_test.py``).  Here the nearest-neighbour search on a grid of the target, the ordered sums, the Kabsch /
-Cholesky step and Open3D's loop with its stop test all run in ``libprobreg_hip.so`` (``prg_icp_*``, csrc/icp.hip) in fp64.
+Cholesky step and Open3D's loop with its stop test all run in ``libprobreg_hip.so`` (``prg_icp_*``, csrc/icp.hip and, for the
+search, csrc/grid_search.hip) in fp64.
 DESIGN.md section 3.15 is the definition; results are byte-identical from run to run and do not depend on the grid.  Neither
 Open3D nor scikit-learn is imported.
 

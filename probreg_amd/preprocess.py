@@ -13,7 +13,7 @@ Differences from Open3D a caller can see (on purpose):
 
 ``remove_statistical_outlier`` and ``remove_radius_outlier`` are Open3D's filters of those names, which clean a cloud of the
 uniform outliers the reference's example set-up adds to every target (examples/utils.py: ``n_random``).  They run on the exact
-k-nearest-neighbour search and the radius count of ``probreg_amd.icp`` (``prg_icp_knn``, ``prg_icp_radius_count``, csrc/icp.hip;
+k-nearest-neighbour search and the radius count of ``probreg_amd.icp`` (``prg_icp_knn``, ``prg_icp_radius_count``, csrc/grid_search.hip; the filters: csrc/icp_outlier.hip;
 DESIGN.md section 3.17), in fp64 with every sum in a stated order.
 
 The result of a global registration on the down-sampled clouds starts a local one on the full clouds::

@@ -1,4 +1,4 @@
-"""The shared cell grid (csrc/cell_grid.hip) through its two users, the FPFH search and the ICP search, on the smallest
+"""The shared cell grid (csrc/cell_grid.hip) through its two users, the FPFH search (csrc/fpfh.hip) and the ICP search (csrc/grid_search.hip), on the smallest
 shapes at which the builder can go wrong: one bucket whose begin and end come from threads of two workgroups, a hashed grid
 whose buckets hold several cells, and a single point.  Compared with the restatements as test_fpfh_gpu.py and
 test_icp_gpu.py compare: FPFH indices and counts equal with d2 within 4 ulp, ICP (index, d2) byte for byte.

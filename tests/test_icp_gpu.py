@@ -1,4 +1,4 @@
-"""ICP on the GPU (probreg_amd.icp, csrc/icp.hip) against its restatement (tests/oracle_icp.py), stage
+"""ICP on the GPU (probreg_amd.icp, csrc/icp.hip, csrc/grid_search.hip) against its restatement (tests/oracle_icp.py), stage
 by stage and end to end.
 
 Matches (index and d2), the raw ordered sums, K and S are compared byte for byte: the host tests (test_oracle_icp.py) show that

@@ -1,4 +1,4 @@
-"""Exact k-NN lists and radius counts on the GPU (IcpPlan.knn / radius_count, csrc/icp.hip: k_icp_knn, k_icp_radius_count)
+"""Exact k-NN lists and radius counts on the GPU (IcpPlan.knn / radius_count, csrc/grid_search.hip: k_icp_knn, k_icp_radius_count)
 against their restatement (tests/oracle_knn.py).
 
 index (int32), d2 and count are compared byte for byte: a list is the k smallest (d2, n) of exactly rounded d2, which does not

@@ -1,4 +1,4 @@
-"""The outlier filters on the GPU (preprocess.remove_statistical_outlier / remove_radius_outlier, csrc/icp.hip) against their
+"""The outlier filters on the GPU (preprocess.remove_statistical_outlier / remove_radius_outlier, csrc/icp_outlier.hip) against their
 restatement (tests/oracle_knn.py) on the target of filterreg_pair(2000), which has 100 uniform outliers.
 
 Masks and kept indices must equal the restatement's: tests/test_oracle_knn.py shows that no decision of these cases lies

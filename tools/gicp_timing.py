@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Time generalized ICP (csrc/icp.hip) on one MI355X and write profiles/gicp_timing.txt (or --out).
+"""Time generalized ICP (csrc/icp.hip, its search in csrc/grid_search.hip) on one MI355X and write profiles/gicp_timing.txt (or --out).
 
 Clouds: synthetic.pt2pl_pair(n, seed=0) at M = N = n with the analytic normals of both clouds (the source's rounded through
 float32 as the target's are), epsilon = 1e-3, r = --radius.  Every loop starts from the identity pose, 12 and 6 degrees from the

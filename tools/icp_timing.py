@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Time ICP (csrc/icp.hip) on one MI355X and write profiles/icp_timing.txt (or --out).
+"""Time ICP (csrc/icp.hip, csrc/grid_search.hip) on one MI355X and write profiles/icp_timing.txt (or --out).
 
 Clouds: synthetic.rigid_pair(n, seed=0) at M = N = n (source and target are independent samples, the target turned by 30 and
 10 degrees), the target's analytic normals for point-to-plane.  Every loop starts from the identity pose: the clouds are not

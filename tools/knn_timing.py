@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Time the k-NN search and the outlier filters (csrc/icp.hip) on one MI355X and write
+"""Time the k-NN search and the outlier filters (csrc/grid_search.hip, csrc/icp_outlier.hip) on one MI355X and write
 profiles/knn_timing.txt (or --out).
 
 Cloud: synthetic.surface(n, 0), searched against itself (queries = cloud, identity pose).  Per size:
