@@ -26,7 +26,8 @@ extern "C" {
 typedef enum prg_status {
     PRG_OK = 0,
     PRG_ERR_INVALID = -1,   /* bad argument (ValueError / AssertionError in the reference) */
-    PRG_ERR_HIP = -2,       /* HIP runtime error; message holds hipGetErrorString */
+    PRG_ERR_HIP = -2,       /* HIP runtime error; message holds hipGetErrorString.  Also: the device of a handle (or the
+                             * `device` argument) could not be selected - every entry point checks that, nothing is launched */
     PRG_ERR_STATE = -3,     /* call order violated (e.g. estep before set_target) */
     PRG_ERR_NOMEM = -4
 } prg_status;

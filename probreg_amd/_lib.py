@@ -7,6 +7,8 @@ with the build command, and every wrapper raises on a non-zero status.
 import ctypes
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PROBREG_HIP_LIB: an alternative build of the same library (instrumented / experimental), for tools only
 LIB_PATH = os.environ.get("PROBREG_HIP_LIB") or os.path.join(_HERE, "csrc", "libprobreg_hip.so")
@@ -307,3 +309,67 @@ def ptr(a):
     if hasattr(a, "data_ptr"):
         return _vp(a.data_ptr())
     return _vp(a.ctypes.data)
+
+
+def _current_device_and_stream(device=None):
+    """(device index, hipStream_t as int) of the calling process; torch is optional plumbing."""
+    try:
+        import torch
+
+        if torch.cuda.is_available():
+            dev = torch.cuda.current_device() if device is None else int(device)
+            return dev, int(torch.cuda.current_stream(dev).cuda_stream)
+    except ImportError:  # pragma: no cover
+        pass
+    return (0 if device is None else int(device)), 0
+
+
+class Handle(object):
+    """Life cycle of one opaque handle of the library: ``create(&h, device, stream, *create_args)`` on the
+    calling process's device and stream unless told otherwise, ``close()`` any number of times, and a ``__del__`` that is
+    safe while the interpreter shuts down.  The plan classes derive from it and add what their handle computes."""
+
+    def __init__(self, create, destroy, device=None, stream=None, *create_args):
+        count = require_gpu()
+        if device is not None and not 0 <= int(device) < count:  # (before torch is asked for that device's stream)
+            raise ValueError("device %d out of range (%d devices)" % (int(device), count))
+        self.device, self.stream = _current_device_and_stream(device)
+        if stream is not None:
+            self.stream = int(stream)
+        self._destroy = destroy
+        self._h = ctypes.c_void_p()
+        check(create(ctypes.byref(self._h), self.device, ctypes.c_void_p(self.stream), *create_args))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+
+def as_points(x):
+    """ndarray or Open3D PointCloud (duck-typed ``.points``) -> float64 ndarray, unchecked (the reference's cpd.py:444);
+    None stays None."""
+    if x is None:
+        return None
+    if hasattr(x, "points") and not isinstance(x, np.ndarray):
+        x = x.points
+    return np.asarray(x, dtype=np.float64)
+
+
+def as_cloud(data, name, dims, min_points=1):
+    """C-contiguous float64 (n, d) of an array or of anything with ``.points``, d in ``dims``; ValueError, naming the
+    argument, for another shape, fewer than ``min_points`` rows, or a value that is not finite."""
+    pts = np.ascontiguousarray(as_points(data))
+    if pts.ndim != 2 or pts.shape[1] not in dims:
+        raise ValueError("%s must be %s, got shape %s" % (name, " or ".join("(n, %d)" % d for d in dims), pts.shape))
+    if pts.shape[0] < min_points:
+        raise ValueError("%s must hold at least %s" % (name, "one point" if min_points == 1 else "%d points" % min_points))
+    if not np.all(np.isfinite(pts)):
+        raise ValueError("%s contains NaN or infinity" % name)
+    return pts

@@ -33,7 +33,8 @@ import scipy.special as spsp
 from . import _lib
 from . import math_utils as mu
 from . import transformation as tf
-from .cpd import Correspondences, _as_points, _params_block
+from ._lib import as_points as _as_points
+from .cpd import Correspondences, _params_block
 from .engine import CpdPlan
 from .log import log
 

@@ -20,6 +20,7 @@ import numpy as np
 from . import _lib
 from . import dist as pdist
 from . import transformation as tf
+from ._lib import as_points as _as_points
 from .engine import CpdBatchPlan, CpdPlan
 from .log import log
 
@@ -85,13 +86,6 @@ def correspondences(t_source, target, sigma2, w=0.0, k=1, side="source", source_
         return _plan_correspondences(plan, k, side)
     finally:
         plan.close()
-
-
-def _as_points(x):
-    """ndarray or Open3D PointCloud (duck-typed ``.points``) -> float64 ndarray (cpd.py:444)."""
-    if hasattr(x, "points") and not isinstance(x, np.ndarray):
-        x = x.points
-    return np.asarray(x, dtype=np.float64)
 
 
 def _params_block(linear, t, scale, dim, delta=None):

@@ -87,9 +87,10 @@ struct CellGridScratch {
 int build_cell_grid(const CellGrid& g, unsigned bits, const double4* pts, int64_t n, CellGridScratch& scratch, double4* sp_out,
                     int2* cells_out, hipStream_t stream);
 
-// Copies n rows of three doubles in (host or device memory); PRG_ERR_INVALID with the message `who` if one is not finite.
-// raw [n][3]: the rows; pad [n][4]: a zero behind each (pad comes in empty or from an earlier call); lo, hi: the box, or NULL.
-int load_cloud3(const double* points_hd, int64_t n, const char* who, std::vector<double>& raw, std::vector<double>& pad,
-                double* lo, double* hi);
+// Copies n rows of `dim` (2 or 3) doubles in (host or device memory); PRG_ERR_INVALID with the message `not_finite` if one
+// is not finite (NULL: not checked).  raw [n][dim]: the rows; pad [n][4]: (x, y, z or 0, 0) per row (pad comes in empty or from
+// an earlier call); lo, hi: the box, or NULL.  The library's one loader of a cloud into the padded layout.
+int load_cloud3(const double* points_hd, int64_t n, int dim, const char* not_finite, std::vector<double>& raw,
+                std::vector<double>& pad, double* lo, double* hi);
 
 }  // namespace prg

@@ -66,17 +66,17 @@ int build_cell_grid(const CellGrid& g, unsigned bits, const double4* pts, int64_
     return PRG_OK;
 }
 
-int load_cloud3(const double* points_hd, int64_t n, const char* who, std::vector<double>& raw, std::vector<double>& pad,
-                double* lo, double* hi) {
-    raw.resize((size_t)n * 3);
+int load_cloud3(const double* points_hd, int64_t n, int dim, const char* not_finite, std::vector<double>& raw,
+                std::vector<double>& pad, double* lo, double* hi) {
+    raw.resize((size_t)n * dim);
     pad.resize((size_t)n * 4, 0.0);  // only columns 0 .. 2 are written below: a pad that is used again keeps its zeros
     PRG_HIP(hipMemcpy(raw.data(), points_hd, raw.size() * sizeof(double), hipMemcpyDefault));
     double b[2][3];  // the box in locals: through lo and hi, which may alias pad, every update would go through memory
-    for (int a = 0; a < 3; ++a) b[0][a] = b[1][a] = raw[a];
+    for (int a = 0; a < 3; ++a) b[0][a] = b[1][a] = a < dim ? raw[a] : 0.0;
     for (int64_t i = 0; i < n; ++i)
         for (int a = 0; a < 3; ++a) {
-            const double v = raw[(size_t)i * 3 + a];
-            PRG_REQUIRE(std::isfinite(v), PRG_ERR_INVALID, "%s", who);
+            const double v = a < dim ? raw[(size_t)i * dim + a] : 0.0;
+            PRG_REQUIRE(!not_finite || std::isfinite(v), PRG_ERR_INVALID, "%s", not_finite);
             pad[(size_t)i * 4 + a] = v;
             b[0][a] = std::min(b[0][a], v);
             b[1][a] = std::max(b[1][a], v);

@@ -116,8 +116,7 @@ int prg_comm_create(prg_comm** out, const unsigned char* id_in, int rank, int nr
     PRG_REQUIRE(out && id_in, PRG_ERR_INVALID, "prg_comm_create: NULL argument");
     PRG_REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, PRG_ERR_INVALID, "prg_comm_create: rank %d outside a world of %d", rank, nranks);
     PRG_TRY(need_rccl());
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_comm_create: cannot select device %d", device);
+    PRG_ENTER(device);
     prg::UniqueId id;
     memcpy(id.bytes, id_in, PRG_COMM_ID_BYTES);
     void* comm = nullptr;
@@ -155,22 +154,20 @@ int prg_comm_info(prg_comm* c, int* rank, int* nranks, int64_t* calls) {
 
 int prg_comm_destroy(prg_comm* c) {
     if (!c) return PRG_OK;
-    int st = PRG_OK;
-    if (c->owned && c->nccl && g_rccl.ok) {
-        prg::DeviceGuard g(c->device);
+    const auto destroy_owned = [c]() -> int {
+        PRG_ENTER_AS("prg_comm_destroy", c->device);
         const int r = g_rccl.CommDestroy(c->nccl);
-        if (r != 0) {
-            prg::set_error("ncclCommDestroy failed: %s", g_rccl.GetErrorString(r));
-            st = PRG_ERR_HIP;
-        }
-    }
-    delete c;
+        PRG_REQUIRE(r == 0, PRG_ERR_HIP, "ncclCommDestroy failed: %s", g_rccl.GetErrorString(r));
+        return PRG_OK;
+    };
+    const int st = c->owned && c->nccl && g_rccl.ok ? destroy_owned() : PRG_OK;
+    delete c;  // (whatever became of the communicator)
     return st;
 }
 
 int prg_comm_all_reduce_f64(prg_comm* c, double* buf_dev, int64_t count, void* hip_stream) {
     PRG_REQUIRE(c && buf_dev, PRG_ERR_INVALID, "prg_comm_all_reduce_f64: NULL argument");
-    prg::DeviceGuard g(c->device);
+    PRG_ENTER(c->device);
     return prg::comm_all_reduce_f64(c, buf_dev, count, reinterpret_cast<hipStream_t>(hip_stream));
 }
 

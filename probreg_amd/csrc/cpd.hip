@@ -331,41 +331,21 @@ int ensure_engine_state(prg_cpd* h) {
 extern "C" {
 
 int prg_cpd_create(prg_cpd** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_cpd_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_cpd_create: device %d out of range (%d devices)",
-                device, count);
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_cpd_create: hipSetDevice(%d) failed", device);
-    prg_cpd* h = new (std::nothrow) prg_cpd();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_cpd_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    // defaults of a new plan from the environment (CpdEnv, cpd_plan.h: these three are read per plan, not once per process)
-    if (const char* eng = getenv("PRG_DENSE_ENGINE")) h->dense_engine = std::max(0, std::min(2, atoi(eng)));
-    if (const char* eng = getenv("PRG_SPARSE_ENGINE")) h->sparse_engine = std::max(0, std::min(2, atoi(eng)));
-    if (const char* eng = getenv("PRG_RESID_SWEEP")) h->resid_sweep = atoi(eng) != 0;  // (A/B runs of the two-sweep sparse regime)
-    const hipError_t e = h->state.reset(PRG_NMOMENTS + PRG_NPARAMS);
-    if (e != hipSuccess) {
-        delete h;
-        prg::set_error("prg_cpd_create: device allocation failed: %s", hipGetErrorString(e));
-        return PRG_ERR_HIP;
-    }
-    h->moments = h->state.p;
-    h->params = h->state.p + PRG_NMOMENTS;
-    k_zero_doubles<<<1, 64, 0, h->stream>>>(h->state.p, PRG_NMOMENTS + PRG_NPARAMS);
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream, [](prg_cpd* h) -> int {
+        // defaults of a new plan from the environment (CpdEnv, cpd_plan.h: these three are read per plan, not once per process)
+        if (const char* eng = getenv("PRG_DENSE_ENGINE")) h->dense_engine = std::max(0, std::min(2, atoi(eng)));
+        if (const char* eng = getenv("PRG_SPARSE_ENGINE")) h->sparse_engine = std::max(0, std::min(2, atoi(eng)));
+        if (const char* eng = getenv("PRG_RESID_SWEEP")) h->resid_sweep = atoi(eng) != 0;  // (A/B runs of the two-sweep sparse regime)
+        PRG_HIP(h->state.reset(PRG_NMOMENTS + PRG_NPARAMS));
+        h->moments = h->state.p;
+        h->params = h->state.p + PRG_NMOMENTS;
+        k_zero_doubles<<<1, 64, 0, h->stream>>>(h->state.p, PRG_NMOMENTS + PRG_NPARAMS);
+        return PRG_OK;
+    });
 }
 
 int prg_cpd_destroy(prg_cpd* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    prg::nonrigid_free(h);
-    delete h;  // (its buffers go with it, on the plan's device)
-    return PRG_OK;
+    return prg::destroy_handle(h, [](prg_cpd* p) { prg::nonrigid_free(p); });  // (its buffers go with it, on the plan's device)
 }
 
 int prg_cpd_set_source(prg_cpd* h, const float* source_hd, int64_t m, int dim) {
@@ -374,7 +354,7 @@ int prg_cpd_set_source(prg_cpd* h, const float* source_hd, int64_t m, int dim) {
                 "prg_cpd_set_source: need m > 0 and dim in {2,3} (got m=%lld dim=%d)", (long long)m, dim);
     PRG_REQUIRE(!h->have_target || h->D == dim, PRG_ERR_INVALID,
                 "prg_cpd_set_source: dim %d does not match target dim %d", dim, h->D);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     // no source until this one is complete: a failure below leaves a plan that says so, whatever the arrays hold by then
     h->have_source = h->have_estep = h->estep_state_live = false;
@@ -408,7 +388,7 @@ int prg_cpd_set_source(prg_cpd* h, const float* source_hd, int64_t m, int dim) {
 int prg_cpd_set_source_weights(prg_cpd* h, const double* log_weights_hd, double uniform_ratio) {
     PRG_REQUIRE(h && h->have_source, PRG_ERR_STATE, "prg_cpd_set_source_weights: source not set");
     PRG_REQUIRE(uniform_ratio >= 0.0, PRG_ERR_INVALID, "prg_cpd_set_source_weights: uniform_ratio must be >= 0");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     h->uniform_ratio = uniform_ratio;
     h->estep_state_live = false;
     if (!log_weights_hd) {
@@ -440,7 +420,7 @@ int prg_cpd_set_target(prg_cpd* h, const float* target_hd, int64_t n_local, int 
                 "prg_cpd_set_target: need 0 < n_local <= n_global and dim in {2,3}");
     PRG_REQUIRE(!h->have_source || h->D == dim, PRG_ERR_INVALID,
                 "prg_cpd_set_target: dim %d does not match source dim %d", dim, h->D);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_target = h->have_estep = h->estep_state_live = false;  // (as in prg_cpd_set_source)
     // (the sums of the previous target no longer describe this one: no lean row pass until prg_cpd_init_sums has run)
@@ -594,7 +574,7 @@ int prg_cpd_set_options(prg_cpd* h, int sort_source, int sort_target, int cull) 
 
 int prg_cpd_init_sums(prg_cpd* h) {
     PRG_REQUIRE(h && h->have_target, PRG_ERR_STATE, "prg_cpd_init_sums: target not set");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_mompart(h));
     const int nblk = (int)prg::ceil_div(h->N, kBlock);
     k_zero_doubles<<<1, 64, 0, h->stream>>>(h->moments, PRG_NMOMENTS);
@@ -628,7 +608,7 @@ static bool is_rotation(const double* lin) {
 
 int prg_cpd_init_params(prg_cpd* h, const double* init_params_host) {
     PRG_REQUIRE(h && h->have_source && h->have_target, PRG_ERR_STATE, "prg_cpd_init_params: clouds not set");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_mompart(h));
     const int nblk = (int)prg::ceil_div(h->M, kBlock);
     double* srcsum = prg::mom_scratch(*h);
@@ -663,7 +643,7 @@ int prg_cpd_estep(prg_cpd* h, double w) { return prg::estep_impl(h, w, nullptr);
 
 int prg_cpd_estep_timed(prg_cpd* h, double w, float* ms_out) {
     PRG_REQUIRE(h && ms_out, PRG_ERR_INVALID, "prg_cpd_estep_timed: NULL argument");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     hipEvent_t ev[6];
     for (int i = 0; i < 6; ++i) PRG_HIP(hipEventCreate(&ev[i]));
     int st = prg::estep_impl(h, w, ev);
@@ -684,7 +664,7 @@ int prg_cpd_estep_timed(prg_cpd* h, double w, float* ms_out) {
 
 int prg_cpd_pair_counts(prg_cpd* h, double* col_pairs, double* row_pairs) {
     PRG_REQUIRE(h && h->have_estep && col_pairs && row_pairs, PRG_ERR_STATE, "prg_cpd_pair_counts: no E-step has been run");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     *col_pairs = h->dense_pairs_col;
     *row_pairs = h->dense_pairs_row;
     for (int pass = 0; pass < 2; ++pass) {  // sweeps over the work queue: one count of (128 x 32) blocks per unit
@@ -736,7 +716,7 @@ int prg_cpd_mstep(prg_cpd* h, int kind, int update_scale) {
     PRG_REQUIRE(kind == PRG_TF_RIGID || !(h->have_estep && h->last_estep_fused), PRG_ERR_STATE,
                 "prg_cpd_mstep: the last E-step ran as the single sweep of a rigid iteration (prg_cpd_set_moments_only(1)): its "
                 "moments do not hold Y^T diag(p1) Y, which the affine M-step needs");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     k_mstep<<<1, 64, 0, h->stream>>>(h->moments, h->params, kind, update_scale, h->D);
     h->estep_state_live = false;  // sigma2 in PARAMS is the next E-step's now
     PRG_HIP(hipGetLastError());
@@ -750,7 +730,7 @@ int prg_cpd_iterate(prg_cpd* h, int kind, int update_scale, double w, int n_iter
     PRG_REQUIRE(kind == PRG_TF_RIGID || kind == PRG_TF_AFFINE, PRG_ERR_INVALID,
                 "prg_cpd_iterate: kind must be PRG_TF_RIGID or PRG_TF_AFFINE");
     PRG_REQUIRE(n_iter >= 0, PRG_ERR_INVALID, "prg_cpd_iterate: n_iter must be >= 0");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     // a rigid iteration wants nothing of its E-step but the moments: the dense regime may run the fused single sweep
     const bool keep = h->moments_only;
     if (kind == PRG_TF_RIGID && h->fused_in_iterate) h->moments_only = true;
@@ -772,7 +752,7 @@ int prg_cpd_iterate(prg_cpd* h, int kind, int update_scale, double w, int n_iter
 
 int prg_cpd_get_params(prg_cpd* h, double* params_host) {
     PRG_REQUIRE(h && params_host, PRG_ERR_INVALID, "prg_cpd_get_params: NULL argument");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     // through pinned memory: a device->host copy into pageable memory pays ~100 us of staging, and the EM driver
     // reads the parameter block every iteration when it has a tolerance to test
     PRG_HIP(h->pinned.ensure(64));
@@ -793,7 +773,7 @@ int prg_cpd_get_params(prg_cpd* h, double* params_host) {
 
 int prg_cpd_set_params(prg_cpd* h, const double* params_host) {
     PRG_REQUIRE(h && params_host, PRG_ERR_INVALID, "prg_cpd_set_params: NULL argument");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     h->estep_state_live = false;
     PRG_HIP(hipMemcpyAsync(h->params, params_host, PRG_NPARAMS * sizeof(double), hipMemcpyHostToDevice, h->stream));
     PRG_HIP(hipStreamSynchronize(h->stream));
@@ -803,10 +783,10 @@ int prg_cpd_set_params(prg_cpd* h, const double* params_host) {
 
 int prg_cpd_get_moments(prg_cpd* h, double* moments_host) {
     PRG_REQUIRE(h && moments_host, PRG_ERR_INVALID, "prg_cpd_get_moments: NULL argument");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipMemcpyAsync(moments_host, h->moments, PRG_NMOMENTS * sizeof(double), hipMemcpyDeviceToHost,
-                           h->stream));
+    PRG_ENTER(h->device);
+    // (not copy_out: the moments may live in memory the caller bound, prg_cpd_bind_moments, which no DevBuf describes)
     PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_HIP(hipMemcpy(moments_host, h->moments, PRG_NMOMENTS * sizeof(double), hipMemcpyDeviceToHost));
     return PRG_OK;
 }
 
@@ -815,7 +795,7 @@ int prg_cpd_get_estep(prg_cpd* h, double* pt1_hd, double* p1_hd, double* px_hd) 
     PRG_REQUIRE(h->rowacc_valid || (!p1_hd && !px_hd), PRG_ERR_STATE,
                 "prg_cpd_get_estep: the last E-step ran as the fused single sweep of a rigid iteration (prg_cpd_iterate / "
                 "prg_cpd_set_moments_only): it leaves MOMENTS and pt1, no per-point p1 / px");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const size_t need = (size_t)(h->N > h->M * h->D ? h->N : h->M * h->D) * sizeof(double);
     PRG_TRY(prg::ensure_stage(h, need));
     if (pt1_hd) {
@@ -839,7 +819,7 @@ int prg_cpd_get_estep(prg_cpd* h, double* pt1_hd, double* p1_hd, double* px_hd) 
 
 int prg_cpd_get_tsource(prg_cpd* h, float* tsource_hd) {
     PRG_REQUIRE(h && h->have_source && tsource_hd, PRG_ERR_STATE, "prg_cpd_get_tsource: source not set");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(float)));
     k_unpack_points<<<grid1(h->M), kBlock, 0, h->stream>>>(h->z4.p, h->M, h->D, (float*)h->stage.p, h->perm_src.p);
     PRG_HIP(hipMemcpyAsync(tsource_hd, h->stage.p, h->M * h->D * sizeof(float), hipMemcpyDefault, h->stream));
@@ -850,7 +830,7 @@ int prg_cpd_get_tsource(prg_cpd* h, float* tsource_hd) {
 int prg_cpd_moments_from_estep(prg_cpd* h, const double* pt1_hd, const double* p1_hd, const double* px_hd) {
     PRG_REQUIRE(h && h->have_source && h->have_target, PRG_ERR_STATE, "prg_cpd_moments_from_estep: clouds not set");
     PRG_REQUIRE(pt1_hd && p1_hd && px_hd, PRG_ERR_INVALID, "prg_cpd_moments_from_estep: NULL array");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const size_t nb_pt1 = (size_t)h->N * sizeof(double), nb_p1 = (size_t)h->M * sizeof(double),
                  nb_px = (size_t)h->M * h->D * sizeof(double);
     PRG_TRY(prg::ensure_stage(h, nb_pt1 + nb_p1 + nb_px));

@@ -404,12 +404,6 @@ int prg_cpd_batch_create(prg_cpd_batch** out, int device, void* hip_stream, int 
     int64_t nt = 0;
     PRG_TRY(prg_cpd_batch_tile_table(nb, m.data(), n.data(), nullptr, 0, &nt));
     PRG_REQUIRE(nt < (1ll << 31) - 1, PRG_ERR_INVALID, "prg_cpd_batch_create: %lld tiles do not fit one grid", (long long)nt);
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_cpd_batch_create: device %d out of range (%d devices)", device,
-                count);
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_cpd_batch_create: hipSetDevice(%d) failed", device);
     // host side of the layout: fp32 points (what the single plan uploads), the tile table and every problem's first tile
     const int64_t mtot = source_offsets[nb], ntot = target_offsets[nb];
     std::vector<float4> s4((size_t)mtot), t4((size_t)ntot);
@@ -426,55 +420,48 @@ int prg_cpd_batch_create(prg_cpd_batch** out, int device, void* hip_stream, int 
         tiles[(size_t)i] = make_int4(t3[3 * i], t3[3 * i + 1], t3[3 * i + 2], 0);
         first[(size_t)t3[3 * i] + 1] = (int)i + 1;
     }
-    // the handle comes AFTER the host vectors: on a failure below its buffers are freed - which drains the stream and the uploads
-    // still queued from those vectors - before the vectors go
-    std::unique_ptr<prg_cpd_batch> h(new (std::nothrow) prg_cpd_batch());  // (a failure below frees what it holds by then)
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_cpd_batch_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    h->dim = dim;
-    h->B = nb;
-    h->ntiles = (int)nt;
-    h->Mtot = mtot;
-    h->Ntot = ntot;
-    auto put = [&h](auto& buf, const auto* host, size_t count) -> int {
-        PRG_HIP(buf.reset((int64_t)count));
-        PRG_HIP(hipMemcpyAsync(buf.p, host, count * sizeof(*host), hipMemcpyHostToDevice, h->stream));
+    // the handle comes AFTER the host vectors, which this function owns: on a failure of the set-up its buffers are freed - which
+    // drains the stream and the uploads still queued from those vectors - before the vectors go
+    return prg::create_handle(__func__, out, device, hip_stream, [&](prg_cpd_batch* h) -> int {
+        h->dim = dim;
+        h->B = nb;
+        h->ntiles = (int)nt;
+        h->Mtot = mtot;
+        h->Ntot = ntot;
+        auto put = [h](auto& buf, const auto* host, size_t count) -> int {
+            PRG_HIP(buf.reset((int64_t)count));
+            PRG_HIP(hipMemcpyAsync(buf.p, host, count * sizeof(*host), hipMemcpyHostToDevice, h->stream));
+            return PRG_OK;
+        };
+        auto zeroed = [h](auto& buf, size_t count) -> int {
+            PRG_HIP(buf.reset((int64_t)count));
+            PRG_HIP(hipMemsetAsync(buf.p, 0, count * sizeof(*buf.p), h->stream));
+            return PRG_OK;
+        };
+        PRG_TRY(put(h->src4, s4.data(), s4.size()));
+        PRG_TRY(put(h->tgt4, t4.data(), t4.size()));
+        PRG_TRY(put(h->soff, source_offsets, (size_t)nb + 1));
+        PRG_TRY(put(h->toff, target_offsets, (size_t)nb + 1));
+        PRG_TRY(put(h->tiles, tiles.data(), tiles.size()));
+        PRG_TRY(put(h->tile_first, first.data(), first.size()));
+        PRG_TRY(zeroed(h->params, (size_t)nb * PRG_NPARAMS));
+        PRG_TRY(zeroed(h->part, (size_t)nt * kBatchComp));
+        PRG_TRY(zeroed(h->init, (size_t)nb * 16));
+        PRG_TRY(zeroed(h->wtol, (size_t)nb * 2));
+        PRG_TRY(zeroed(h->flags, (size_t)nb * 2 + 1));
+        PRG_HIP(h->pinned.ensure((int64_t)nb * 2 + 8));
+        PRG_HIP(hipStreamSynchronize(h->stream));  // (the uploads read this call's own host vectors)
         return PRG_OK;
-    };
-    auto zeroed = [&h](auto& buf, size_t count) -> int {
-        PRG_HIP(buf.reset((int64_t)count));
-        PRG_HIP(hipMemsetAsync(buf.p, 0, count * sizeof(*buf.p), h->stream));
-        return PRG_OK;
-    };
-    PRG_TRY(put(h->src4, s4.data(), s4.size()));
-    PRG_TRY(put(h->tgt4, t4.data(), t4.size()));
-    PRG_TRY(put(h->soff, source_offsets, (size_t)nb + 1));
-    PRG_TRY(put(h->toff, target_offsets, (size_t)nb + 1));
-    PRG_TRY(put(h->tiles, tiles.data(), tiles.size()));
-    PRG_TRY(put(h->tile_first, first.data(), first.size()));
-    PRG_TRY(zeroed(h->params, (size_t)nb * PRG_NPARAMS));
-    PRG_TRY(zeroed(h->part, (size_t)nt * kBatchComp));
-    PRG_TRY(zeroed(h->init, (size_t)nb * 16));
-    PRG_TRY(zeroed(h->wtol, (size_t)nb * 2));
-    PRG_TRY(zeroed(h->flags, (size_t)nb * 2 + 1));
-    PRG_HIP(h->pinned.ensure((int64_t)nb * 2 + 8));
-    PRG_HIP(hipStreamSynchronize(h->stream));  // (the uploads read this call's own host vectors)
-    *out = h.release();
-    return PRG_OK;
+    });
 }
 
 int prg_cpd_batch_destroy(prg_cpd_batch* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_cpd_batch_init(prg_cpd_batch* h, const double* init_params_host) {
     PRG_REQUIRE(h, PRG_ERR_INVALID, "prg_cpd_batch_init: NULL handle");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     if (init_params_host)
         PRG_HIP(hipMemcpyAsync(h->init.p, init_params_host, (size_t)h->B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     k_batch_init<<<h->B, 256, 0, h->stream>>>(h->src4.p, h->tgt4.p, h->soff.p, h->toff.p, init_params_host ? h->init.p : nullptr, h->params.p,
@@ -504,7 +491,7 @@ int prg_cpd_batch_iterate(prg_cpd_batch* h, int kind, int update_scale, const do
         PRG_REQUIRE(w[b] >= 0.0 && w[b] < 1.0, PRG_ERR_INVALID, "prg_cpd_batch_iterate: w[%d] = %g is outside [0, 1)", b, w[b]);
         may_stop = may_stop || !(tol[b] < 0.0);
     }
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     // w and tol are uploaded only when they differ from what the device holds: through the plan's pinned block, whose previous
     // copy has to be over before it is overwritten (a wait at the door, once per change - never between two iterations)
     std::vector<double> now(w, w + h->B);
@@ -537,19 +524,16 @@ int prg_cpd_batch_iterate(prg_cpd_batch* h, int kind, int update_scale, const do
 int prg_cpd_batch_active(prg_cpd_batch* h, int* active) {
     PRG_REQUIRE(h && active, PRG_ERR_INVALID, "prg_cpd_batch_active: NULL argument");
     PRG_REQUIRE(h->initialised, PRG_ERR_STATE, "prg_cpd_batch_active: prg_cpd_batch_init has not run");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     return read_active(h, active);
 }
 
 int prg_cpd_batch_get_params(prg_cpd_batch* h, double* params_host, int* n_iter_host) {
     PRG_REQUIRE(h && params_host, PRG_ERR_INVALID, "prg_cpd_batch_get_params: NULL argument");
     PRG_REQUIRE(h->initialised, PRG_ERR_STATE, "prg_cpd_batch_get_params: prg_cpd_batch_init has not run");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipMemcpyAsync(params_host, h->params.p, (size_t)h->B * PRG_NPARAMS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (n_iter_host)
-        PRG_HIP(hipMemcpyAsync(n_iter_host, h->flags.p + h->B, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    return PRG_OK;
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(params_host, h->params, (int64_t)h->B * PRG_NPARAMS, h->stream));
+    return prg::copy_out(n_iter_host, h->flags, h->B, h->stream, h->B);
 }
 
 }  // extern "C"

@@ -267,7 +267,7 @@ extern "C" int prg_cpd_bcpd_solve(prg_cpd* h, double lmd, double cfac, const dou
     PRG_REQUIRE(resid_hd && vhat_hd && sigma_diag_hd, PRG_ERR_INVALID, "prg_cpd_bcpd_solve: NULL argument");
     PRG_REQUIRE(lmd > 0.0 && cfac > 0.0, PRG_ERR_INVALID, "prg_cpd_bcpd_solve: lmd and c must be > 0 (got %g, %g)", lmd,
                 cfac);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     if (h->F.p) return bcpd_solve_lowrank(h, lmd, cfac, nu_hd, resid_hd, vhat_hd, sigma_diag_hd);
     const int64_t m = h->M, mp = prg::round_up(m, NB), nblk = mp / NB;
     const prg::BcpdDenseWs o = prg::bcpd_dense_ws(m);

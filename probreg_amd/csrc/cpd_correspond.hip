@@ -227,8 +227,7 @@ int prg_topk_sweep(int device, void* hip_stream, const float* owned_hd, const fl
     PRG_REQUIRE(std::isfinite(kappa) && kappa >= 0.0, PRG_ERR_INVALID, "prg_topk_sweep: kappa must be finite and >= 0");
     PRG_REQUIRE(segments >= 0 && segments <= kMaxSegments, PRG_ERR_INVALID, "prg_topk_sweep: segments must be in [0, %d]",
                 kMaxSegments);
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_topk_sweep: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     const TopkCut cut = cut_topk(n_o, n_s, k, segments);
     prg::DevBuf<float> raw_o, raw_s, bs, ps;
@@ -272,8 +271,7 @@ int prg_cpd_correspond(prg_cpd* h, int side, int k, int* index_out, float* log2_
     const int64_t n_o = side == 0 ? h->M : h->N, n_s = side == 0 ? h->N : h->M;
     PRG_REQUIRE(k >= 1 && k <= kMaxK && k <= n_s, PRG_ERR_INVALID,
                 "prg_cpd_correspond: k must be in [1, %d] and at most the %lld streamed points (got %d)", kMaxK, (long long)n_s, k);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_cpd_correspond: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     double sigma2 = 0.0;
     PRG_HIP(hipMemcpyAsync(&sigma2, h->params + 13, sizeof(double), hipMemcpyDeviceToHost, st));

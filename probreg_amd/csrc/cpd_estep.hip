@@ -1329,7 +1329,7 @@ int two_sweep_tail(prg_cpd* h, const EstepLayout& L, const EstepEngines& d, cons
 int prg::estep_impl(prg_cpd* h, double w, hipEvent_t* ev) {
     PRG_REQUIRE(h && h->have_source && h->have_target, PRG_ERR_STATE, "prg_cpd_estep: clouds not set");
     PRG_REQUIRE(w >= 0.0 && w < 1.0, PRG_ERR_INVALID, "prg_cpd_estep: w must be in [0, 1) (got %g)", w);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER_AS("prg_cpd_estep", h->device);
     EstepLayout L;
     PRG_TRY(estep_layout(*h, &L));
     PRG_TRY(ensure_estep_buffers(h, L));

@@ -478,7 +478,7 @@ extern "C" {
 int prg_cpd_nonrigid_build_g(prg_cpd* h, double beta) {
     PRG_REQUIRE(h && h->have_source, PRG_ERR_STATE, "prg_cpd_nonrigid_build_g: source not set");
     PRG_REQUIRE(beta > 0.0, PRG_ERR_INVALID, "prg_cpd_nonrigid_build_g: beta must be > 0 (got %g)", beta);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(prg::build_kernel_matrix(h, 0, beta));
     h->beta = beta;
     h->nonrigid = true;
@@ -514,7 +514,7 @@ int prg_cpd_bcpd_set_solver(prg_cpd* h, int mode, int max_rank, double tol) {
 int prg_cpd_bcpd_build_g(prg_cpd* h, double c) {
     PRG_REQUIRE(h && h->have_source, PRG_ERR_STATE, "prg_cpd_bcpd_build_g: source not set");
     PRG_REQUIRE(c > 0.0, PRG_ERR_INVALID, "prg_cpd_bcpd_build_g: c must be > 0 (got %g)", c);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(prg::build_kernel_matrix(h, 1, c));
     h->beta = c;
     h->bcpd = true;  // the linear transform kernel adds the displacement W (= v_hat) before s R . + t
@@ -523,7 +523,7 @@ int prg_cpd_bcpd_build_g(prg_cpd* h, double c) {
 
 int prg_cpd_nonrigid_get_g(prg_cpd* h, float* g_hd) {
     PRG_REQUIRE(h && (h->G.p || h->F.p) && !h->bcpd && g_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_get_g: G has not been built");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const size_t bytes = (size_t)h->M * h->M * sizeof(float);
     if (h->G.p && !h->perm_src.p) {
         PRG_HIP(hipMemcpyAsync(g_hd, h->G.p, bytes, hipMemcpyDefault, h->stream));
@@ -546,7 +546,7 @@ int prg_cpd_nonrigid_get_g(prg_cpd* h, float* g_hd) {
 
 int prg_cpd_nonrigid_set_w(prg_cpd* h, const double* w_hd) {
     PRG_REQUIRE(h && h->W.p && w_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_set_w: G has not been built");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(double)));
     PRG_HIP(hipMemcpyAsync(h->stage.p, w_hd, (size_t)h->M * h->D * sizeof(double), hipMemcpyDefault, h->stream));
     k_pack_w<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage.p, h->M, h->D, h->W.p, 1, h->perm_src.p);
@@ -558,7 +558,7 @@ int prg_cpd_nonrigid_set_w(prg_cpd* h, const double* w_hd) {
 
 int prg_cpd_nonrigid_get_w(prg_cpd* h, double* w_hd) {
     PRG_REQUIRE(h && h->W.p && w_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_get_w: G has not been built");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(double)));
     k_pack_w<<<grid1(h->M), kBlock, 0, h->stream>>>((const double*)h->stage.p, h->M, h->D, h->W.p, 0, h->perm_src.p);
     PRG_HIP(hipGetLastError());
@@ -569,7 +569,7 @@ int prg_cpd_nonrigid_get_w(prg_cpd* h, double* w_hd) {
 
 int prg_cpd_nonrigid_set_priors(prg_cpd* h, const double* p1_tilde_hd, const double* px_tilde_hd, double alpha) {
     PRG_REQUIRE(h && (h->G.p || h->F.p), PRG_ERR_STATE, "prg_cpd_nonrigid_set_priors: G has not been built");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     if (!p1_tilde_hd || !px_tilde_hd) {  // clear
         h->nr_alpha = 0.0;
         return PRG_OK;
@@ -613,7 +613,7 @@ __global__ __launch_bounds__(kBlock) void k_apply_out(const float4* __restrict__
 
 extern "C" int prg_cpd_nonrigid_apply(prg_cpd* h, double* t_hd) {
     PRG_REQUIRE(h && (h->G.p || h->F.p) && h->W.p && t_hd, PRG_ERR_STATE, "prg_cpd_nonrigid_apply: G has not been built");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     double* gw = h->nr_work.p;
     PRG_TRY(prg::nonrigid_gw(h, h->W.p, gw));
     PRG_TRY(prg::ensure_stage(h, (size_t)h->M * h->D * sizeof(double)));

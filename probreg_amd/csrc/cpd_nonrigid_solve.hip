@@ -438,7 +438,7 @@ extern "C" int prg_cpd_mstep_nonrigid(prg_cpd* h, double lmd) {
     PRG_REQUIRE(h && (h->G.p || h->F.p) && h->W.p && h->have_estep, PRG_ERR_STATE,
                 "prg_cpd_mstep_nonrigid: needs build_g and an E-step first");
     PRG_REQUIRE(lmd > 0.0, PRG_ERR_INVALID, "prg_cpd_mstep_nonrigid: lmd must be > 0 (got %g)", lmd);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     h->estep_state_live = false;  // sigma2 in PARAMS is the next E-step's now
     if (h->F.p) return mstep_nonrigid_lowrank(h, lmd);
     const int64_t m = h->M, mp = prg::round_up(m, NB), nblk = mp / NB;

@@ -30,6 +30,7 @@ using prg::Lattice;
 // =============================================================================================
 struct prg_filterreg {
     Lattice L;
+    Lattice& ctx() { return L; }  // device and stream (plan_base.h)
     int64_t M = 0, N = 0;
     int D = 0;
     // (the device buffers own their memory, dev_buf.h: deleting the plan releases them)
@@ -571,29 +572,18 @@ extern "C" {
 // FilterReg plan
 // ---------------------------------------------------------------------------------------------
 int prg_fr_create(prg_filterreg** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_fr_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_fr_create: device %d out of range", device);
-    prg::DeviceGuard g(device);
-    std::unique_ptr<prg_filterreg> h(new (std::nothrow) prg_filterreg());  // (deleted on the way out of a failure)
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_fr_create: out of host memory");
-    h->L.device = device;
-    h->L.stream = (hipStream_t)hip_stream;
-    PRG_HIP(h->state.reset(64));
-    (void)hipMemsetAsync(h->state.p, 0, 64 * sizeof(double), h->L.stream);
-    h->L.fx_scale_static = true;  // the plan's value array (target moments) only changes in fr_alloc
-    *out = h.release();
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream, [](prg_filterreg* h) -> int {
+        PRG_HIP(h->state.reset(64));
+        (void)hipMemsetAsync(h->state.p, 0, 64 * sizeof(double), h->L.stream);
+        h->L.fx_scale_static = true;  // the plan's value array (target moments) only changes in fr_alloc
+        return PRG_OK;
+    });
 }
 
 int prg_fr_destroy(prg_filterreg* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->L.device);
-    (void)hipStreamSynchronize(h->L.stream);
-    if (h->kin) h->kin_free(h->kin);
-    delete h;  // (the lattice's and the plan's buffers release themselves)
-    return PRG_OK;
+    return prg::destroy_handle(h, [](prg_filterreg* p) {  // (the lattice's and the plan's buffers release themselves)
+        if (p->kin) p->kin_free(p->kin);
+    });
 }
 
 // the buffers that depend on both clouds
@@ -626,7 +616,7 @@ int prg_fr_set_source(prg_filterreg* h, const double* source_hd, int64_t m, int 
     PRG_REQUIRE(h && source_hd, PRG_ERR_INVALID, "prg_fr_set_source: NULL argument");
     PRG_REQUIRE(m > 0 && (dim == 2 || dim == 3), PRG_ERR_INVALID, "prg_fr_set_source: need m > 0, dim in {2,3}");
     PRG_REQUIRE(!h->have_tgt || h->D == dim, PRG_ERR_INVALID, "prg_fr_set_source: dim mismatch with target");
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     PRG_HIP(hipStreamSynchronize(h->L.stream));
     if (h->kin) {  // skinning weights belong to the previous source
         h->kin_free(h->kin);
@@ -665,7 +655,7 @@ int prg_fr_set_target(prg_filterreg* h, const double* target_hd, int64_t n, int 
     PRG_REQUIRE(h && target_hd, PRG_ERR_INVALID, "prg_fr_set_target: NULL argument");
     PRG_REQUIRE(n > 0 && (dim == 2 || dim == 3), PRG_ERR_INVALID, "prg_fr_set_target: need n > 0, dim in {2,3}");
     PRG_REQUIRE(!h->have_src || h->D == dim, PRG_ERR_INVALID, "prg_fr_set_target: dim mismatch with source");
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     PRG_HIP(hipStreamSynchronize(h->L.stream));
     h->have_tgt = false;  // until the new cloud is on the device
     PRG_HIP(h->tgt.reset(n * 4));  // (x, y, z, 0) per point
@@ -694,7 +684,7 @@ int prg_fr_set_target(prg_filterreg* h, const double* target_hd, int64_t n, int 
 int prg_fr_set_state(prg_filterreg* h, const double* rot9, const double* t3, double sigma2) {
     PRG_REQUIRE(h && rot9 && t3, PRG_ERR_INVALID, "prg_fr_set_state: NULL argument");
     PRG_REQUIRE(sigma2 > 0.0, PRG_ERR_INVALID, "prg_fr_set_state: sigma2 must be > 0 (got %g)", sigma2);
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     double buf[20];
     for (int i = 0; i < 9; ++i) buf[i] = rot9[i];
     for (int i = 0; i < 3; ++i) buf[9 + i] = t3[i];
@@ -709,7 +699,7 @@ int prg_fr_set_state(prg_filterreg* h, const double* rot9, const double* t3, dou
 
 int prg_fr_estep(prg_filterreg* h, double alpha, int* lattice_size, int* with_blur) {
     PRG_REQUIRE(h && h->have_src && h->have_tgt, PRG_ERR_STATE, "prg_fr_estep: clouds not set");
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     const int64_t tot = h->M + h->N;
     // features are produced inside the embedding kernels (transform, division by sigma, float32 cast)
     h->have_estep = false;  // (a failure below leaves no half-built lattice behind for an M-step)
@@ -800,7 +790,7 @@ static int fr_fetch_columns(prg_filterreg* h, int col0, int ncols, float* out_hd
 
 int prg_fr_get_estep(prg_filterreg* h, float* m0_hd, float* m1_hd, float* m2_hd) {
     PRG_REQUIRE(h && h->have_estep, PRG_ERR_STATE, "prg_fr_get_estep: no E-step has been run");
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     if (m0_hd) PRG_TRY(fr_fetch_columns(h, 0, 1, m0_hd));
     if (m1_hd) PRG_TRY(fr_fetch_columns(h, 1, h->D, m1_hd));
     if (m2_hd) PRG_TRY(fr_fetch_columns(h, 4, 1, m2_hd));
@@ -808,7 +798,6 @@ int prg_fr_get_estep(prg_filterreg* h, float* m0_hd, float* m1_hd, float* m2_hd)
 }
 
 static int fr_read_state(prg_filterreg* h, double* out_host, int count) {
-    prg::DeviceGuard g(h->L.device);
     hipStream_t st = h->L.stream;
     PRG_HIP(h->L.pinned.ensure(64, hipHostMallocDefault));
     PRG_HIP(hipMemcpyAsync(h->L.pinned.p, h->state.p, count * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -819,13 +808,14 @@ static int fr_read_state(prg_filterreg* h, double* out_host, int count) {
 
 int prg_fr_get_state(prg_filterreg* h, double* out_host) {
     PRG_REQUIRE(h && out_host, PRG_ERR_INVALID, "prg_fr_get_state: NULL argument");
+    PRG_ENTER(h->L.device);
     return fr_read_state(h, out_host, 20);
 }
 
 int prg_fr_mstep(prg_filterreg* h, double w, int update_sigma2, double min_sigma2, double* out_host) {
     PRG_REQUIRE(h && h->have_estep, PRG_ERR_STATE, "prg_fr_mstep: run prg_fr_estep first");
     PRG_REQUIRE(w >= 0.0 && w < 1.0, PRG_ERR_INVALID, "prg_fr_mstep: w must be in [0, 1) (got %g)", w);
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     hipStream_t st = h->L.stream;
     const double wfac = w / (1.0 - w) * (double)h->N / (double)h->M;
     const int nblk = (int)h->part_blocks;
@@ -845,7 +835,7 @@ int prg_fr_mstep(prg_filterreg* h, double w, int update_sigma2, double min_sigma
 int prg_fr_set_target_normals(prg_filterreg* h, const double* normals_hd) {
     PRG_REQUIRE(h && h->have_tgt, PRG_ERR_STATE, "prg_fr_set_target_normals: target not set");
     PRG_REQUIRE(h->D == 3 || !normals_hd, PRG_ERR_INVALID, "prg_fr_set_target_normals: point-to-plane needs 3-D clouds");
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     PRG_HIP(hipStreamSynchronize(h->L.stream));
     h->have_estep = false;
     h->nrm.release();
@@ -866,7 +856,7 @@ int prg_fr_set_target_normals(prg_filterreg* h, const double* normals_hd) {
 int prg_fr_get_nx(prg_filterreg* h, float* nx_hd) {
     PRG_REQUIRE(h && h->have_estep && h->ch == 8 && nx_hd, PRG_ERR_STATE,
                 "prg_fr_get_nx: needs target normals and an E-step");
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     return fr_fetch_columns(h, 5, 3, nx_hd);
 }
 
@@ -874,7 +864,7 @@ int prg_fr_mstep_pt2pl(prg_filterreg* h, double w, int update_sigma2, double min
     PRG_REQUIRE(h && h->have_estep, PRG_ERR_STATE, "prg_fr_mstep_pt2pl: run prg_fr_estep first");
     PRG_REQUIRE(h->ch == 8, PRG_ERR_STATE, "prg_fr_mstep_pt2pl: target normals have not been set");
     PRG_REQUIRE(w >= 0.0 && w < 1.0, PRG_ERR_INVALID, "prg_fr_mstep_pt2pl: w must be in [0, 1) (got %g)", w);
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     hipStream_t st = h->L.stream;
     const double wfac = w / (1.0 - w) * (double)h->N / (double)h->M;
     const int nblk = (int)h->part_blocks;
@@ -898,8 +888,7 @@ int prg_fr_mstep_from_arrays(int device, void* hip_stream, const double* t_sourc
     PRG_REQUIRE(!nx_hd || dim == 3, PRG_ERR_INVALID, "prg_fr_mstep_from_arrays: point-to-plane needs 3-D clouds");
     PRG_REQUIRE(w >= 0.0 && w < 1.0, PRG_ERR_INVALID, "prg_fr_mstep_from_arrays: w must be in [0, 1) (got %g)", w);
     PRG_REQUIRE(sigma2 > 0.0, PRG_ERR_INVALID, "prg_fr_mstep_from_arrays: sigma2 must be > 0 (got %g)", sigma2);
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_fr_mstep_from_arrays: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     const int ch = nx_hd ? 8 : 5;
     const int nblk = (int)std::min<int64_t>(prg::ceil_div(m, kBlock), 512), npack = (int)prg::ceil_div(m, kBlock);
@@ -952,8 +941,7 @@ int prg_kabsch_weighted(int device, void* hip_stream, const float* model_hd, con
     PRG_REQUIRE(model_hd && target_hd && weight_hd && rot_host && t_host, PRG_ERR_INVALID,
                 "prg_kabsch_weighted: NULL argument");
     PRG_REQUIRE(n > 0 && (dim == 2 || dim == 3), PRG_ERR_INVALID, "prg_kabsch_weighted: need n > 0, dim in {2,3}");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_kabsch_weighted: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     const int nblk = (int)prg::ceil_div(n, kBlock);
     DevBuf<float> bm, bt, bw;

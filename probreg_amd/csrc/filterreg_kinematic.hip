@@ -337,8 +337,7 @@ int prg_dq_skin(int device, void* hip_stream, const double* points_hd, int64_t m
                 const float* weights_hd, const double* dualquats_hd, int k_nodes, double* out_hd) {
     PRG_REQUIRE(points_hd && pairs_hd && weights_hd && dualquats_hd && out_hd, PRG_ERR_INVALID, "prg_dq_skin: NULL argument");
     PRG_REQUIRE(m > 0 && m < (1ll << 31) && k_nodes > 0, PRG_ERR_INVALID, "prg_dq_skin: need 0 < m < 2^31 and k_nodes > 0");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_dq_skin: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     std::vector<int> pairs((size_t)m * 2);
     PRG_HIP(hipMemcpy(pairs.data(), pairs_hd, pairs.size() * sizeof(int), hipMemcpyDefault));
@@ -371,7 +370,7 @@ int prg_fr_set_skinning(prg_filterreg* h, const int* pairs_hd, const float* weig
     PRG_REQUIRE(v.D == 3, PRG_ERR_INVALID, "prg_fr_set_skinning: the kinematic model needs 3-D clouds");
     PRG_REQUIRE(m == v.M, PRG_ERR_INVALID, "prg_fr_set_skinning: %lld weights for %lld source points", (long long)m, (long long)v.M);
     PRG_REQUIRE(k_nodes > 0 && k_nodes <= 32768, PRG_ERR_INVALID, "prg_fr_set_skinning: need 0 < k_nodes <= 32768");
-    prg::DeviceGuard g(v.device);
+    PRG_ENTER(v.device);
     std::vector<int> pairs((size_t)m * 2);
     std::vector<float> wts((size_t)m * 2);
     PRG_HIP(hipMemcpy(pairs.data(), pairs_hd, pairs.size() * sizeof(int), hipMemcpyDefault));
@@ -399,7 +398,7 @@ int prg_fr_set_dualquats(prg_filterreg* h, const double* dualquats_host, int k_n
     Kin* k = kin_of(v);
     PRG_REQUIRE(k, PRG_ERR_STATE, "prg_fr_set_dualquats: set the skinning weights first");
     PRG_REQUIRE(k_nodes == k->K, PRG_ERR_INVALID, "prg_fr_set_dualquats: %d dual quaternions for %d nodes", k_nodes, k->K);
-    prg::DeviceGuard g(v.device);
+    PRG_ENTER(v.device);
     k->dq_host.assign(dualquats_host, dualquats_host + (size_t)k_nodes * 8);
     PRG_HIP(hipMemcpyAsync(k->dq.p, k->dq_host.data(), k->dq_host.size() * sizeof(double), hipMemcpyHostToDevice, v.stream));
     PRG_HIP(hipStreamSynchronize(v.stream));
@@ -413,10 +412,8 @@ int prg_fr_get_dualquats(prg_filterreg* h, double* dualquats_host, int k_nodes) 
     Kin* k = kin_of(v);
     PRG_REQUIRE(k, PRG_ERR_STATE, "prg_fr_get_dualquats: set the skinning weights first");
     PRG_REQUIRE(k_nodes == k->K, PRG_ERR_INVALID, "prg_fr_get_dualquats: %d dual quaternions for %d nodes", k_nodes, k->K);
-    prg::DeviceGuard g(v.device);
-    PRG_HIP(hipMemcpyAsync(dualquats_host, k->dq.p, (size_t)k_nodes * 8 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    PRG_HIP(hipStreamSynchronize(v.stream));
-    return PRG_OK;
+    PRG_ENTER(v.device);
+    return prg::copy_out(dualquats_host, k->dq, (int64_t)k_nodes * 8, v.stream);
 }
 
 int prg_fr_kinematic_estep(prg_filterreg* h, double sigma2, double alpha, int* lattice_size, int* with_blur) {
@@ -426,7 +423,7 @@ int prg_fr_kinematic_estep(prg_filterreg* h, double sigma2, double alpha, int* l
     PRG_TRY(prg::fr_view(h, &v, false));
     Kin* k = kin_of(v);
     PRG_REQUIRE(k && v.have_src && v.have_tgt, PRG_ERR_STATE, "prg_fr_kinematic_estep: clouds or skinning weights not set");
-    prg::DeviceGuard g(v.device);
+    PRG_ENTER(v.device);
     k_kin_skin<<<(unsigned)prg::ceil_div(k->M, kBlock), kBlock, 0, v.stream>>>(v.src, k->ord_plan.p, k->kp.p, k->kw.p, k->dq.p, k->M, k->moved.p);
     PRG_HIP(hipGetLastError());
     // the embedding applies the plan's rigid state to what it is given: the identity here, the skinned cloud passes unchanged
@@ -446,7 +443,7 @@ int prg_fr_kinematic_set_arrays(prg_filterreg* h, const double* t_source_hd, con
     PRG_TRY(prg::fr_view(h, &v, false));
     Kin* k = kin_of(v);
     PRG_REQUIRE(k, PRG_ERR_STATE, "prg_fr_kinematic_set_arrays: set the skinning weights first");
-    prg::DeviceGuard g(v.device);
+    PRG_ENTER(v.device);
     const size_t m = (size_t)k->M;
     // staging: t_source [m][3] f64 | m0 [m] | m1 [m][3] | m2 [m]
     const size_t o_m0 = m * 3 * sizeof(double), o_m1 = o_m0 + m * sizeof(float), o_m2 = o_m1 + m * 3 * sizeof(float),
@@ -477,7 +474,7 @@ int prg_fr_kinematic_normal_sums(prg_filterreg* h, double sigma2, double w, int 
     PRG_REQUIRE(k, PRG_ERR_STATE, "prg_fr_kinematic_normal_sums: set the skinning weights first");
     PRG_REQUIRE(k->use_arrays || v.have_estep, PRG_ERR_STATE, "prg_fr_kinematic_normal_sums: no E-step values");
     PRG_REQUIRE(n_segments == k->S, PRG_ERR_INVALID, "prg_fr_kinematic_normal_sums: %d segments expected, the plan has %d", n_segments, k->S);
-    prg::DeviceGuard g(v.device);
+    PRG_ENTER(v.device);
     EstepIn in = k->arr_in;
     const int* ord = k->ord_caller.p;
     int64_t n_target = k->arr_n_target;
@@ -501,7 +498,7 @@ int prg_fr_kinematic_grad_sums(prg_filterreg* h, const double* twists_host, int 
     Kin* k = kin_of(v);
     PRG_REQUIRE(k && k->have_normal, PRG_ERR_STATE, "prg_fr_kinematic_grad_sums: run prg_fr_kinematic_normal_sums first");
     PRG_REQUIRE(n_segments == k->S, PRG_ERR_INVALID, "prg_fr_kinematic_grad_sums: %d segments expected, the plan has %d", n_segments, k->S);
-    prg::DeviceGuard g(v.device);
+    PRG_ENTER(v.device);
     PRG_HIP(hipMemcpyAsync(k->tw.p, twists_host, (size_t)k->K * 6 * sizeof(double), hipMemcpyHostToDevice, v.stream));
     k_dq_from_twist<<<(unsigned)prg::ceil_div(k->K, 64), 64, 0, v.stream>>>(k->tw.p, k->K, k->dq_inc.p);
     k_kin_grad<<<k->n_chunks, kBlock, 0, v.stream>>>(k->chunks.p, k->pt.p, k->mu.p, k->kp.p, k->kw.p, k->dq_inc.p, reference_form, k->part.p);

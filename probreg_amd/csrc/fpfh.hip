@@ -464,24 +464,11 @@ int run_search(prg_fpfh* h, NeighbourLists& out, double radius, int k) {
 extern "C" {
 
 int prg_fpfh_create(prg_fpfh** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_fpfh_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_fpfh_create: device %d out of range", device);
-    prg_fpfh* h = new (std::nothrow) prg_fpfh();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_fpfh_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_fpfh_destroy(prg_fpfh* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_fpfh_max_nn(int* max_nn_host) {
@@ -493,10 +480,10 @@ int prg_fpfh_max_nn(int* max_nn_host) {
 int prg_fpfh_set_data(prg_fpfh* h, const double* points_hd, int64_t n) {
     PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_fpfh_set_data: NULL argument");
     PRG_REQUIRE(n >= 1 && n <= (int64_t)1 << 30, PRG_ERR_INVALID, "prg_fpfh_set_data: need 1 <= n <= 2^30 points");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     std::vector<double> raw, pad;
     double lo[3], hi[3];
-    PRG_TRY(prg::load_cloud3(points_hd, n, "prg_fpfh_set_data: data contains NaN or infinity", raw, pad, lo, hi));
+    PRG_TRY(prg::load_cloud3(points_hd, n, 3, "prg_fpfh_set_data: data contains NaN or infinity", raw, pad, lo, hi));
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->n = 0;
     h->have_normals = h->have_spfh = h->have_fpfh = false;
@@ -525,7 +512,7 @@ int prg_fpfh_search(prg_fpfh* h, int which, double radius, int max_nn) {
     PRG_REQUIRE(max_nn >= 1 && max_nn <= kMaxNN, PRG_ERR_INVALID, "prg_fpfh_search: max_nn must lie in 1 .. %d, got %d",
                 kMaxNN, max_nn);
     PRG_REQUIRE(h->pts.p != nullptr, PRG_ERR_STATE, "prg_fpfh_search: no data (prg_fpfh_set_data first)");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     NeighbourLists& l = h->nb[which];
     PRG_HIP(hipStreamSynchronize(h->stream));
     l.k = 0;
@@ -548,19 +535,17 @@ int prg_fpfh_get_neighbours(prg_fpfh* h, int which, int* idx_host, double* d2_ho
     PRG_REQUIRE(which == 0 || which == 1, PRG_ERR_INVALID, "prg_fpfh_get_neighbours: which must be 0 or 1");
     const NeighbourLists& l = h->nb[which];
     PRG_REQUIRE(l.valid, PRG_ERR_STATE, "prg_fpfh_get_neighbours: prg_fpfh_search first");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    const size_t slots = (size_t)h->n * (size_t)l.k;
-    if (idx_host) PRG_HIP(hipMemcpy(idx_host, l.idx.p, slots * sizeof(int), hipMemcpyDeviceToHost));
-    if (d2_host) PRG_HIP(hipMemcpy(d2_host, l.d2.p, slots * sizeof(double), hipMemcpyDeviceToHost));
-    if (count_host) PRG_HIP(hipMemcpy(count_host, l.cnt.p, (size_t)h->n * sizeof(int), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(idx_host, l.idx, h->n * l.k, h->stream));
+    PRG_TRY(prg::copy_out(d2_host, l.d2, h->n * l.k, h->stream));
+    PRG_TRY(prg::copy_out(count_host, l.cnt, h->n, h->stream));
     return PRG_OK;
 }
 
 int prg_fpfh_normals(prg_fpfh* h) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_normals: NULL argument");
     PRG_REQUIRE(h->nb[0].valid, PRG_ERR_STATE, "prg_fpfh_normals: prg_fpfh_search(0, ...) first");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     k_normals<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts.p, h->nb[0].idx.p, h->nb[0].cnt.p, h->nb[0].k, h->normals.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
@@ -572,9 +557,8 @@ int prg_fpfh_normals(prg_fpfh* h) {
 int prg_fpfh_set_normals(prg_fpfh* h, const double* normals_hd) {
     PRG_REQUIRE(h && normals_hd, PRG_ERR_INVALID, "prg_fpfh_set_normals: NULL argument");
     PRG_REQUIRE(h->pts.p != nullptr, PRG_ERR_STATE, "prg_fpfh_set_normals: no data (prg_fpfh_set_data first)");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(h->normals.p, normals_hd, (size_t)h->n * 3 * sizeof(double), hipMemcpyDefault));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_in(h->normals, normals_hd, h->n * 3, h->stream));
     h->have_normals = true;
     h->have_spfh = h->have_fpfh = false;
     return PRG_OK;
@@ -583,9 +567,8 @@ int prg_fpfh_set_normals(prg_fpfh* h, const double* normals_hd) {
 int prg_fpfh_get_normals(prg_fpfh* h, double* normals_host) {
     PRG_REQUIRE(h && normals_host, PRG_ERR_INVALID, "prg_fpfh_get_normals: NULL argument");
     PRG_REQUIRE(h->have_normals, PRG_ERR_STATE, "prg_fpfh_get_normals: prg_fpfh_normals or prg_fpfh_set_normals first");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(normals_host, h->normals.p, (size_t)h->n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(normals_host, h->normals, h->n * 3, h->stream));
     return PRG_OK;
 }
 
@@ -593,7 +576,7 @@ int prg_fpfh_spfh(prg_fpfh* h) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_spfh: NULL argument");
     PRG_REQUIRE(h->nb[1].valid, PRG_ERR_STATE, "prg_fpfh_spfh: prg_fpfh_search(1, ...) first");
     PRG_REQUIRE(h->have_normals, PRG_ERR_STATE, "prg_fpfh_spfh: prg_fpfh_normals or prg_fpfh_set_normals first");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     k_spfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->pts.p, h->normals.p, h->nb[1].idx.p, h->nb[1].cnt.p, h->nb[1].k, h->spfh.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
@@ -605,16 +588,15 @@ int prg_fpfh_spfh(prg_fpfh* h) {
 int prg_fpfh_get_spfh(prg_fpfh* h, double* spfh_host) {
     PRG_REQUIRE(h && spfh_host, PRG_ERR_INVALID, "prg_fpfh_get_spfh: NULL argument");
     PRG_REQUIRE(h->have_spfh, PRG_ERR_STATE, "prg_fpfh_get_spfh: prg_fpfh_spfh first");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(spfh_host, h->spfh.p, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(spfh_host, h->spfh, h->n * kBins, h->stream));
     return PRG_OK;
 }
 
 int prg_fpfh_fpfh(prg_fpfh* h) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_fpfh_fpfh: NULL argument");
     PRG_REQUIRE(h->have_spfh && h->nb[1].valid, PRG_ERR_STATE, "prg_fpfh_fpfh: prg_fpfh_spfh first");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     k_fpfh<<<(unsigned)h->n, kWave, 0, h->stream>>>(h->spfh.p, h->nb[1].idx.p, h->nb[1].d2.p, h->nb[1].cnt.p, h->nb[1].k, h->fpfh.p);
     PRG_HIP(hipGetLastError());
     PRG_HIP(hipStreamSynchronize(h->stream));
@@ -625,9 +607,8 @@ int prg_fpfh_fpfh(prg_fpfh* h) {
 int prg_fpfh_get_fpfh(prg_fpfh* h, double* fpfh_host) {
     PRG_REQUIRE(h && fpfh_host, PRG_ERR_INVALID, "prg_fpfh_get_fpfh: NULL argument");
     PRG_REQUIRE(h->have_fpfh, PRG_ERR_STATE, "prg_fpfh_get_fpfh: prg_fpfh_fpfh first");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(fpfh_host, h->fpfh.p, (size_t)h->n * kBins * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(fpfh_host, h->fpfh, h->n * kBins, h->stream));
     return PRG_OK;
 }
 

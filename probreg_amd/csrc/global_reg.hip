@@ -163,8 +163,7 @@ int match_impl(const char* who, int device, void* hip_stream, const double* a_hd
                 "%s: need 1 <= na, nb < 2^31", who);
     PRG_REQUIRE(segments >= 0 && segments <= kMaxSegments, PRG_ERR_INVALID, "%s: segments must lie in 0 .. %d", who,
                 kMaxSegments);
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "%s: hipSetDevice(%d) failed", who, device);
+    PRG_ENTER_AS(who, device);
     hipStream_t st = (hipStream_t)hip_stream;
     const int D = template_dim(d);
     prg::DevBuf<double> raw, a_pad, b_pad, part_d2, d2_ab, d2_ba;
@@ -535,32 +534,18 @@ int prg_feature_match_mutual(int device, void* hip_stream, const double* a_hd, i
 }
 
 int prg_ransac_create(prg_ransac** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_ransac_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_ransac_create: device %d out of range", device);
-    prg_ransac* h = new (std::nothrow) prg_ransac();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_ransac_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_ransac_destroy(prg_ransac* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_ransac_set_correspondences(prg_ransac* h, const double* p_hd, const double* q_hd, int64_t C) {
     PRG_REQUIRE(h && p_hd && q_hd, PRG_ERR_INVALID, "prg_ransac_set_correspondences: NULL argument");
     PRG_REQUIRE(C >= 3 && C < (int64_t)1 << 31, PRG_ERR_INVALID,
                 "prg_ransac_set_correspondences: need 3 <= C < 2^31 correspondences, got %lld", (long long)C);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_ransac_set_correspondences: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     PRG_HIP(hipStreamSynchronize(st));
     h->C = 0;
@@ -604,8 +589,7 @@ int prg_ransac_build(prg_ransac* h, uint64_t seed, uint64_t h_offset, int64_t H,
     PRG_REQUIRE(edge_similarity >= 0.0 && edge_similarity <= 1.0, PRG_ERR_INVALID,
                 "prg_ransac_build: edge_similarity must lie in [0, 1], got %g", edge_similarity);
     PRG_REQUIRE(h->C >= 3, PRG_ERR_STATE, "prg_ransac_build: no correspondences (prg_ransac_set_correspondences first)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_ransac_build: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_hypotheses(h, H));
     k_hyp_build<<<(unsigned)prg::ceil_div(H, kBlock), kBlock, 0, h->stream>>>(h->pq.p, (uint32_t)h->C, seed, h_offset, H,
                                                                              edge_similarity, h->tri.p, h->pose.p, h->valid.p);
@@ -620,11 +604,10 @@ int prg_ransac_get_hypotheses(prg_ransac* h, int* triples_host, double* pose_hos
     PRG_REQUIRE(h->H >= 1, PRG_ERR_STATE, "prg_ransac_get_hypotheses: prg_ransac_build or prg_ransac_set_hypotheses first");
     PRG_REQUIRE(!triples_host || h->have_triples, PRG_ERR_STATE,
                 "prg_ransac_get_hypotheses: hypotheses installed by prg_ransac_set_hypotheses carry no triples");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    if (triples_host) PRG_HIP(hipMemcpy(triples_host, h->tri.p, (size_t)h->H * 3 * sizeof(int), hipMemcpyDeviceToHost));
-    if (pose_host) PRG_HIP(hipMemcpy(pose_host, h->pose.p, (size_t)h->H * 12 * sizeof(double), hipMemcpyDeviceToHost));
-    if (valid_host) PRG_HIP(hipMemcpy(valid_host, h->valid.p, (size_t)h->H * sizeof(int), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(triples_host, h->tri, h->H * 3, h->stream));
+    PRG_TRY(prg::copy_out(pose_host, h->pose, h->H * 12, h->stream));
+    PRG_TRY(prg::copy_out(valid_host, h->valid, h->H, h->stream));
     return PRG_OK;
 }
 
@@ -632,11 +615,10 @@ int prg_ransac_set_hypotheses(prg_ransac* h, const double* pose_host, const int*
     PRG_REQUIRE(h && pose_host && valid_host, PRG_ERR_INVALID, "prg_ransac_set_hypotheses: NULL argument");
     PRG_REQUIRE(H >= 1 && H <= kMaxHyp, PRG_ERR_INVALID, "prg_ransac_set_hypotheses: need 1 <= H <= %lld hypotheses, got %lld",
                 (long long)kMaxHyp, (long long)H);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_ransac_set_hypotheses: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_hypotheses(h, H));
-    PRG_HIP(hipMemcpy(h->pose.p, pose_host, (size_t)H * 12 * sizeof(double), hipMemcpyHostToDevice));
-    PRG_HIP(hipMemcpy(h->valid.p, valid_host, (size_t)H * sizeof(int), hipMemcpyHostToDevice));
+    PRG_TRY(prg::copy_in(h->pose, pose_host, H * 12, h->stream));
+    PRG_TRY(prg::copy_in(h->valid, valid_host, H, h->stream));
     h->H = H;
     return PRG_OK;
 }
@@ -646,8 +628,7 @@ int prg_ransac_score(prg_ransac* h, double tau) {
     PRG_REQUIRE(std::isfinite(tau) && tau >= 0.0, PRG_ERR_INVALID, "prg_ransac_score: tau must be finite and >= 0, got %g", tau);
     PRG_REQUIRE(h->C >= 3, PRG_ERR_STATE, "prg_ransac_score: no correspondences (prg_ransac_set_correspondences first)");
     PRG_REQUIRE(h->H >= 1, PRG_ERR_STATE, "prg_ransac_score: no hypotheses (prg_ransac_build or prg_ransac_set_hypotheses first)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_ransac_score: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     const int nseg = (int)prg::ceil_div(h->C, kScoreSegment);
     const int ntiles = (int)prg::ceil_div(h->H, kCompactTile);
@@ -679,18 +660,16 @@ int prg_ransac_score(prg_ransac* h, double tau) {
 int prg_ransac_get_scores(prg_ransac* h, int* counts_host, double* sums_host) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_ransac_get_scores: NULL argument");
     PRG_REQUIRE(h->have_scores, PRG_ERR_STATE, "prg_ransac_get_scores: prg_ransac_score first");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    if (counts_host) PRG_HIP(hipMemcpy(counts_host, h->counts.p, (size_t)h->H * sizeof(int), hipMemcpyDeviceToHost));
-    if (sums_host) PRG_HIP(hipMemcpy(sums_host, h->sums.p, (size_t)h->H * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(counts_host, h->counts, h->H, h->stream));
+    PRG_TRY(prg::copy_out(sums_host, h->sums, h->H, h->stream));
     return PRG_OK;
 }
 
 int prg_ransac_best(prg_ransac* h, int64_t* index_host, int* count_host, double* sum_host, double* pose_host) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_ransac_best: NULL argument");
     PRG_REQUIRE(h->have_scores, PRG_ERR_STATE, "prg_ransac_best: prg_ransac_score first");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_ransac_best: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_REQUIRE(h->n_valid >= 1, PRG_ERR_STATE,
                 "prg_ransac_best: none of the %lld hypotheses is valid (repeated index, edge lengths or degenerate triangle)",
                 (long long)h->H);
@@ -720,8 +699,7 @@ int prg_ransac_refine(prg_ransac* h, double tau, int iters, double* pose_io_host
     for (int k = 0; k < 12; ++k)
         PRG_REQUIRE(std::isfinite(pose_io_host[k]), PRG_ERR_INVALID, "prg_ransac_refine: the pose contains NaN or infinity");
     PRG_REQUIRE(h->C >= 3, PRG_ERR_STATE, "prg_ransac_refine: no correspondences (prg_ransac_set_correspondences first)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_ransac_refine: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     double state[kStateLen] = {0.0};
     for (int k = 0; k < 12; ++k) state[kStatePose + k] = pose_io_host[k];

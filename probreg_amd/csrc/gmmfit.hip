@@ -25,6 +25,7 @@
 #include <new>
 #include <vector>
 
+#include "cell_grid.h"
 #include "dev_buf.h"
 #include "prg_common.h"
 
@@ -482,31 +483,18 @@ int check_k(prg_gmmfit* h, int k, const char* who) {
 extern "C" {
 
 int prg_gmmfit_create(prg_gmmfit** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_gmmfit_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_gmmfit_create: device %d out of range", device);
-    prg_gmmfit* h = new (std::nothrow) prg_gmmfit();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_gmmfit_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_gmmfit_destroy(prg_gmmfit* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_gmmfit_set_data(prg_gmmfit* h, const double* data_hd, int64_t n, int dim) {
     PRG_REQUIRE(h && data_hd, PRG_ERR_INVALID, "prg_gmmfit_set_data: NULL argument");
     PRG_REQUIRE(dim == 2 || dim == 3, PRG_ERR_INVALID, "prg_gmmfit_set_data: dim must be 2 or 3, got %d", dim);
     PRG_REQUIRE(n >= 1 && n < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_gmmfit_set_data: need 1 <= n < 2^31 points");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->n = 0;
     h->dim = 0;
@@ -519,14 +507,14 @@ int prg_gmmfit_set_data(prg_gmmfit* h, const double* data_hd, int64_t n, int dim
     if (e == hipSuccess) e = h->scal.ensure(4, 4);
     if (e == hipSuccess) e = h->n_changed.ensure(1, 1);
     // padded layout (x, y, z or 0, 0): 2-D clouds run through the same kernels with z = 0 on both sides
-    std::vector<double> raw((size_t)n * dim), pad((size_t)n * 4, 0.0);
-    if (e == hipSuccess) e = hipMemcpy(raw.data(), data_hd, raw.size() * sizeof(double), hipMemcpyDefault);
-    for (int64_t i = 0; i < n; ++i)
-        for (int d = 0; d < dim; ++d) pad[(size_t)i * 4 + d] = raw[(size_t)i * dim + d];
-    if (e == hipSuccess) e = hipMemcpyAsync(h->xs.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    std::vector<double> raw, pad;
+    const int st = e == hipSuccess ? prg::load_cloud3(data_hd, n, dim, nullptr, raw, pad, nullptr, nullptr) : PRG_OK;
+    if (e == hipSuccess && st == PRG_OK)
+        e = hipMemcpyAsync(h->xs.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess)  // no half-built cloud: the handle is back to "no data"
+    if (e != hipSuccess || st != PRG_OK)  // no half-built cloud: the handle is back to "no data"
         prg::release_all(h->xs, h->lse, h->mind2, h->labels, h->qpart, h->seed_part, h->seed_pre);
+    PRG_TRY(st);
     PRG_HIP(e);
     h->n = n;
     h->dim = dim;
@@ -541,7 +529,7 @@ int prg_gmmfit_seed(prg_gmmfit* h, int k, const double* uniforms_host, int n_tri
     for (int64_t i = 0; i < (int64_t)k * n_trials; ++i)
         PRG_REQUIRE(uniforms_host[i] >= 0.0 && uniforms_host[i] < 1.0, PRG_ERR_INVALID,
                     "prg_gmmfit_seed: uniforms must lie in [0, 1)");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_comps(h, k));
     h->k = k;
     const int64_t n = h->n;
@@ -573,17 +561,15 @@ int prg_gmmfit_seed(prg_gmmfit* h, int k, const double* uniforms_host, int n_tri
 int prg_gmmfit_get_seeds(prg_gmmfit* h, int* index_host) {
     PRG_REQUIRE(h && index_host, PRG_ERR_INVALID, "prg_gmmfit_get_seeds: NULL argument");
     PRG_REQUIRE(h->have_centers && h->centers.p, PRG_ERR_STATE, "prg_gmmfit_get_seeds: prg_gmmfit_seed first");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipMemcpyAsync(index_host, h->centers.p, (size_t)h->k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    return PRG_OK;
+    PRG_ENTER(h->device);
+    return prg::copy_out(index_host, h->centers, h->k, h->stream);
 }
 
 int prg_gmmfit_lloyd(prg_gmmfit* h, int max_iter, double tol, int* n_iter_host) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_gmmfit_lloyd: NULL argument");
     PRG_REQUIRE(h->have_centers, PRG_ERR_STATE, "prg_gmmfit_lloyd: no centres (prg_gmmfit_seed first)");
     PRG_REQUIRE(max_iter >= 1, PRG_ERR_INVALID, "prg_gmmfit_lloyd: max_iter must be >= 1");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const int64_t n = h->n;
     const unsigned nb = (unsigned)prg::ceil_div(n, kBlock), kb = (unsigned)prg::ceil_div(h->k, kBlock);
     PRG_HIP(hipMemsetAsync(h->labels.p, 0xFF, (size_t)n * sizeof(int), h->stream));  // -1: every label changes first
@@ -625,7 +611,7 @@ int prg_gmmfit_init_from_labels(prg_gmmfit* h, double reg_covar) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_gmmfit_init_from_labels: NULL argument");
     PRG_REQUIRE(h->have_labels, PRG_ERR_STATE, "prg_gmmfit_init_from_labels: no labels (prg_gmmfit_lloyd first)");
     PRG_REQUIRE(reg_covar >= 0.0, PRG_ERR_INVALID, "prg_gmmfit_init_from_labels: reg_covar must be >= 0");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(moments<true>(h));
     PRG_TRY(mstep(h, reg_covar, kFinInit));
     PRG_HIP(hipStreamSynchronize(h->stream));
@@ -640,7 +626,7 @@ int prg_gmmfit_set_params(prg_gmmfit* h, int k, const double* weights_host, cons
     for (int j = 0; j < k; ++j)
         PRG_REQUIRE(precisions_host[j] > 0.0 && weights_host[j] >= 0.0, PRG_ERR_INVALID,
                     "prg_gmmfit_set_params: component %d needs precision > 0 and weight >= 0", j);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_comps(h, k));
     h->k = k;
     std::vector<double> mu((size_t)k * 3, 0.0);
@@ -665,7 +651,7 @@ int prg_gmmfit_em(prg_gmmfit* h, double tol, int max_iter, double reg_covar, int
                 "prg_gmmfit_em: no parameters (prg_gmmfit_set_params or prg_gmmfit_init_from_labels first)");
     PRG_REQUIRE(max_iter >= 1, PRG_ERR_INVALID, "prg_gmmfit_em: max_iter must be >= 1");
     PRG_REQUIRE(reg_covar >= 0.0, PRG_ERR_INVALID, "prg_gmmfit_em: reg_covar must be >= 0");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const int64_t n = h->n;
     const unsigned nb = (unsigned)prg::ceil_div(n, kBlock);
     double prev = -std::numeric_limits<double>::infinity();
@@ -699,15 +685,12 @@ int prg_gmmfit_get_params(prg_gmmfit* h, double* weights_host, double* means_hos
     PRG_REQUIRE(h->have_params || h->have_centers, PRG_ERR_STATE, "prg_gmmfit_get_params: nothing fitted yet");
     PRG_REQUIRE((!weights_host && !covariances_host) || h->have_cov, PRG_ERR_STATE,
                 "prg_gmmfit_get_params: weights and covariances exist after an M-step only");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const int k = h->k;
     std::vector<double> mu((size_t)k * 3);
-    if (weights_host)
-        PRG_HIP(hipMemcpyAsync(weights_host, h->w.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (covariances_host)
-        PRG_HIP(hipMemcpyAsync(covariances_host, h->cov.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipMemcpyAsync(mu.data(), h->mu.p, mu.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_TRY(prg::copy_out(weights_host, h->w, k, h->stream));
+    PRG_TRY(prg::copy_out(covariances_host, h->cov, k, h->stream));
+    PRG_TRY(prg::copy_out(mu.data(), h->mu, k * 3, h->stream));
     if (means_host)
         for (int j = 0; j < k; ++j)
             for (int d = 0; d < h->dim; ++d) means_host[(size_t)j * h->dim + d] = mu[(size_t)j * 3 + d];

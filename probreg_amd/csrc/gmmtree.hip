@@ -18,6 +18,7 @@
 #include <new>
 #include <vector>
 
+#include "cell_grid.h"
 #include "dev_buf.h"
 #include "lattice_sort.h"
 #include "prg_common.h"
@@ -557,24 +558,11 @@ void init_nodes(const double* pts, int64_t n, int levels, const int64_t* idx, st
 extern "C" {
 
 int prg_gmm_create(prg_gmmtree** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_gmm_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_gmm_create: device %d out of range", device);
-    prg_gmmtree* h = new (std::nothrow) prg_gmmtree();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_gmm_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_gmm_destroy(prg_gmmtree* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_gmm_build(prg_gmmtree* h, const double* points_hd, int64_t n, int tree_level, const int64_t* init_idx_host,
@@ -588,15 +576,13 @@ int prg_gmm_build(prg_gmmtree* h, const double* points_hd, int64_t n, int tree_l
     for (int64_t j = 0; j < nl; ++j)
         PRG_REQUIRE(init_idx_host[j] >= 0 && init_idx_host[j] < n, PRG_ERR_INVALID,
                     "prg_gmm_build: init index %lld out of range", (long long)init_idx_host[j]);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(alloc_tree(h, tree_level));
     PRG_TRY(ensure_ws(h, n, nl / 8, 80));
     PRG_HIP(h->q.ensure(8, 8));
     // host copy of the points: initialisation (not a hot path) and the padded device layout
-    std::vector<double> pts((size_t)n * 3), pad((size_t)n * 4, 0.0), init;
-    PRG_HIP(hipMemcpy(pts.data(), points_hd, pts.size() * sizeof(double), hipMemcpyDefault));
-    for (int64_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) pad[(size_t)i * 4 + k] = pts[(size_t)i * 3 + k];
+    std::vector<double> pts, pad, init;
+    PRG_TRY(prg::load_cloud3(points_hd, n, 3, nullptr, pts, pad, nullptr, nullptr));
     PRG_HIP(hipMemcpyAsync(h->xa.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     init_nodes(pts.data(), n, tree_level, init_idx_host, init);
     PRG_TRY(upload_nodes(h, init.data()));
@@ -653,7 +639,7 @@ int prg_gmm_set_nodes(prg_gmmtree* h, const double* nodes_host, int tree_level) 
     PRG_REQUIRE(h && nodes_host, PRG_ERR_INVALID, "prg_gmm_set_nodes: NULL argument");
     PRG_REQUIRE(tree_level >= 1 && tree_level <= 4, PRG_ERR_INVALID, "prg_gmm_set_nodes: tree_level %d not in [1, 4]",
                 tree_level);
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(alloc_tree(h, tree_level));
     return upload_nodes(h, nodes_host);
 }
@@ -661,16 +647,14 @@ int prg_gmm_set_nodes(prg_gmmtree* h, const double* nodes_host, int tree_level) 
 int prg_gmm_get_nodes(prg_gmmtree* h, double* nodes_host) {
     PRG_REQUIRE(h && nodes_host, PRG_ERR_INVALID, "prg_gmm_get_nodes: NULL argument");
     PRG_REQUIRE(h->nodes.p, PRG_ERR_STATE, "prg_gmm_get_nodes: no tree (build or set_nodes first)");
-    prg::DeviceGuard g(h->device);
-    PRG_HIP(hipMemcpyAsync(nodes_host, h->nodes.p, h->n_nodes * kNodeD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    return PRG_OK;
+    PRG_ENTER(h->device);
+    return prg::copy_out(nodes_host, h->nodes, h->n_nodes * kNodeD, h->stream);
 }
 
 int prg_gmm_set_target(prg_gmmtree* h, const double* target_hd, int64_t n) {
     PRG_REQUIRE(h && target_hd, PRG_ERR_INVALID, "prg_gmm_set_target: NULL argument");
     PRG_REQUIRE(n >= 1 && n < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_gmm_set_target: need 1 <= n < 2^31 points");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->n_tgt = 0;
     hipError_t e = h->tgt.reset(n * 3);
@@ -686,7 +670,7 @@ int prg_gmm_reg_estep(prg_gmmtree* h, const double* rot9, const double* t3, doub
                       double* m01_host, double* m2_host) {
     PRG_REQUIRE(h && rot9 && t3 && m01_host, PRG_ERR_INVALID, "prg_gmm_reg_estep: NULL argument");
     PRG_REQUIRE(h->nodes.p && h->tgt.p, PRG_ERR_STATE, "prg_gmm_reg_estep: need a tree and a target");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const int64_t n = h->n_tgt;
     const int n_seg = (int)h->n_nodes;
     PRG_TRY(ensure_ws(h, n, n_seg, 80));

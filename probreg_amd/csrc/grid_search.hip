@@ -476,11 +476,9 @@ int prg_icp_get_grid(prg_icp* h, double* cell_edge_host, int* dims_host, int* de
 
 int prg_icp_get_matches(prg_icp* h, int* index_host, double* d2_host) {
     PRG_TRY(require_ready(h, "prg_icp_get_matches", true));
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_matches: hipSetDevice(%d) failed", h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    if (index_host) PRG_HIP(hipMemcpy(index_host, h->idx.p, (size_t)h->M * sizeof(int), hipMemcpyDeviceToHost));
-    if (d2_host) PRG_HIP(hipMemcpy(d2_host, h->d2.p, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(index_host, h->idx, h->M, h->stream));
+    PRG_TRY(prg::copy_out(d2_host, h->d2, h->M, h->stream));
     return PRG_OK;
 }
 
@@ -492,28 +490,23 @@ int prg_icp_max_k(int* out) {
 
 int prg_icp_knn(prg_icp* h, int k, double r) {
     PRG_TRY(require_ready(h, "prg_icp_knn", false));
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_knn: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     return run_knn(h, "prg_icp_knn", k, r);
 }
 
 int prg_icp_get_knn(prg_icp* h, int* index_host, double* d2_host, int* count_host) {
     PRG_TRY(require_ready(h, "prg_icp_get_knn", false));
     PRG_REQUIRE(h->have_knn > 0, PRG_ERR_STATE, "prg_icp_get_knn: no lists (prg_icp_knn first)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_knn: hipSetDevice(%d) failed", h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    const size_t slots = (size_t)h->M * (size_t)h->have_knn;
-    if (index_host) PRG_HIP(hipMemcpy(index_host, h->knn_idx.p, slots * sizeof(int), hipMemcpyDeviceToHost));
-    if (d2_host) PRG_HIP(hipMemcpy(d2_host, h->knn_d2.p, slots * sizeof(double), hipMemcpyDeviceToHost));
-    if (count_host) PRG_HIP(hipMemcpy(count_host, h->knn_cnt.p, (size_t)h->M * sizeof(int), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(index_host, h->knn_idx, h->M * h->have_knn, h->stream));
+    PRG_TRY(prg::copy_out(d2_host, h->knn_d2, h->M * h->have_knn, h->stream));
+    PRG_TRY(prg::copy_out(count_host, h->knn_cnt, h->M, h->stream));
     return PRG_OK;
 }
 
 int prg_icp_radius_count(prg_icp* h, double r) {
     PRG_TRY(require_ready(h, "prg_icp_radius_count", false));
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_radius_count: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     return run_radius_count(h, "prg_icp_radius_count", r);
 }
 
@@ -521,10 +514,8 @@ int prg_icp_get_counts(prg_icp* h, int* count_host) {
     PRG_TRY(require_ready(h, "prg_icp_get_counts", false));
     PRG_REQUIRE(count_host != nullptr, PRG_ERR_INVALID, "prg_icp_get_counts: NULL argument");
     PRG_REQUIRE(h->have_counts, PRG_ERR_STATE, "prg_icp_get_counts: no counts (prg_icp_radius_count first)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_counts: hipSetDevice(%d) failed", h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(count_host, h->counts.p, (size_t)h->M * sizeof(int), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(count_host, h->counts, h->M, h->stream));
     return PRG_OK;
 }
 

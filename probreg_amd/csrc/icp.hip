@@ -413,24 +413,11 @@ void drop_lists(prg_icp* h) {
 extern "C" {
 
 int prg_icp_create(prg_icp** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_icp_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_icp_create: device %d out of range", device);
-    prg_icp* h = new (std::nothrow) prg_icp();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_icp_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_icp_destroy(prg_icp* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normals_hd, int64_t n, double cell_edge) {
@@ -439,8 +426,7 @@ int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normal
                 (long long)n);
     PRG_REQUIRE(cell_edge >= 0.0 && std::isfinite(cell_edge), PRG_ERR_INVALID,
                 "prg_icp_set_target: cell_edge must be finite and >= 0 (0: chosen from the cloud), got %g", cell_edge);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_target: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     PRG_HIP(hipStreamSynchronize(st));
     h->N = 0;
@@ -448,12 +434,12 @@ int prg_icp_set_target(prg_icp* h, const double* points_hd, const double* normal
     drop_lists(h);
     std::vector<double> raw, pad;
     double lo[3], hi[3];
-    PRG_TRY(prg::load_cloud3(points_hd, n, "prg_icp_set_target: the points contain NaN or infinity", raw, pad, lo, hi));
+    PRG_TRY(prg::load_cloud3(points_hd, n, 3, "prg_icp_set_target: the points contain NaN or infinity", raw, pad, lo, hi));
     PRG_HIP(h->tp.ensure(n, n));
     PRG_HIP(hipMemcpy(h->tp.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
     PRG_TRY(build_levels(h, raw, n, lo, hi, cell_edge));
     if (normals_hd) {
-        PRG_TRY(prg::load_cloud3(normals_hd, n, "prg_icp_set_target: the normals contain NaN or infinity", raw, pad, nullptr,
+        PRG_TRY(prg::load_cloud3(normals_hd, n, 3, "prg_icp_set_target: the normals contain NaN or infinity", raw, pad, nullptr,
                                  nullptr));
         PRG_HIP(h->tn.ensure(n, n));
         PRG_HIP(hipMemcpy(h->tn.p, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -468,8 +454,7 @@ int prg_icp_set_source(prg_icp* h, const double* points_hd, int64_t m) {
     PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_icp_set_source: NULL argument");
     PRG_REQUIRE(m >= 1 && m < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_icp_set_source: need 1 <= m < 2^31 points, got %lld",
                 (long long)m);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_source: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->M = 0;
     h->have_order = h->have_matches = h->have_cov[0] = false;
@@ -495,8 +480,7 @@ int prg_icp_set_covariances(prg_icp* h, int which, const double* cov_hd, int64_t
     PRG_REQUIRE(h && cov_hd, PRG_ERR_INVALID, "prg_icp_set_covariances: NULL argument");
     int64_t rows = 0;
     PRG_TRY(cov_rows(h, "prg_icp_set_covariances", which, n, &rows));
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_covariances: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->have_cov[which] = false;
     std::vector<double> raw((size_t)rows * kCov);
@@ -521,8 +505,7 @@ int prg_icp_set_covariances_from_normals(prg_icp* h, int which, const double* no
     PRG_TRY(cov_rows(h, "prg_icp_set_covariances_from_normals", which, n, &rows));
     PRG_REQUIRE(epsilon > 0.0 && epsilon <= 1.0, PRG_ERR_INVALID,
                 "prg_icp_set_covariances_from_normals: epsilon must lie in (0, 1], got %g", epsilon);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_covariances_from_normals: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     PRG_HIP(hipStreamSynchronize(st));
     h->have_cov[which] = false;
@@ -551,23 +534,17 @@ int prg_icp_get_covariances(prg_icp* h, int which, double* cov_host) {
                 which);
     PRG_REQUIRE(h->have_cov[which], PRG_ERR_STATE, "prg_icp_get_covariances: the %s has no covariances",
                 which == 0 ? "source" : "target");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_covariances: hipSetDevice(%d) failed", h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    const int64_t rows = which == 0 ? h->M : h->N;
-    PRG_HIP(hipMemcpy(cov_host, h->cov[which].p, (size_t)rows * kCov * sizeof(double), hipMemcpyDeviceToHost));
-    return PRG_OK;
+    PRG_ENTER(h->device);
+    return prg::copy_out(cov_host, h->cov[which], (which == 0 ? h->M : h->N) * kCov, h->stream);
 }
 
 int prg_icp_set_pose(prg_icp* h, const double* pose_host) {
     PRG_REQUIRE(h && pose_host, PRG_ERR_INVALID, "prg_icp_set_pose: NULL argument");
     for (int k = 0; k < 12; ++k)
         PRG_REQUIRE(std::isfinite(pose_host[k]), PRG_ERR_INVALID, "prg_icp_set_pose: the pose contains NaN or infinity");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_set_pose: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_state(h));
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(h->state.p + kStPose, pose_host, 12 * sizeof(double), hipMemcpyHostToDevice));
+    PRG_TRY(prg::copy_in(h->state, pose_host, 12, h->stream, kStPose));
     h->have_matches = false;
     drop_lists(h);
     return PRG_OK;
@@ -575,19 +552,16 @@ int prg_icp_set_pose(prg_icp* h, const double* pose_host) {
 
 int prg_icp_get_pose(prg_icp* h, double* pose_host) {
     PRG_REQUIRE(h && pose_host, PRG_ERR_INVALID, "prg_icp_get_pose: NULL argument");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_pose: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_state(h));
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(pose_host, h->state.p + kStPose, 12 * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_TRY(prg::copy_out(pose_host, h->state, 12, h->stream, kStPose));
     return PRG_OK;
 }
 
 int prg_icp_search(prg_icp* h, double r) {
     PRG_TRY(require_ready(h, "prg_icp_search", false));
     PRG_REQUIRE(r > 0.0, PRG_ERR_INVALID, "prg_icp_search: r must be > 0 (infinity: no limit), got %g", r);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_search: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_order(h));
     k_icp_reset<<<1, 1, 0, h->stream>>>(0, h->state.p);
     enqueue_search(h, r);
@@ -600,8 +574,7 @@ int prg_icp_sums(prg_icp* h, int kind, double* out_host) {
     PRG_TRY(require_ready(h, "prg_icp_sums", true));
     PRG_REQUIRE(out_host != nullptr, PRG_ERR_INVALID, "prg_icp_sums: NULL argument");
     PRG_TRY(check_kind("prg_icp_sums", h, kind));
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_sums: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     k_icp_reset<<<1, 1, 0, h->stream>>>(0, h->state.p);
     enqueue_eval(h, kind, 0, 0.0, 0.0);
     if (kind == kPointToPoint) enqueue_sums<1>(h, 0, 0.0, 0.0);
@@ -622,8 +595,7 @@ int prg_icp_sums(prg_icp* h, int kind, double* out_host) {
 int prg_icp_step(prg_icp* h, int kind) {
     PRG_TRY(require_ready(h, "prg_icp_step", true));
     PRG_TRY(check_kind("prg_icp_step", h, kind));
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_step: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     k_icp_reset<<<1, 1, 0, h->stream>>>(1, h->state.p);
     enqueue_eval(h, kind, 0, 0.0, 0.0);
     enqueue_step(h, kind);
@@ -642,8 +614,7 @@ int prg_icp_iterate(prg_icp* h, int kind, double r, int max_iteration, double re
     PRG_REQUIRE(std::isfinite(rel_fitness) && std::isfinite(rel_rmse), PRG_ERR_INVALID,
                 "prg_icp_iterate: relative_fitness and relative_rmse must be finite");
     PRG_REQUIRE(chunk >= 1, PRG_ERR_INVALID, "prg_icp_iterate: chunk must be >= 1, got %d", chunk);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_iterate: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     PRG_TRY(ensure_order(h));
     drop_lists(h);  // the loop moves the pose
@@ -672,12 +643,10 @@ int prg_icp_iterate(prg_icp* h, int kind, double r, int max_iteration, double re
 int prg_icp_get_state(prg_icp* h, double* pose_host, int64_t* count_host, double* sum_host, int* n_iter_host,
                       int* converged_host, int* status_host) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_icp_get_state: NULL argument");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_state: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_TRY(ensure_state(h));
     double s[kStLen];
-    PRG_HIP(hipMemcpyAsync(s, h->state.p, sizeof(s), hipMemcpyDeviceToHost, h->stream));
-    PRG_HIP(hipStreamSynchronize(h->stream));
+    PRG_TRY(prg::copy_out(s, h->state, kStLen, h->stream));
     if (pose_host)
         for (int k = 0; k < 12; ++k) pose_host[k] = s[kStPose + k];
     if (count_host) *count_host = (int64_t)s[kStCount];

@@ -88,8 +88,7 @@ int prg_icp_outlier_statistical(prg_icp* h, int k, double std_ratio) {
     PRG_TRY(require_ready(h, "prg_icp_outlier_statistical", false));
     PRG_REQUIRE(std_ratio >= 0.0 && std::isfinite(std_ratio), PRG_ERR_INVALID,
                 "prg_icp_outlier_statistical: std_ratio must be finite and >= 0, got %g", std_ratio);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_outlier_statistical: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     h->have_outlier = 0;
     PRG_TRY(run_knn(h, "prg_icp_outlier_statistical", k, INFINITY));
     const int64_t M = h->M, nruns = prg::ceil_div(M, kRun);  // part holds nruns kSlots doubles (prg_icp_set_source)
@@ -112,8 +111,7 @@ int prg_icp_outlier_statistical(prg_icp* h, int k, double std_ratio) {
 int prg_icp_outlier_radius(prg_icp* h, double r, int nb_points) {
     PRG_TRY(require_ready(h, "prg_icp_outlier_radius", false));
     PRG_REQUIRE(nb_points >= 0, PRG_ERR_INVALID, "prg_icp_outlier_radius: nb_points must be >= 0, got %d", nb_points);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_outlier_radius: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     h->have_outlier = 0;
     PRG_TRY(run_radius_count(h, "prg_icp_outlier_radius", r));
     const int64_t M = h->M;
@@ -130,12 +128,10 @@ int prg_icp_get_outlier(prg_icp* h, unsigned char* keep_host, double* score_host
                 "prg_icp_get_outlier: no filter result (prg_icp_outlier_statistical or prg_icp_outlier_radius first)");
     PRG_REQUIRE(h->have_outlier == 1 || (score_host == nullptr && stat_host == nullptr), PRG_ERR_STATE,
                 "prg_icp_get_outlier: the radius filter has no score or statistics (its counts: prg_icp_get_counts)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_icp_get_outlier: hipSetDevice(%d) failed", h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    if (keep_host) PRG_HIP(hipMemcpy(keep_host, h->keep.p, (size_t)h->M, hipMemcpyDeviceToHost));
-    if (score_host) PRG_HIP(hipMemcpy(score_host, h->score.p, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost));
-    if (stat_host) PRG_HIP(hipMemcpy(stat_host, h->stat.p, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    PRG_ENTER(h->device);
+    PRG_TRY(prg::copy_out(keep_host, h->keep, h->M, h->stream));
+    PRG_TRY(prg::copy_out(score_host, h->score, h->M, h->stream));
+    PRG_TRY(prg::copy_out(stat_host, h->stat, 3, h->stream));
     return PRG_OK;
 }
 

@@ -21,8 +21,8 @@ struct FrFeat {
 // what the resolve kernel publishes to the host (see k_resolve)
 struct LatticeMail { int size, overflow, side_size, side_overflow; unsigned seq; unsigned pad[3]; };
 
-// Every buffer owns its memory (dev_buf.h): deleting the handle, under its DeviceGuard and after the stream has drained,
-// releases everything.
+// Every buffer owns its memory (dev_buf.h): deleting the handle (destroy_handle, plan_base.h: on its device, after the stream
+// has drained) releases everything.
 struct Lattice {
     int device = 0;
     hipStream_t stream = nullptr;

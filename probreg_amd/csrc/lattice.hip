@@ -1325,6 +1325,7 @@ int lat_filter(Lattice* L, const float* in, int ch, int64_t first, int64_t n_out
 
 struct prg_ph {
     prg::Lattice L;
+    prg::Lattice& ctx() { return L; }  // device and stream (plan_base.h)
 };
 
 extern "C" {
@@ -1340,31 +1341,18 @@ int prg_lattice_set_splat_mode(int mode) {
 // stand-alone lattice (gaussian_filtering.Permutohedral)
 // ---------------------------------------------------------------------------------------------
 int prg_ph_create(prg_ph** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_ph_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_ph_create: device %d out of range", device);
-    prg_ph* h = new (std::nothrow) prg_ph();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_ph_create: out of host memory");
-    h->L.device = device;
-    h->L.stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_ph_destroy(prg_ph* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->L.device);
-    (void)hipStreamSynchronize(h->L.stream);
-    delete h;  // (the lattice's buffers release themselves)
-    return PRG_OK;
+    return prg::destroy_handle(h);  // (the lattice's buffers release themselves)
 }
 
 int prg_ph_init(prg_ph* h, const float* points_hd, int64_t n, int dim, int with_blur) {
     PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_ph_init: NULL argument");
     PRG_REQUIRE(n > 0 && dim >= 1 && dim <= kMaxDG, PRG_ERR_INVALID,
                 "prg_ph_init: need n > 0 and feature dimension in [1, %d] (got n=%lld d=%d)", kMaxDG, (long long)n, dim);
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     prg::Lattice* L = &h->L;
     L->n = 0;  // "not initialised" until the build has gone through
     PRG_HIP(L->feat.reset(n * dim));
@@ -1385,7 +1373,7 @@ int prg_ph_filter(prg_ph* h, const float* values_hd, int channels, float* out_hd
     PRG_REQUIRE(h && values_hd && out_hd, PRG_ERR_INVALID, "prg_ph_filter: NULL argument");
     PRG_REQUIRE(h->L.n > 0, PRG_ERR_STATE, "prg_ph_filter: lattice not initialised");
     PRG_REQUIRE(channels >= 1 && channels <= 32, PRG_ERR_INVALID, "prg_ph_filter: channels must be in [1, 32]");
-    prg::DeviceGuard g(h->L.device);
+    PRG_ENTER(h->L.device);
     prg::Lattice* L = &h->L;
     const int64_t count = L->n * channels;
     const size_t nb = (size_t)count * sizeof(float);

@@ -288,8 +288,7 @@ int prg_squared_kernel_sum(int device, void* hip_stream, const float* x_hd, int6
     PRG_REQUIRE(x_hd && y_hd && out_host, PRG_ERR_INVALID, "prg_squared_kernel_sum: NULL argument");
     PRG_REQUIRE(m > 0 && n > 0 && dim >= 1 && dim <= 64, PRG_ERR_INVALID,
                 "prg_squared_kernel_sum: need m, n > 0 and dim in [1, 64]");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_squared_kernel_sum: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     if (dim != 2 && dim != 3) {  // feature clouds (FilterReg with a feature_fn, filterreg.py:126-128)
         DevBuf<float> fx, fy;
@@ -336,8 +335,7 @@ int prg_rbf_kernel(int device, void* hip_stream, const float* x_hd, int64_t m, c
     PRG_REQUIRE(x_hd && y_hd && out_hd, PRG_ERR_INVALID, "prg_rbf_kernel: NULL argument");
     PRG_REQUIRE(m > 0 && n > 0 && (dim == 2 || dim == 3) && beta > 0, PRG_ERR_INVALID,
                 "prg_rbf_kernel: need m, n > 0, dim in {2,3}, beta > 0");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_rbf_kernel: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     DevBuf<float> bx, by, bo;
     PRG_HIP(bx.reset(m * dim));
@@ -358,8 +356,7 @@ int prg_inverse_multiquadric_kernel(int device, void* hip_stream, const float* x
     PRG_REQUIRE(x_hd && y_hd && out_hd, PRG_ERR_INVALID, "prg_inverse_multiquadric_kernel: NULL argument");
     PRG_REQUIRE(m > 0 && n > 0 && (dim == 2 || dim == 3) && c > 0, PRG_ERR_INVALID,
                 "prg_inverse_multiquadric_kernel: need m, n > 0, dim in {2,3}, c > 0");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_inverse_multiquadric_kernel: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     DevBuf<float> bx, by, bo;
     PRG_HIP(bx.reset(m * dim));
@@ -380,8 +377,7 @@ int prg_nn_mean_distance(int device, void* hip_stream, const float* a_hd, int64_
     PRG_REQUIRE(a_hd && b_hd && out_host, PRG_ERR_INVALID, "prg_nn_mean_distance: NULL argument");
     PRG_REQUIRE(m > 0 && n > 0 && (dim == 2 || dim == 3), PRG_ERR_INVALID,
                 "prg_nn_mean_distance: need m, n > 0 and dim in {2,3}");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_nn_mean_distance: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     // enough (a block, b segment) workgroups to fill 256 CUs even for a few thousand points
     const int64_t nbx = prg::ceil_div(m, kBlock);
@@ -415,8 +411,7 @@ int prg_gauss_transform_direct(int device, void* hip_stream, const double* sourc
                 "prg_gauss_transform_direct: NULL argument");
     PRG_REQUIRE(s > 0 && t > 0 && (dim == 2 || dim == 3) && n_weight_rows > 0 && h > 0, PRG_ERR_INVALID,
                 "prg_gauss_transform_direct: need s, t, rows > 0, dim in {2,3}, h > 0");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_gauss_transform_direct: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     const int64_t cap = prg::round_up(s, 256);
     const int rows = n_weight_rows;
@@ -460,8 +455,7 @@ int prg_gauss_transform_direct_f64(int device, void* hip_stream, const double* s
                 "prg_gauss_transform_direct_f64: NULL argument");
     PRG_REQUIRE(s > 0 && t > 0 && (dim == 2 || dim == 3) && n_weight_rows > 0 && h > 0, PRG_ERR_INVALID,
                 "prg_gauss_transform_direct_f64: need s, t, rows > 0, dim in {2,3}, h > 0");
-    prg::DeviceGuard g(device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_gauss_transform_direct_f64: hipSetDevice(%d) failed", device);
+    PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     const int64_t cap = prg::round_up(s, 256);
     const int rows = n_weight_rows;

@@ -33,6 +33,7 @@
 #include <new>
 #include <vector>
 
+#include "cell_grid.h"
 #include "dev_buf.h"
 #include "prg_common.h"
 
@@ -233,50 +234,24 @@ struct prg_ocsvm {
     std::vector<double> alpha_host;
     std::vector<int> support;
     double prof_ms[4] = {0.0, 0.0, 0.0, 0.0};  // initial gradient, select, subproblem, sweep
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-};
-
-namespace {
-
-// Host copy of k x dim doubles that live on the host or the device, padded to (x, y, z or 0, 0)
-int padded_points(const double* pts_hd, int64_t k, int dim, std::vector<double>& pad) {
-    std::vector<double> raw((size_t)k * dim);
-    PRG_HIP(hipMemcpy(raw.data(), pts_hd, raw.size() * sizeof(double), hipMemcpyDefault));
-    pad.assign((size_t)k * 4, 0.0);
-    for (int64_t i = 0; i < k; ++i)
-        for (int d = 0; d < dim; ++d) {
-            const double v = raw[(size_t)i * dim + d];
-            if (!std::isfinite(v)) return PRG_ERR_INVALID;
-            pad[(size_t)i * 4 + d] = v;
+    struct Events {  // created by prg_ocsvm_set_profile, destroyed with the handle
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t x : e)
+                if (x) (void)hipEventDestroy(x);
         }
-    return PRG_OK;
-}
-
-}  // namespace
+        hipEvent_t& operator[](int i) { return e[i]; }
+    } ev;
+};
 
 extern "C" {
 
 int prg_ocsvm_create(prg_ocsvm** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_ocsvm_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_ocsvm_create: device %d out of range", device);
-    prg_ocsvm* h = new (std::nothrow) prg_ocsvm();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_ocsvm_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_ocsvm_destroy(prg_ocsvm* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_ocsvm_working_set_size(int* q_host) {
@@ -289,11 +264,9 @@ int prg_ocsvm_set_data(prg_ocsvm* h, const double* data_hd, int64_t n, int dim) 
     PRG_REQUIRE(h && data_hd, PRG_ERR_INVALID, "prg_ocsvm_set_data: NULL argument");
     PRG_REQUIRE(dim == 2 || dim == 3, PRG_ERR_INVALID, "prg_ocsvm_set_data: dim must be 2 or 3, got %d", dim);
     PRG_REQUIRE(n >= 1 && n < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_ocsvm_set_data: need 1 <= n < 2^31 points");
-    prg::DeviceGuard g(h->device);
-    std::vector<double> pad;
-    const int st = padded_points(data_hd, n, dim, pad);
-    PRG_REQUIRE(st != PRG_ERR_INVALID, PRG_ERR_INVALID, "prg_ocsvm_set_data: data contains NaN or infinity");
-    PRG_TRY(st);
+    PRG_ENTER(h->device);
+    std::vector<double> raw, pad;
+    PRG_TRY(prg::load_cloud3(data_hd, n, dim, "prg_ocsvm_set_data: data contains NaN or infinity", raw, pad, nullptr, nullptr));
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->solved = false;
     h->n = 0;
@@ -315,9 +288,9 @@ int prg_ocsvm_set_data(prg_ocsvm* h, const double* data_hd, int64_t n, int dim) 
 
 int prg_ocsvm_set_profile(prg_ocsvm* h, int on) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_ocsvm_set_profile: NULL argument");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     if (on)
-        for (hipEvent_t& e : h->ev)
+        for (hipEvent_t& e : h->ev.e)
             if (!e) PRG_HIP(hipEventCreate(&e));
     h->profile = on != 0;
     return PRG_OK;
@@ -338,7 +311,7 @@ int prg_ocsvm_solve(prg_ocsvm* h, double gamma, double nu, double tol, int max_i
     PRG_REQUIRE(tol > 0.0 && std::isfinite(tol), PRG_ERR_INVALID, "prg_ocsvm_solve: tol must be > 0 and finite");
     PRG_REQUIRE(max_iter >= 0, PRG_ERR_INVALID, "prg_ocsvm_solve: max_iter must be >= 0");
     PRG_REQUIRE(inner_cap >= 1, PRG_ERR_INVALID, "prg_ocsvm_solve: inner_cap must be >= 1");
-    prg::DeviceGuard g(h->device);
+    PRG_ENTER(h->device);
     const int64_t n = h->n;
     const unsigned nb = (unsigned)prg::ceil_div(n, kBlock);
     h->solved = false;
@@ -455,11 +428,9 @@ int prg_ocsvm_decision(prg_ocsvm* h, const double* points_hd, int64_t k, double*
     PRG_REQUIRE(h && points_hd && out_hd, PRG_ERR_INVALID, "prg_ocsvm_decision: NULL argument");
     PRG_REQUIRE(h->solved, PRG_ERR_STATE, "prg_ocsvm_decision: prg_ocsvm_solve first");
     PRG_REQUIRE(k >= 1 && k < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_ocsvm_decision: need 1 <= k < 2^31 points");
-    prg::DeviceGuard g(h->device);
-    std::vector<double> pad;
-    const int st = padded_points(points_hd, k, h->dim, pad);
-    PRG_REQUIRE(st != PRG_ERR_INVALID, PRG_ERR_INVALID, "prg_ocsvm_decision: points contain NaN or infinity");
-    PRG_TRY(st);
+    PRG_ENTER(h->device);
+    std::vector<double> raw, pad;
+    PRG_TRY(prg::load_cloud3(points_hd, k, h->dim, "prg_ocsvm_decision: points contain NaN or infinity", raw, pad, nullptr, nullptr));
     prg::DevBuf<double4> tg;
     prg::DevBuf<double> out;
     PRG_HIP(tg.reset(k));

@@ -8,34 +8,9 @@
 #include <string>
 
 #include "../../include/probreg_hip.h"
+#include "plan_base.h"  // PRG_HIP, PRG_REQUIRE, PRG_TRY, PRG_ENTER and the handle templates
 
 namespace prg {
-
-void set_error(const char* fmt, ...);
-
-#define PRG_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) {                                                                \
-            prg::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__,    \
-                           __LINE__);                                                          \
-            return PRG_ERR_HIP;                                                                \
-        }                                                                                      \
-    } while (0)
-
-#define PRG_REQUIRE(cond, status, ...)                                                         \
-    do {                                                                                       \
-        if (!(cond)) {                                                                         \
-            prg::set_error(__VA_ARGS__);                                                       \
-            return (status);                                                                   \
-        }                                                                                      \
-    } while (0)
-
-#define PRG_TRY(expr)                                                                          \
-    do {                                                                                       \
-        int _s = (expr);                                                                       \
-        if (_s != PRG_OK) return _s;                                                           \
-    } while (0)
 
 static inline int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -45,20 +20,6 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // contributes exp2(-huge) == 0 to every sum - inner loops need no bounds checks.
 constexpr float kSrcPad = 1.0e18f;
 constexpr float kTgtPad = -1.0e18f;
-
-// RAII device selection for API entry points.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 
 // Wait for a device-written sequence number in a mapped host mailbox without draining the queue: a short spin (the
 // answer normally arrives within microseconds of the kernel that writes it), bounded by a time budget - a stream that

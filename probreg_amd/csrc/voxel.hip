@@ -261,14 +261,11 @@ int sums_of(prg_voxel* h, const double* src, int K, double* means, bool with_cou
 }
 
 template <class T>
-int fetch(prg_voxel* h, const char* who, T* host, const T* dev, int64_t count) {
+int fetch(prg_voxel* h, const char* who, T* host, const prg::DevBuf<T>* dev, int64_t count) {
     PRG_REQUIRE(h && host, PRG_ERR_INVALID, "%s: NULL argument", who);
     PRG_REQUIRE(h->have_result, PRG_ERR_STATE, "%s: prg_voxel_run first", who);
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "%s: hipSetDevice(%d) failed", who, h->device);
-    PRG_HIP(hipStreamSynchronize(h->stream));
-    PRG_HIP(hipMemcpy(host, dev, (size_t)count * sizeof(T), hipMemcpyDeviceToHost));
-    return PRG_OK;
+    PRG_ENTER_AS(who, h->device);
+    return prg::copy_out(host, *dev, count, h->stream);
 }
 
 }  // namespace
@@ -276,24 +273,11 @@ int fetch(prg_voxel* h, const char* who, T* host, const T* dev, int64_t count) {
 extern "C" {
 
 int prg_voxel_create(prg_voxel** out, int device, void* hip_stream) {
-    PRG_REQUIRE(out != nullptr, PRG_ERR_INVALID, "prg_voxel_create: out is NULL");
-    int count = 0;
-    PRG_HIP(hipGetDeviceCount(&count));
-    PRG_REQUIRE(device >= 0 && device < count, PRG_ERR_INVALID, "prg_voxel_create: device %d out of range", device);
-    prg_voxel* h = new (std::nothrow) prg_voxel();
-    PRG_REQUIRE(h != nullptr, PRG_ERR_NOMEM, "prg_voxel_create: out of host memory");
-    h->device = device;
-    h->stream = (hipStream_t)hip_stream;
-    *out = h;
-    return PRG_OK;
+    return prg::create_handle(__func__, out, device, hip_stream);
 }
 
 int prg_voxel_destroy(prg_voxel* h) {
-    if (!h) return PRG_OK;
-    prg::DeviceGuard g(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-    return PRG_OK;
+    return prg::destroy_handle(h);
 }
 
 int prg_voxel_set_data(prg_voxel* h, const double* points_hd, int64_t n, int d) {
@@ -301,8 +285,7 @@ int prg_voxel_set_data(prg_voxel* h, const double* points_hd, int64_t n, int d) 
     PRG_REQUIRE(n >= 1 && n < (int64_t)1 << 31, PRG_ERR_INVALID, "prg_voxel_set_data: need 1 <= n < 2^31 points, got %lld",
                 (long long)n);
     PRG_REQUIRE(h && points_hd, PRG_ERR_INVALID, "prg_voxel_set_data: NULL argument");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_voxel_set_data: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->n = 0;
     h->C = 0;
@@ -320,8 +303,7 @@ int prg_voxel_set_channels(prg_voxel* h, const double* channels_hd, int c) {
                 kMaxChannels, c);
     PRG_REQUIRE(h && (c == 0 || channels_hd), PRG_ERR_INVALID, "prg_voxel_set_channels: NULL argument");
     PRG_REQUIRE(h->n >= 1, PRG_ERR_STATE, "prg_voxel_set_channels: no points (prg_voxel_set_data first)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_voxel_set_channels: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     PRG_HIP(hipStreamSynchronize(h->stream));
     h->C = 0;
     h->have_result = false;
@@ -337,8 +319,7 @@ int prg_voxel_run(prg_voxel* h, double v) {
     PRG_REQUIRE(std::isfinite(v) && v > 0.0, PRG_ERR_INVALID, "prg_voxel_run: voxel_size must be finite and > 0, got %g", v);
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_voxel_run: NULL argument");
     PRG_REQUIRE(h->n >= 1, PRG_ERR_STATE, "prg_voxel_run: no points (prg_voxel_set_data first)");
-    prg::DeviceGuard g(h->device);
-    PRG_REQUIRE(g.ok, PRG_ERR_HIP, "prg_voxel_run: hipSetDevice(%d) failed", h->device);
+    PRG_ENTER(h->device);
     hipStream_t st = h->stream;
     const int64_t n = h->n;
     const int d = h->d;
@@ -434,29 +415,29 @@ int prg_voxel_count(prg_voxel* h, int64_t* v_host) {
 }
 
 int prg_voxel_get_means(prg_voxel* h, double* means_host) {
-    return fetch(h, "prg_voxel_get_means", means_host, h ? h->means.p : nullptr, h ? h->V * h->d : 0);
+    return fetch(h, "prg_voxel_get_means", means_host, h ? &h->means : nullptr, h ? h->V * h->d : 0);
 }
 
 int prg_voxel_get_channel_means(prg_voxel* h, double* means_host) {
     PRG_REQUIRE(h != nullptr, PRG_ERR_INVALID, "prg_voxel_get_channel_means: NULL argument");
     PRG_REQUIRE(!h->have_result || h->C > 0, PRG_ERR_STATE, "prg_voxel_get_channel_means: no channels (prg_voxel_set_channels)");
-    return fetch(h, "prg_voxel_get_channel_means", means_host, h->chan_means.p, h->V * h->C);
+    return fetch(h, "prg_voxel_get_channel_means", means_host, &h->chan_means, h->V * h->C);
 }
 
 int prg_voxel_get_counts(prg_voxel* h, int* counts_host) {
-    return fetch(h, "prg_voxel_get_counts", counts_host, h ? h->counts.p : nullptr, h ? h->V : 0);
+    return fetch(h, "prg_voxel_get_counts", counts_host, h ? &h->counts : nullptr, h ? h->V : 0);
 }
 
 int prg_voxel_get_first(prg_voxel* h, int* first_host) {
-    return fetch(h, "prg_voxel_get_first", first_host, h ? h->first.p : nullptr, h ? h->V : 0);
+    return fetch(h, "prg_voxel_get_first", first_host, h ? &h->first : nullptr, h ? h->V : 0);
 }
 
 int prg_voxel_get_inverse(prg_voxel* h, int* inverse_host) {
-    return fetch(h, "prg_voxel_get_inverse", inverse_host, h ? h->inverse.p : nullptr, h ? h->n : 0);
+    return fetch(h, "prg_voxel_get_inverse", inverse_host, h ? &h->inverse : nullptr, h ? h->n : 0);
 }
 
 int prg_voxel_get_keys(prg_voxel* h, uint64_t* keys_host) {
-    PRG_TRY(fetch(h, "prg_voxel_get_keys", keys_host, h ? h->keys.p : nullptr, h ? h->n : 0));
+    PRG_TRY(fetch(h, "prg_voxel_get_keys", keys_host, h ? &h->keys : nullptr, h ? h->n : 0));
     // packed x | y | z in the bits in use -> the definition's c_x 2^42 + c_y 2^21 + c_z
     const int sx = h->shift[0], sy = h->shift[1];
     for (int64_t i = 0; i < h->n; ++i) {
@@ -468,11 +449,11 @@ int prg_voxel_get_keys(prg_voxel* h, uint64_t* keys_host) {
 }
 
 int prg_voxel_get_order(prg_voxel* h, int* order_host) {
-    return fetch(h, "prg_voxel_get_order", order_host, h ? h->order.p : nullptr, h ? h->n : 0);
+    return fetch(h, "prg_voxel_get_order", order_host, h ? &h->order : nullptr, h ? h->n : 0);
 }
 
 int prg_voxel_get_rows(prg_voxel* h, int* rows_host) {
-    return fetch(h, "prg_voxel_get_rows", rows_host, h ? h->rows.p : nullptr, h ? h->n : 0);
+    return fetch(h, "prg_voxel_get_rows", rows_host, h ? &h->rows : nullptr, h ? h->n : 0);
 }
 
 }  // extern "C"

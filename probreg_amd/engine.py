@@ -9,20 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib, ptr
-
-
-def _current_device_and_stream(device=None):
-    """(device index, hipStream_t as int) of the calling process; torch is optional plumbing."""
-    try:
-        import torch
-
-        if torch.cuda.is_available():
-            dev = torch.cuda.current_device() if device is None else int(device)
-            return dev, int(torch.cuda.current_stream(dev).cuda_stream)
-    except ImportError:  # pragma: no cover
-        pass
-    return (0 if device is None else int(device)), 0
+from ._lib import _current_device_and_stream, check, lib, ptr  # noqa: F401 (_current_device_and_stream: re-exported)
 
 
 def spatial_order(points, on_device=True):
@@ -46,33 +33,14 @@ def engine_bounds(m, n_local):
     return float(a.value), float(b.value)
 
 
-class CpdPlan(object):
+class CpdPlan(_lib.Handle):
     """Owns one ``prg_cpd`` handle."""
 
     def __init__(self, device=None, stream=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        if stream is not None:
-            st = int(stream)
-        self.device = dev
-        self.stream = st
-        self._h = ctypes.c_void_p()
-        check(lib.prg_cpd_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(lib.prg_cpd_create, lib.prg_cpd_destroy, device, stream)
         self._moments_tensor = None
         self._comm = None
         self.m = self.n = self.dim = 0
-
-    # -- life cycle -------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.prg_cpd_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover
-            pass
 
     # -- uploads ----------------------------------------------------------------------------
     @staticmethod
@@ -410,19 +378,13 @@ def batch_tile_table(m, n):
     return out
 
 
-class CpdBatchPlan(object):
+class CpdBatchPlan(_lib.Handle):
     """Owns one ``prg_cpd_batch`` handle: B rigid / affine registrations of ragged clouds on one GPU, one HIP stream.
 
     sources, targets : lists of centred (M_b, D) / (N_b, D) float64 arrays (every cloud minus its own mean)
     """
 
     def __init__(self, sources, targets, device=None, stream=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        if stream is not None:
-            st = int(stream)
-        self.device = dev
-        self.stream = st
         self.b = len(sources)
         self.dim = int(sources[0].shape[1])
         soff = np.zeros(self.b + 1, dtype=np.int64)
@@ -431,20 +393,8 @@ class CpdBatchPlan(object):
         toff[1:] = np.cumsum([t.shape[0] for t in targets])
         src = np.ascontiguousarray(np.concatenate(sources, axis=0), dtype=np.float64)
         tgt = np.ascontiguousarray(np.concatenate(targets, axis=0), dtype=np.float64)
-        self._h = ctypes.c_void_p()
-        check(lib.prg_cpd_batch_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st), self.dim, self.b, ptr(soff), ptr(toff),
-                                       ptr(src), ptr(tgt)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.prg_cpd_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover
-            pass
+        super().__init__(lib.prg_cpd_batch_create, lib.prg_cpd_batch_destroy, device, stream, self.dim, self.b, ptr(soff),
+                         ptr(toff), ptr(src), ptr(tgt))
 
     def init(self, init16=None):
         """Start (or restart) every registration; ``init16``: None or (B, 16) blocks as ``CpdPlan.init_params`` takes one."""

@@ -24,7 +24,6 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .engine import _current_device_and_stream
 
 MAX_SEED_TRIALS = 16
 LLOYD_MAX_ITER = 300  # sklearn.cluster.KMeans defaults
@@ -47,29 +46,14 @@ class Feature(abc.ABC):
         return self.compute(data)
 
 
-class GmmFitPlan(object):
+class GmmFitPlan(_lib.Handle):
     """One ``prg_gmmfit`` handle: a cloud on one device / stream and the stages of the fit."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self.device = dev
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib.prg_gmmfit_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_gmmfit_create, _lib.lib.prg_gmmfit_destroy, device)
         self.n = 0
         self.dim = 0
         self.k = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib.prg_gmmfit_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
 
     def set_data(self, data):
         data = np.ascontiguousarray(data, dtype=np.float64)

@@ -26,6 +26,7 @@ import numpy as np
 from . import _lib
 from . import math_utils as mu
 from . import transformation as tf
+from ._lib import as_points as _as_points
 from ._lib import check, lib, ptr
 from .engine import _current_device_and_stream
 from .log import log
@@ -35,26 +36,15 @@ MstepResult = namedtuple("MstepResult", ["transformation", "sigma2", "q"])
 MstepResult.__doc__ = """(transformation, sigma2, q) of one FilterReg M-step / of the whole registration (reference filterreg.py:28)."""
 
 
-def _as_points(x):
-    if x is None:
-        return None
-    if hasattr(x, "points") and not isinstance(x, np.ndarray):
-        x = x.points
-    return np.asarray(x, dtype=np.float64)
-
-
 def _identity(x):
     return x
 
 
-class _Plan(object):
+class _Plan(_lib.Handle):
     """One ``prg_filterreg`` handle."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self._h = ctypes.c_void_p()
-        check(lib.prg_fr_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_fr_create, _lib.lib.prg_fr_destroy, device)
         self.m = self.n = self.dim = 0
 
     def set_source(self, a):
@@ -159,17 +149,6 @@ class _Plan(object):
         out = np.empty((self.seg_a.shape[0], 16))
         check(lib.prg_fr_kinematic_grad_sums(self._h, ptr(tw), 1 if reference_form else 0, out.shape[0], ptr(out)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.prg_fr_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover
-            pass
 
 
 class FilterReg(abc.ABC):

@@ -19,7 +19,6 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .engine import _current_device_and_stream
 from .features import Feature
 
 N_BINS = 33
@@ -34,43 +33,16 @@ def max_neighbours():
     return int(k.value)
 
 
-def _as_cloud(data):
-    """(n, 3) float64 of an array or of anything with ``.points``; ValueError for what the descriptor is not defined on."""
-    pts = np.ascontiguousarray(np.asarray(getattr(data, "points", data)), dtype=np.float64)
-    if pts.ndim != 2 or pts.shape[1] != 3:
-        raise ValueError("data must be (n, 3), got shape %s" % (pts.shape,))
-    if pts.shape[0] < 1:
-        raise ValueError("data must hold at least one point")
-    if not np.all(np.isfinite(pts)):
-        raise ValueError("data contains NaN or infinity")
-    return pts
-
-
-class FpfhPlan(object):
+class FpfhPlan(_lib.Handle):
     """One ``prg_fpfh`` handle: a cloud on one device / stream and the stages of the descriptor."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self.device = dev
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib.prg_fpfh_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_fpfh_create, _lib.lib.prg_fpfh_destroy, device)
         self.n = 0
         self.max_nn = [0, 0]
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib.prg_fpfh_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
-
     def set_data(self, points):
-        points = _as_cloud(points)
+        points = _lib.as_cloud(points, "data", (3,))
         _lib.check(_lib.lib.prg_fpfh_set_data(self._h, _lib.ptr(points), points.shape[0]))
         self.n = points.shape[0]
 
@@ -160,7 +132,7 @@ class FPFH(Feature):
         """Unit normals (n, 3) of an (n, 3) array or of an object with ``.points`` (features.py:43-44); an object that
         has a ``.normals`` attribute gets them assigned as well."""
         self._check_params()
-        pts = _as_cloud(data)
+        pts = _lib.as_cloud(data, "data", (3,))
         plan = FpfhPlan(self._device)
         try:
             plan.set_data(pts)
@@ -174,7 +146,7 @@ class FPFH(Feature):
     def compute(self, data):
         """The (n, 33) float64 descriptors of ``data`` (n, 3) (features.py:46-51)."""
         self._check_params()
-        pts = _as_cloud(data)
+        pts = _lib.as_cloud(data, "data", (3,))
         plan = FpfhPlan(self._device)
         try:
             plan.set_data(pts)

@@ -5,10 +5,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .engine import _current_device_and_stream
 
 
-class Permutohedral(object):
+class Permutohedral(_lib.Handle):
     """``Permutohedral(p, with_blur)`` / ``get_lattice_size()`` / ``filter(v, start)`` as in the reference.
 
     ``p`` is (n, d), 1 <= d <= 64: d <= 3 (positions) takes the packed-key kernels, larger d (feature lattices such as
@@ -16,10 +15,7 @@ class Permutohedral(object):
     """
 
     def __init__(self, p, with_blur=True):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream()
-        self._h = ctypes.c_void_p()
-        check(lib.prg_ph_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_ph_create, _lib.lib.prg_ph_destroy)
         self.init(p, with_blur)
 
     def init(self, p, with_blur=True):
@@ -46,11 +42,3 @@ class Permutohedral(object):
         out = np.empty_like(v)
         check(lib.prg_ph_filter(self._h, ptr(v), v.shape[1], ptr(out)))
         return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                lib.prg_ph_destroy(self._h)
-                self._h = None
-        except Exception:  # pragma: no cover
-            pass

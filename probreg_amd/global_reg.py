@@ -96,28 +96,13 @@ def _check_tau(tau):
     return float(tau)
 
 
-class RansacPlan(object):
+class RansacPlan(_lib.Handle):
     """One ``prg_ransac`` handle: correspondences on one device / stream and the stages of the pose search."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self.device = dev
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib.prg_ransac_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_ransac_create, _lib.lib.prg_ransac_destroy, device)
         self.n_corr = 0
         self.n_hyp = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib.prg_ransac_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
 
     def set_correspondences(self, p, q):
         """Source points ``p`` (C, 3) and their matched target points ``q`` (C, 3)."""

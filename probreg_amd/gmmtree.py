@@ -29,15 +29,13 @@ Differences a caller can see (all on purpose):
 With ``torch.distributed`` initialised every rank solves the whole problem (replicas; nothing is sharded).  Work runs on
 the caller's current HIP stream.
 """
-import ctypes
 from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
 from . import transformation as tf
-from .cpd import _as_points
-from .engine import _current_device_and_stream
+from ._lib import as_points as _as_points
 from .log import log
 
 EstepResult = namedtuple("EstepResult", ["moments"])
@@ -120,27 +118,12 @@ def _tree_level_of(count):
     raise ValueError("a GMM tree has 8 (8^L - 1) / 7 nodes for 1 <= L <= %d, not %d" % (MAX_TREE_LEVEL, count))
 
 
-class GmmTreePlan(object):
+class GmmTreePlan(_lib.Handle):
     """One ``prg_gmmtree`` handle: the tree and the registration target on one device / stream."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self.device = dev
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib.prg_gmm_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_gmm_create, _lib.lib.prg_gmm_destroy, device)
         self.tree_level = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib.prg_gmm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
 
     def build(self, points, tree_level, idx, lambda_s, lambda_d, max_iter):
         pts = np.ascontiguousarray(points, dtype=np.float64)

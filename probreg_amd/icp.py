@@ -27,7 +27,6 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .engine import _current_device_and_stream
 from .global_reg import _as_rows, _single_process
 from .transformation import RigidTransformation
 
@@ -211,29 +210,14 @@ def _normals_of(target, target_normals, n):
     return nrm
 
 
-class IcpPlan(object):
+class IcpPlan(_lib.Handle):
     """One ``prg_icp`` handle: a target with its search grid, a source and a pose on one device / stream, and the stages of
     ICP.  ``cell_edge`` overrides the grid's cell edge (it never changes a result)."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self.device = dev
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib.prg_icp_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_icp_create, _lib.lib.prg_icp_destroy, device)
         self.n_source = 0
         self.n_target = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib.prg_icp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
 
     def set_target(self, points, normals=None, cell_edge=None):
         pts = _as_rows(points, "target", 3)

@@ -23,7 +23,7 @@ from scipy.optimize import minimize
 
 from . import cost_functions as cf
 from . import features as ft
-from .cpd import _as_points
+from ._lib import as_points as _as_points
 from .svm import OneClassSVM
 from .log import log
 

@@ -29,23 +29,11 @@ import numpy as np
 
 from . import _lib
 from . import dist as pdist
-from .engine import _current_device_and_stream
 
 MAX_ATTRIBUTES = 64
 MAX_CELLS = 1 << 21
 
 VoxelDownSample = collections.namedtuple("VoxelDownSample", ["points", "normals", "attributes", "counts", "first", "inverse"])
-
-
-def _as_cloud(points):
-    pts = np.ascontiguousarray(np.asarray(getattr(points, "points", points)), dtype=np.float64)
-    if pts.ndim != 2 or pts.shape[1] not in (2, 3):
-        raise ValueError("points must be (n, 2) or (n, 3), got shape %s" % (pts.shape,))
-    if pts.shape[0] < 1:
-        raise ValueError("points must hold at least one point")
-    if not np.all(np.isfinite(pts)):
-        raise ValueError("points contains NaN or infinity")
-    return pts
 
 
 def _as_channel(a, name, n, cols, max_cols=None):
@@ -77,34 +65,19 @@ def _single_process(what):
                                   % (what, pdist.world()[1]))
 
 
-class VoxelPlan(object):
+class VoxelPlan(_lib.Handle):
     """One ``prg_voxel`` handle: a cloud on one device / stream and the stages of the down-sampling.  A plan can be run
     again with other data or another voxel size."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self.device = dev
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib.prg_voxel_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_voxel_create, _lib.lib.prg_voxel_destroy, device)
         self.n = 0
         self.dim = 0
         self.n_channels = 0
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib.prg_voxel_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
-
     def set_data(self, points):
         """The cloud (n, 2) or (n, 3); the channels of an earlier cloud go."""
-        points = _as_cloud(points)
+        points = _lib.as_cloud(points, "points", (2, 3))
         _lib.check(_lib.lib.prg_voxel_set_data(self._h, _lib.ptr(points), points.shape[0], points.shape[1]))
         self.n, self.dim = points.shape
         self.n_channels = 0
@@ -194,7 +167,7 @@ def voxel_down_sample(points, voxel_size, normals=None, attributes=None, unit_no
         first (V,) int32: the smallest original index in the voxel, inverse (n,) int32: the voxel row of every input
         point)``.  Voxels are in ascending cell order (x, then y, then z).
     """
-    pts = _as_cloud(points)
+    pts = _lib.as_cloud(points, "points", (2, 3))
     n, d = pts.shape
     v = _check_voxel_size(voxel_size)
     if normals is None and not isinstance(points, np.ndarray) and hasattr(points, "points"):
@@ -240,7 +213,7 @@ def _pad3(pts):
 
 
 def _filter_inputs(points, normals, attributes):
-    pts = _as_cloud(points)
+    pts = _lib.as_cloud(points, "points", (2, 3))
     n, d = pts.shape
     if normals is None and not isinstance(points, np.ndarray) and hasattr(points, "points"):
         own = getattr(points, "normals", None)

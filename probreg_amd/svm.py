@@ -20,7 +20,6 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .engine import _current_device_and_stream
 from .features import Feature
 from .log import log
 
@@ -34,28 +33,13 @@ def working_set_size():
     return int(q.value)
 
 
-class OcsvmPlan(object):
+class OcsvmPlan(_lib.Handle):
     """One ``prg_ocsvm`` handle: a cloud on one device / stream, its solve and the solution."""
 
     def __init__(self, device=None):
-        _lib.require_gpu()
-        dev, st = _current_device_and_stream(device)
-        self.device = dev
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib.prg_ocsvm_create(ctypes.byref(self._h), dev, ctypes.c_void_p(st)))
+        super().__init__(_lib.lib.prg_ocsvm_create, _lib.lib.prg_ocsvm_destroy, device)
         self.n = 0
         self.dim = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib.prg_ocsvm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
 
     def set_data(self, data):
         data = np.ascontiguousarray(data, dtype=np.float64)

@@ -9,6 +9,12 @@ test_gmmtree_stages_gpu.test_reused_handle_gives_a_fresh_handles_bytes): these s
 A = 300 points, B = 70 points: several cells of the search grid, several 64-point chunks, and component counts below
 and above one 256-thread block.  What the stages compute is checked against the oracles by test_fpfh_gpu,
 test_gmmfit_stages_gpu, test_gmmtree_stages_gpu and test_ocsvm_gpu; this file pins what re-creation must not change.
+
+The other seven plan classes (the CPD plan, the CPD batch, the FilterReg plan, the stand-alone lattice, the RANSAC plan, the
+voxel plan and the ICP plan) get the life cycle every handle shares (``_lib.Handle`` over csrc/plan_base.h) on a 64-point cloud
+(the batch: 4 problems of 64): close twice; a device index one past the last is a ValueError that leaves no handle; a getter
+before any data is the handle's own state error; and one tiny run on a handle created after the first was closed gives the
+first run's bytes (none of these stages adds floating-point numbers in arrival order: the lattice splats in fixed point).
 """
 import numpy as np
 import pytest
@@ -131,3 +137,177 @@ def test_ocsvm_plan():
         return out
 
     check_reuse(svm.OcsvmPlan, run)
+
+
+# ---- the life cycle of the other seven plan classes -------------------------------------------------------------------------
+N_TINY = 64
+
+
+def tiny_pair():
+    from probreg_amd import synthetic
+
+    src, tgt, _ = synthetic.rigid_pair(N_TINY, seed=41)
+    return src, tgt
+
+
+def check_lifecycle(cls, init, unset_getter, unset_message, run):
+    """init(obj, device) constructs ``obj`` in place (device None: the current one); unset_getter(plan) reads a result that a
+    new handle does not have; run(plan) -> [(name, array or scalar)] of one tiny run."""
+    from probreg_amd import _lib
+
+    def make():
+        plan = cls.__new__(cls)
+        init(plan, None)
+        return plan
+
+    plan = make()
+    assert plan._h
+    plan.close()
+    assert not plan._h
+    plan.close()
+    refused = cls.__new__(cls)
+    with pytest.raises(ValueError, match="out of range"):
+        init(refused, _lib.device_count())
+    assert not getattr(refused, "_h", None)
+    refused.close()
+    plan = make()
+    try:
+        with pytest.raises(_lib.ProbregHipError, match=unset_message) as info:
+            unset_getter(plan)
+        assert "status %d" % _lib.PRG_ERR_STATE in str(info.value)
+        first = as_bytes(run(plan))
+    finally:
+        plan.close()
+    again = make()
+    try:
+        second = as_bytes(run(again))
+    finally:
+        again.close()
+    assert [o[0] for o in first] == [o[0] for o in second] and len(first) >= 1
+    for a, b in zip(first, second):
+        assert a == b, "%s differs on a handle created after the first was closed" % a[0]
+
+
+def test_cpd_plan_lifecycle():
+    from probreg_amd import _lib, engine
+
+    src, tgt = tiny_pair()
+
+    def run(plan):
+        plan.set_source(src.astype(np.float32))
+        plan.set_target(tgt.astype(np.float32))
+        plan.init_sums()
+        plan.init_params()
+        plan.iterate(_lib.PRG_TF_RIGID, True, 0.1, 5)
+        out = [("params", plan.get_params()), ("moments", plan.get_moments())]
+        plan.estep(0.1)
+        out += zip(("pt1", "p1", "px"), plan.get_estep())
+        return out
+
+    check_lifecycle(engine.CpdPlan, lambda p, d: p.__init__(device=d), lambda p: p.get_estep_pt1(),
+                    "no E-step has been run", run)
+
+
+def test_cpd_batch_plan_lifecycle():
+    from probreg_amd import _lib, engine, synthetic
+
+    pairs = [synthetic.rigid_pair(N_TINY, seed=50 + b)[:2] for b in range(4)]
+    srcs = [s - s.mean(axis=0) for s, _ in pairs]
+    tgts = [t - t.mean(axis=0) for _, t in pairs]
+
+    def run(plan):
+        plan.init()
+        plan.iterate(_lib.PRG_TF_RIGID, True, np.full(4, 0.1), np.full(4, -1.0), 5)
+        return list(zip(("params", "iterations"), plan.get_params()))
+
+    check_lifecycle(engine.CpdBatchPlan, lambda p, d: p.__init__(srcs, tgts, device=d), lambda p: p.get_params(),
+                    "prg_cpd_batch_init has not run", run)
+
+
+def test_filterreg_plan_lifecycle():
+    from probreg_amd import filterreg
+
+    src, tgt = tiny_pair()
+
+    def run(plan):
+        plan.set_source(src)
+        plan.set_target(tgt)
+        plan.set_state(np.identity(3), np.zeros(3), 0.05)
+        size, blur = plan.estep()
+        out = [("lattice size", size), ("blur", blur), ("mstep", plan.mstep(0.1, True, "pt2pt", 1.0e-4)),
+               ("state", plan.get_state())]
+        out += zip(("m0", "m1", "m2"), plan.get_estep(True))
+        return out
+
+    check_lifecycle(filterreg._Plan, lambda p, d: p.__init__(device=d), lambda p: p.get_estep(False),
+                    "no E-step has been run", run)
+
+
+def test_permutohedral_lifecycle():
+    from probreg_amd import _lib, gaussian_filtering as gf
+
+    src, _ = tiny_pair()
+    values = np.random.default_rng(7).uniform(0.0, 1.0, (N_TINY, 2))
+
+    def init(plan, device):  # (the class builds its lattice in the constructor and takes no device: the handle alone)
+        _lib.Handle.__init__(plan, _lib.lib.prg_ph_create, _lib.lib.prg_ph_destroy, device)
+
+    def run(plan):
+        plan.init(src / 0.2)
+        return [("lattice size", plan.get_lattice_size()), ("filtered", plan.filter(values))]
+
+    check_lifecycle(gf.Permutohedral, init, lambda p: p.get_lattice_size(), "lattice not initialised", run)
+
+
+def test_ransac_plan_lifecycle():
+    from probreg_amd import global_reg, synthetic
+
+    p = synthetic.surface(N_TINY, 43)
+    q = p @ synthetic.rot_zx(20.0, 10.0).T + np.array([0.1, -0.2, 0.05])
+
+    def run(plan):
+        plan.set_correspondences(p, q)
+        plan.build(5, 256)
+        out = list(zip(("triples", "pose", "valid"), plan.hypotheses()))
+        plan.score(0.05)
+        out += zip(("count", "sum"), plan.scores())
+        best = plan.best()
+        out += zip(("best index", "best count", "best sum", "best pose"), best)
+        out += zip(("refined pose", "refined count", "refined sum", "inliers"), plan.refine(best[3], 0.05))
+        return out
+
+    check_lifecycle(global_reg.RansacPlan, lambda plan, d: plan.__init__(device=d), lambda plan: plan.scores(),
+                    "prg_ransac_score first", run)
+
+
+def test_voxel_plan_lifecycle():
+    from probreg_amd import preprocess
+
+    src, _ = tiny_pair()
+
+    def run(plan):
+        plan.set_data(src)
+        plan.run(0.2)
+        return [("count", plan.count()), ("keys", plan.keys()), ("order", plan.order()), ("rows", plan.rows()),
+                ("means", plan.means()), ("counts", plan.counts()), ("first", plan.first()), ("inverse", plan.inverse())]
+
+    check_lifecycle(preprocess.VoxelPlan, lambda p, d: p.__init__(device=d), lambda p: p.count(), "prg_voxel_run first", run)
+
+
+def test_icp_plan_lifecycle():
+    from probreg_amd import icp
+
+    src, tgt = tiny_pair()
+
+    def run(plan):
+        plan.set_target(tgt)
+        plan.set_source(src)
+        plan.search(0.5)
+        out = list(zip(("index", "d2"), plan.matches()))
+        out += zip(("knn index", "knn d2", "knn count"), plan.knn(4))
+        plan.iterate("point_to_point", 0.5, 5)
+        state = plan.state()
+        out += [("pose", state.pose), ("count", state.count), ("sum", state.sum), ("iterations", state.n_iter)]
+        return out
+
+    check_lifecycle(icp.IcpPlan, lambda p, d: p.__init__(device=d), lambda p: p.matches(), "no target", run)
