@@ -864,6 +864,29 @@ int prg_icp_outlier_radius(prg_icp* h, double r, int nb_points);
  * be NULL.  Synchronises. */
 int prg_icp_get_outlier(prg_icp* h, unsigned char* keep_host, double* score_host, double* stat_host);
 
+/* ---- Kernel fields: a non-rigid result evaluated at any points ------------------------------------------------------------
+ * f(x)_c = sum_m k(|x - y_m|^2) w_mc over M control points y_m (D = 2 or 3) with C <= 4 weight columns, for Q query points x
+ * that need not be the control points: the displacement field behind NonRigidTransformation (gaussian), CombinedTransformation
+ * (imq) and TPSTransformation (tps), which the reference only ever evaluates through an M x M or Q x K float32 kernel matrix.
+ * fp64 throughout (differences, d2, kernel, sums), straight from the caller's coordinates; control points in ascending index
+ * in slabs of 65 536 whose sums are added in ascending order, no floating-point atomics: byte-identical from run to run and
+ * independent of Q, of the launch geometry and of the batching of the queries (csrc/field.hip). */
+#define PRG_FIELD_GAUSSIAN 0 /* exp(-d2 / (2 param)), param = beta > 0: math_utils.rbf_kernel (2 beta, not 2 beta^2) */
+#define PRG_FIELD_IMQ 1      /* 1 / sqrt(d2 + param), param = c > 0: math_utils.inverse_multiquadric_kernel */
+#define PRG_FIELD_TPS 2      /* math_utils.tps_kernel: D = 2: d2 log(d2) / 2 where d2 > 1e-9, else 0; D = 3: -sqrt(d2) */
+typedef struct prg_field prg_field;
+/* One field on one device / stream; the control points can be set again.  Replaces: none in the reference (as every
+ * prg_field_* entry point below); the nearest is `np.dot(kernel(points, control), weights)` of transformation.py:81-160. */
+int prg_field_create(prg_field** out, int device, void* hip_stream);
+int prg_field_destroy(prg_field* h);
+/* The control points (m x d float64) and their weights (m x c float64), finite, host or device, 1 <= m < 2^31, d = 2 or 3,
+ * 1 <= c <= 4; kind and param as above (param is ignored for PRG_FIELD_TPS).  Packed once into [y, w] rows.  Synchronises. */
+int prg_field_set_control(prg_field* h, const double* control_hd, const double* weights_hd, int64_t m, int d, int c, int kind,
+                          double param);
+/* f at q points (q x d float64, finite, host or device, 0 <= q < 2^31) -> out_host q x c float64.  With more than 65 536
+ * control points the queries go through in batches that keep the slab sums within 64 MB.  Synchronises. */
+int prg_field_evaluate(prg_field* h, const double* points_hd, int64_t q, double* out_host);
+
 #ifdef __cplusplus
 }
 #endif

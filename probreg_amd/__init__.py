@@ -14,7 +14,7 @@ from .version import __version__
 
 _SUBMODULES = ("cpd", "filterreg", "transformation", "math_utils", "gauss_transform", "gaussian_filtering",
                "cost_functions", "dist", "engine", "synthetic", "bcpd",
-               "gmmtree", "features", "l2dist_regs", "se3_op", "global_reg", "preprocess", "icp")
+               "gmmtree", "features", "l2dist_regs", "se3_op", "global_reg", "preprocess", "icp", "field")
 
 
 def __getattr__(name):

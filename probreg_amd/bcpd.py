@@ -303,7 +303,14 @@ class CombinedBCPD(BayesianCoherentPointDrift):
         s2 = np.einsum("md,md->", px, y_hat)
         s3 = nu_v @ np.einsum("md,md->m", y_hat, y_hat)
         sigma2 = (s1 - 2.0 * s2 + s3) / (n_p * dim) + scale ** 2 * sigma2_m
-        return MstepResult(tf.CombinedTransformation(rot, t, scale, v_hat), u_hat, sigma_diag, alpha, sigma2)
+        # the continuous field behind v_hat: Sigma^-1 v_hat = s2s2 nu o residual with Sigma^-1 = lmd G^-1 + s2s2 diag(nu) gives
+        # v_hat = G W_b, W_b = (s2s2 / lmd) nu o (residual - v_hat), with no solve (and for the singular G = F F^T of the
+        # low-rank solver alike).  G is the plan's kernel: inverse multiquadric, c = 1, on the float32 centred source.
+        nu_s = np.asarray(nu_v if nu is None else nu, dtype=np.float64)
+        w_b = (s2s2 / self.lmd) * nu_s[:, None] * (residual - v_hat)
+        control = (source - self._cy).astype(np.float32).astype(np.float64) + self._cy
+        return MstepResult(tf.CombinedTransformation(rot, t, scale, v_hat, field=(control, w_b, 1.0)), u_hat, sigma_diag,
+                           alpha, sigma2)
 
 
 def registration_bcpd(source, target, w=0.0, maxiter=50, tol=0.001, callbacks=(), **kwargs):

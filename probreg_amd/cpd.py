@@ -473,7 +473,7 @@ class NonRigidCPD(CoherentPointDrift):
         self._plan, self._origin = _nonrigid_plan(self._source, self._beta, self._device, self._solver_mode, self._factor_tol)
         self._source_uploaded = True
         self._tf_obj = tf.NonRigidTransformation(None, self._source, self._beta, _plan=self._plan,
-                                                 _plan_points=self._source - self._origin)
+                                                 _plan_points=self._source - self._origin, _origin=self._origin)
 
     def set_source(self, source):
         self._source = _as_points(source)

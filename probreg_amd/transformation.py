@@ -3,6 +3,8 @@
 These are small host-side value objects (a 3x3 matrix, a vector, an M x D weight matrix); the
 per-iteration transform of the *source cloud* inside the EM loop runs fused on the GPU
 (``k_transform_linear`` / ``k_gw`` in csrc/), not through these classes.
+``transform`` keeps the reference's contract (a non-rigid result moves the control points it was fitted on); ``warp`` moves any
+points: the non-rigid classes evaluate their continuous displacement field on the GPU (``probreg_amd.field``).
 ``DeformableKinematicModel`` (transformation.py:163-212) skins its points on the GPU (``prg_dq_skin``).
 """
 import abc
@@ -28,6 +30,38 @@ class Transformation(abc.ABC):
     @abc.abstractmethod
     def _transform(self, points):
         return points
+
+    def warp(self, points):
+        """Move any points.  For a transformation that is a function of the point alone (rigid, affine, the kinematic model)
+        this is ``transform``; the non-rigid results override it with their continuous displacement field."""
+        return self.transform(points)
+
+
+def _field(obj, control, weights, kernel, param=None, device=None):
+    """The ``field.KernelField`` a transformation object keeps between ``warp`` calls, holding the control points and weights
+    given: created on the first call, set again on every later one (an EM callback sees new weights every iteration),
+    released by ``_close_field``."""
+    from .field import KernelField
+
+    field = obj.__dict__.get("_warp_field")
+    if field is None:
+        field = obj.__dict__["_warp_field"] = KernelField(control, weights, kernel, param, device)
+    else:
+        field.set_control(control, weights, kernel, param)
+    return field
+
+
+def _close_field(obj):
+    field = obj.__dict__.pop("_warp_field", None)
+    if field is not None:
+        field.close()
+
+
+def _warp_points(points, dim):
+    """The points of a ``warp`` call as a finite float64 (n, dim) array (ValueError otherwise); n = 0 is fine."""
+    from . import _lib
+
+    return _lib.as_cloud(points, "points", (dim,), min_points=0)
 
 
 class RigidTransformation(Transformation):
@@ -65,15 +99,41 @@ class AffineTransformation(Transformation):
 
 class CombinedTransformation(Transformation):
     """x -> scale * rot @ (x + v) + t : non-rigid displacement first, similarity second (reference
-    transformation.py:105-121, the result type of BCPD).  ``v`` is one row per point (or 0)."""
+    transformation.py:105-121, the result type of BCPD).  ``v`` is one row per point (or 0).
 
-    def __init__(self, rot=np.identity(3), t=np.zeros(3), scale=1.0, v=0.0):
+    ``field`` = ``(control, weights, c)``: the continuous displacement ``v(x) = sum_m weights_m / sqrt(|x - control_m|^2 + c)``
+    that ``v`` samples at the control points; ``CombinedBCPD`` attaches it, and ``warp`` needs it to move other points."""
+
+    def __init__(self, rot=np.identity(3), t=np.zeros(3), scale=1.0, v=0.0, field=None):
         super(CombinedTransformation, self).__init__()
         self.rigid_trans = RigidTransformation(rot, t, scale)
         self.v = v
+        self.field = field
 
     def _transform(self, points):
         return self.rigid_trans._transform(points + self.v)
+
+    def warp(self, points):
+        """``scale * rot @ (x + v(x)) + t`` for any points ``x``, ``v(x)`` evaluated on the GPU in fp64."""
+        if self.field is None:
+            if np.any(np.asarray(self.v) != 0.0):
+                raise ValueError("CombinedTransformation.warp: this object holds its displacement `v` per control point only "
+                                 "and no `field=(control, weights, c)` to evaluate it elsewhere (CombinedBCPD attaches one); "
+                                 "use transform() on the control points.")
+            return self.rigid_trans._transform(np.asarray(points))
+        control, weights, c = self.field
+        pts = _warp_points(points, np.asarray(control).shape[1])
+        return self.rigid_trans._transform(pts + _field(self, control, weights, "imq", c).evaluate(pts))
+
+    def close(self):
+        """Release the GPU handle that ``warp`` keeps."""
+        _close_field(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown: the library may be gone already
+            pass
 
 
 class NonRigidTransformation(Transformation):
@@ -84,13 +144,15 @@ class NonRigidTransformation(Transformation):
     factor, as the matrix itself); ``.g`` evaluates / downloads the M x M float32 matrix on first access (M*M*4 bytes).
     """
 
-    def __init__(self, w, points, beta=2.0, xp=np, _plan=None, _plan_points=None):
+    def __init__(self, w, points, beta=2.0, xp=np, _plan=None, _plan_points=None, _origin=None):
         super(NonRigidTransformation, self).__init__(xp)
         self._points = np.asarray(points)
         self._beta = beta
         self._plan = _plan
-        # the control points as the plan holds them (NonRigidCPD shifts far-from-origin clouds before the float32 upload)
+        # the control points as the plan holds them (NonRigidCPD shifts far-from-origin clouds before the float32 upload):
+        # _plan_points = points - _origin
         self._plan_points = self._points if _plan_points is None else np.asarray(_plan_points)
+        self._origin = np.zeros(self._points.shape[1]) if _origin is None else np.asarray(_origin, dtype=np.float64)
         self._g = None
         self.w = w
 
@@ -106,10 +168,12 @@ class NonRigidTransformation(Transformation):
         return self._g
 
     def close(self):
-        """Release the GPU plan an explicit-array M-step (``NonRigidCPD._maximization_step``) cached on this object."""
+        """Release the GPU plan an explicit-array M-step (``NonRigidCPD._maximization_step``) cached on this object, and
+        the handle that ``warp`` keeps."""
         cache = self.__dict__.pop("_mstep_plan", None)
         if cache is not None:
             cache[0].close()
+        _close_field(self)
 
     def __del__(self):
         try:
@@ -125,6 +189,19 @@ class NonRigidTransformation(Transformation):
             disp = self._plan.nonrigid_apply() - self._plan_points.astype(np.float32).astype(np.float64)
             return np.asarray(points) + disp
         return points + np.dot(self.g, self.w)
+
+    def field_control(self):
+        """The control points of the displacement field, in the frame ``x - _origin``: the float32-rounded cloud the kernel
+        matrix was built from, as float64."""
+        return np.asarray(self._plan_points).astype(np.float32).astype(np.float64)
+
+    def warp(self, points):
+        """``x + sum_m exp(-|x - y_m|^2 / (2 beta)) w_m`` for any points ``x``, on the GPU in fp64.  The ``y_m`` are the
+        control points as the kernel matrix of ``transform`` saw them; the queries are shifted into their frame in fp64."""
+        pts = _warp_points(points, self._points.shape[1])
+        w = np.asarray(self.w, dtype=np.float64)
+        device = None if self._plan is None else self._plan.device
+        return pts + _field(self, self.field_control(), w, "gaussian", self._beta, device).evaluate(pts - self._origin)
 
 
 def _tps_kernel(x, y):
@@ -162,6 +239,32 @@ class TPSTransformation(Transformation):
     def _transform(self, points):
         basis, _ = self.prepare(points)
         return self.transform_basis(basis)
+
+    def field_weights(self):
+        """``N v``: the warp coefficients per control point (K, dim), ``N`` the null-space basis of ``prepare``."""
+        ctrl = np.asarray(self.control_pts, dtype=np.float64)
+        u, _, _ = np.linalg.svd(np.c_[np.ones((ctrl.shape[0], 1)), ctrl])
+        return np.dot(u[:, ctrl.shape[1] + 1:], np.asarray(self.v, dtype=np.float64))
+
+    def warp(self, points):
+        """``[1 x] a + sum_k U(|x - c_k|) (N v)_k`` with the kernel sum on the GPU in fp64: no Q x K matrix is formed.  An
+        object built with a kernel of its own has no device counterpart and goes through ``transform``."""
+        if self._kernel is not _tps_kernel:
+            return self.transform(points)
+        ctrl = np.asarray(self.control_pts, dtype=np.float64)
+        pts = _warp_points(points, ctrl.shape[1])
+        a = np.asarray(self.a, dtype=np.float64)
+        return a[0] + np.dot(pts, a[1:]) + _field(self, ctrl, self.field_weights(), "tps").evaluate(pts)
+
+    def close(self):
+        """Release the GPU handle that ``warp`` keeps."""
+        _close_field(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown: the library may be gone already
+            pass
 
 
 # ---- dual quaternions (DESIGN.md section 3.10): 8 doubles (r_w, r_x, r_y, r_z, d_w, d_x, d_y, d_z) -------------------
