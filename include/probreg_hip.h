@@ -474,6 +474,16 @@ int prg_fr_mstep(prg_filterreg* h, double w, int update_sigma2, double min_sigma
 /* The device state (synchronises): out_host[20] = the 18 entries of prg_fr_mstep, then [18] q of the last M-step that had
  * anything to fit (an all-zero one sets [13] to NaN and [16] to 0), [19] the number of such M-steps since prg_fr_set_state. */
 int prg_fr_get_state(prg_filterreg* h, double* out_host);
+/* How the last prg_fr_estep / prg_fr_kinematic_estep on the plan chose between the blurred and the non-blurred lattice
+ * (filterreg.py:90-91; the choice itself is the reference's every time).  Host bookkeeping, nothing is launched or copied.
+ * out4[0] route: 1 blurred lattice built first and kept, 2 built first and rejected (the previous E-step blurred, or the
+ *   threshold N * alpha is negative or >= 2e9), 3 non-blurred lattice built while a 1/16 sample proved the blurred one too
+ *   large, 4 blurred build with the threshold stopped after its first sixteenth, 5 that build completed and kept,
+ *   6 completed and rejected;
+ * out4[1] lattice builds of the E-step (1..3); out4[2] hash-table attempts of its last build (2: retried at full capacity);
+ * out4[3] 1 if routes 3..6 looked at a sixteenth of the points first (M + N >= 4096), else 0.
+ * PRG_ERR_STATE before the first E-step, and after one that failed.  No reference counterpart: tests and diagnosis. */
+int prg_fr_last_route(prg_filterreg* h, int* out4);
 
 /* Point-to-plane objective (filterreg.py:101-105, 183-186): target normals (n x 3 float64, NULL clears) add a
  * 3-channel filter `nx` to the E-step; prg_fr_mstep_pt2pl solves the 6 x 6 twist system

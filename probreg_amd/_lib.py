@@ -152,6 +152,7 @@ SIGNATURES = {
     "prg_fr_get_estep": [_vp, _vp, _vp, _vp],
     "prg_fr_mstep": [_vp, _d, _i, _d, _vp],
     "prg_fr_get_state": [_vp, _vp],
+    "prg_fr_last_route": [_vp, _c.POINTER(_i)],
     "prg_fr_set_target_normals": [_vp, _vp],
     "prg_fr_get_nx": [_vp, _vp],
     "prg_fr_mstep_pt2pl": [_vp, _d, _i, _d, _vp],

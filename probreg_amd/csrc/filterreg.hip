@@ -51,6 +51,7 @@ struct prg_filterreg {
     bool have_src = false, have_tgt = false, have_estep = false;
     FrFeat prod;             // feature producer handed to the embedding kernels
     int last_blur = 1;       // with_blur of the previous E-step: which lattice the next one tries first
+    int route[4] = {0, 0, 0, 0};  // how the last E-step chose its lattice (prg_fr_last_route); route[0] == 0: none yet
     // deformable kinematic model (filterreg_kinematic.hip, reached through fr_plan.h)
     std::vector<int> src_order;            // host copy of src_perm (empty: caller's order)
     const double* src_override = nullptr;  // non-null during prg_fr_kinematic_estep: the skinned source stands in for `src`
@@ -100,7 +101,8 @@ __device__ void fr_finish_body(const double* __restrict__ part, int nblk, int di
 // one launch, one dependent-launch gap and one 22 MB re-read less per EM iteration.  The Kabsch finish is a launch of its own
 // again (k_fr_finish): folded into the last workgroup of this kernel (round 3) it doubled the kernel's registers (200 VGPRs:
 // 2 waves per SIMD for the 512 workgroups that never run it) and cost 57 us where the two launches take 16 + 12.
-template <bool SLICE>
+// M1SEQ (2-D clouds): the reference filters m1 as y.shape[1] = 2 channels, and at most two channels go through seqCompute.
+template <bool SLICE, bool M1SEQ = false>
 __global__ __launch_bounds__(kBlock) void k_fr_terms(const float* __restrict__ vout_in, float* __restrict__ vout_w, int ch,
                                                      const int* __restrict__ offset, const float* __restrict__ bary,
                                                      const float* __restrict__ vals, float alpha,
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void k_fr_terms(const float* __restrict__ v
     // grid-stride: a few hundred workgroups, each thread sums several points before the (32-component) reduction
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
         float f[5];
-        if (SLICE) {  // (ch == 5, seq_mask 0x11: channels 0 and 4 follow seqCompute, 1..3 sseCompute - see k_slice)
+        if (SLICE) {  // (ch == 5, fr_seq_mask: channels 0 and 4 follow seqCompute, 1..3 sseCompute unless M1SEQ - see k_slice)
             const int d1 = dim + 1;
 #pragma unroll
             for (int k = 0; k < 5; ++k) f[k] = 0.f;
@@ -125,9 +127,14 @@ __global__ __launch_bounds__(kBlock) void k_fr_terms(const float* __restrict__ v
                 const float* __restrict__ v = vals + (int64_t)o * 5;
                 const float wa = __fmul_rn(w, alpha);
                 f[0] = __fadd_rn(f[0], __fmul_rn(__fmul_rn(w, v[0]), alpha));
-                f[1] = __fadd_rn(f[1], __fmul_rn(wa, v[1]));
-                f[2] = __fadd_rn(f[2], __fmul_rn(wa, v[2]));
-                f[3] = __fadd_rn(f[3], __fmul_rn(wa, v[3]));
+                if (M1SEQ) {  // (channel 3 is zero in 2-D)
+                    f[1] = __fadd_rn(f[1], __fmul_rn(__fmul_rn(w, v[1]), alpha));
+                    f[2] = __fadd_rn(f[2], __fmul_rn(__fmul_rn(w, v[2]), alpha));
+                } else {
+                    f[1] = __fadd_rn(f[1], __fmul_rn(wa, v[1]));
+                    f[2] = __fadd_rn(f[2], __fmul_rn(wa, v[2]));
+                    f[3] = __fadd_rn(f[3], __fmul_rn(wa, v[3]));
+                }
                 f[4] = __fadd_rn(f[4], __fmul_rn(__fmul_rn(w, v[4]), alpha));
             }
 #pragma unroll
@@ -697,12 +704,18 @@ int prg_fr_set_state(prg_filterreg* h, const double* rot9, const double* t3, dou
     return PRG_OK;
 }
 
+// Which channels of the fused filter pass follow the reference's seqCompute (bit k set) and which its sseCompute: the
+// reference filters m0 and m2 alone (one channel: seqCompute) and m1 as one filter of y.shape[1] channels - three take
+// sseCompute, the two of a 2-D cloud seqCompute (permutohedral.cpp picks seqCompute up to two channels).  Normals: sseCompute.
+static unsigned fr_seq_mask(const prg_filterreg* h) { return h->D == 2 ? 0x1Fu : 0x11u; }
+
 int prg_fr_estep(prg_filterreg* h, double alpha, int* lattice_size, int* with_blur) {
     PRG_REQUIRE(h && h->have_src && h->have_tgt, PRG_ERR_STATE, "prg_fr_estep: clouds not set");
     PRG_ENTER(h->L.device);
     const int64_t tot = h->M + h->N;
     // features are produced inside the embedding kernels (transform, division by sigma, float32 cast)
     h->have_estep = false;  // (a failure below leaves no half-built lattice behind for an M-step)
+    h->route[0] = 0;
     h->prod = FrFeat{h->src_override ? h->src_override : h->src.p, h->tgt.p, h->state.p, h->ts.p, h->M, h->D};
     h->L.prod = &h->prod;
     h->L.ref_pos = h->ref_pos.p;
@@ -716,30 +729,53 @@ int prg_fr_estep(prg_filterreg* h, double alpha, int* lattice_size, int* with_bl
     const double thr = (double)h->N * alpha;
     const int64_t decide = thr >= 0.0 && thr < 2.0e9 ? (int64_t)floor(thr) : -1;
     bool done = false;
+    int route = 0, builds = 0;  // (prg_fr_last_route)
     if (h->last_blur == 0 && decide >= 0 && tot >= 4096) {
         PRG_TRY(prg::lat_side_stage(&h->L, tot, h->D));
         PRG_TRY(prg::lat_build(&h->L, tot, h->D, 0));
+        ++builds;
         if (h->L.side_overflow == 0 && h->L.side_size > decide) {
             blur = 0;
             done = true;
+            route = 3;
         }
     }
     if (!done) {
-        PRG_TRY(prg::lat_build(&h->L, tot, h->D, 1, h->last_blur == 1 ? -1 : decide));
-        if (!h->L.built || (double)h->L.size > thr) {
+        const int64_t decide_above = h->last_blur == 1 ? -1 : decide;
+        PRG_TRY(prg::lat_build(&h->L, tot, h->D, 1, decide_above));
+        ++builds;
+        const bool rejected = !h->L.built || (double)h->L.size > thr;
+        // Route 4 needs the first sixteenth alone to exceed the threshold.  With tot >= 4096 that sixteenth is the side
+        // stage's sample under the same scaling, which has just failed to exceed it - so only an overflow of the side table
+        // (a probe chain of more than 4096 slots in a table a quarter full at the most) leads here.
+        if (decide_above >= 0) route = !h->L.built ? 4 : (rejected ? 6 : 5);
+        else route = rejected ? 2 : 1;
+        if (rejected) {
             blur = 0;
             PRG_TRY(prg::lat_build(&h->L, tot, h->D, 0));
+            ++builds;
         }
     }
     h->last_blur = blur;
     // one fused 5-channel pass: channels 0 (m0) and 4 (m2) are single-channel filters in the reference
-    // (seqCompute arithmetic), channels 1..3 (m1) its 3-channel filter (sseCompute arithmetic)
+    // (seqCompute arithmetic), channels 1..3 (m1) its 3-channel filter (sseCompute arithmetic) - fr_seq_mask
     // (point-to-point plans, ch == 5: the slice step waits for its consumer - the M-step slices inside its terms kernel)
     h->slice_pending = h->ch == 5;
-    PRG_TRY(prg::lat_filter(&h->L, h->vin.p, h->ch, h->M, h->M, 0x11u, h->vout.p, h->slice_pending));  // normals (ch 5..7): 3-channel filter
+    PRG_TRY(prg::lat_filter(&h->L, h->vin.p, h->ch, h->M, h->M, fr_seq_mask(h), h->vout.p, h->slice_pending));  // normals (ch 5..7): 3-channel filter
     if (lattice_size) *lattice_size = h->L.size;
     if (with_blur) *with_blur = blur;
     h->have_estep = true;
+    h->route[1] = builds;
+    h->route[2] = h->L.attempts;
+    h->route[3] = route >= 3 && tot >= 4096 ? 1 : 0;  // the decision looked at a sixteenth of the points first
+    h->route[0] = route;
+    return PRG_OK;
+}
+
+int prg_fr_last_route(prg_filterreg* h, int* out4) {
+    PRG_REQUIRE(h && out4, PRG_ERR_INVALID, "prg_fr_last_route: NULL argument");
+    PRG_REQUIRE(h->route[0] != 0, PRG_ERR_STATE, "prg_fr_last_route: no E-step has been run");
+    for (int i = 0; i < 4; ++i) out4[i] = h->route[i];
     return PRG_OK;
 }
 
@@ -773,7 +809,7 @@ extern "C" {
 static int fr_flush_slice(prg_filterreg* h) {
     if (!h->slice_pending) return PRG_OK;
     h->slice_pending = false;
-    return prg::lat_slice(&h->L, h->L.pend_vals, h->L.pend_alpha, h->ch, h->M, 0x11u, h->vout.p);
+    return prg::lat_slice(&h->L, h->L.pend_vals, h->L.pend_alpha, h->ch, h->M, fr_seq_mask(h), h->vout.p);
 }
 
 // columns [col0, col0 + ncols) of the filtered values, one row per source point in the CALLER's order -> out_hd
@@ -821,8 +857,12 @@ int prg_fr_mstep(prg_filterreg* h, double w, int update_sigma2, double min_sigma
     const int nblk = (int)h->part_blocks;
     if (h->slice_pending) {  // slice + terms in one launch (the values still go to vout for prg_fr_get_estep)
         h->slice_pending = false;
-        k_fr_terms<true><<<nblk, kBlock, 0, st>>>(nullptr, h->vout.p, 5, h->L.pslot.p, h->L.bary.p, h->L.pend_vals, h->L.pend_alpha,
-                                                  h->ts.p, h->M, h->D, wfac, h->state.p, h->part.p);
+        if (h->D == 2)
+            k_fr_terms<true, true><<<nblk, kBlock, 0, st>>>(nullptr, h->vout.p, 5, h->L.pslot.p, h->L.bary.p, h->L.pend_vals,
+                                                            h->L.pend_alpha, h->ts.p, h->M, h->D, wfac, h->state.p, h->part.p);
+        else
+            k_fr_terms<true><<<nblk, kBlock, 0, st>>>(nullptr, h->vout.p, 5, h->L.pslot.p, h->L.bary.p, h->L.pend_vals, h->L.pend_alpha,
+                                                      h->ts.p, h->M, h->D, wfac, h->state.p, h->part.p);
     } else {
         k_fr_terms<false><<<nblk, kBlock, 0, st>>>(h->vout.p, nullptr, h->ch, nullptr, nullptr, nullptr, 0.f, h->ts.p, h->M, h->D, wfac,
                                                    h->state.p, h->part.p);

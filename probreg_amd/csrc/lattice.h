@@ -47,6 +47,7 @@ struct Lattice {
     // build starts by taking the next generation instead of clearing the table (gen 0 = freshly zeroed memory)
     unsigned gen = 0, gen2 = 0;
     int prev_size[2] = {0, 0};          // last lattice size without / with blur: sizes the next hash table
+    int attempts = 0;                   // table attempts of the last d <= 3 build (2: it was retried at full capacity)
     HostBuf<double> pinned;             // 64 doubles of pinned host memory: small device->host read-backs (a copy
                                         // into pageable memory costs ~100 us of staging, this one a few us)
     bool built = false;                 // false after a decision-only build that stopped early (lat_build)

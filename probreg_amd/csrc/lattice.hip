@@ -1063,6 +1063,7 @@ int lat_build(Lattice* L, int64_t n, int d, int with_blur, int64_t decide_above)
     L->seg_valid = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
         L->cap_used = capu;
+        L->attempts = attempt + 1;
         PRG_TRY(next_generation(L->tkeys.p, cap, &L->gen, st));
         if (!L->count_clean) PRG_HIP(hipMemsetAsync(L->count.p, 0, 2 * sizeof(int), st));  // (normally left clean by k_resolve)
         L->count_clean = false;

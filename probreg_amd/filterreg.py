@@ -108,6 +108,12 @@ class _Plan(_lib.Handle):
         check(lib.prg_fr_get_state(self._h, ptr(out)))
         return out
 
+    def last_route(self):
+        """(route, lattice builds, table attempts of the last build, sampled) of the last E-step (prg_fr_last_route)."""
+        out = (ctypes.c_int * 4)()
+        check(lib.prg_fr_last_route(self._h, out))
+        return tuple(int(v) for v in out)
+
     # ---- deformable kinematic model (DESIGN.md section 3.10) ----
     def set_skinning(self, pairs, vals, n_nodes):
         pairs = np.ascontiguousarray(pairs, dtype=np.int32)
