@@ -873,6 +873,18 @@ int prg_icp_outlier_radius(prg_icp* h, double r, int nb_points);
  * stat_host 3 float64 (mu, s, thr), which must be NULL after the radius filter (its scores are prg_icp_get_counts).  Each may
  * be NULL.  Synchronises. */
 int prg_icp_get_outlier(prg_icp* h, unsigned char* keep_host, double* score_host, double* stat_host);
+/* DBSCAN of the source, which the caller has also set as the target, at the identity pose (csrc/icp_cluster.hip):
+ * c_i the radius count of eps, the point itself included; point i is core iff c_i >= min_points; the clusters are the connected
+ * components of the core points under d2 <= eps * eps, numbered 0, 1, ... in ascending order of their smallest core index; a
+ * point that is not core takes the cluster of its nearest core neighbour within eps, the minimum of (d2, index) (Open3D and
+ * scikit-learn: the cluster that reaches it first), or -1, noise, when it has none.  eps finite and > 0, min_points >= 1, as many
+ * target as source points.  Integer atomics only; independent of the grid, the launch geometry and the run.  Replaces: none in the
+ * reference; Open3D's cluster_dbscan(eps, min_points).  Enqueues only. */
+int prg_icp_dbscan(prg_icp* h, double eps, int min_points);
+/* The last prg_icp_dbscan: labels_host m int32 (-1: noise), core_host m bytes (1 core, 0 not), n_clusters_host one int32 and
+ * sizes_host n_clusters int32, the members of every cluster with its border points (its length is known from a first call with
+ * sizes_host NULL).  Each may be NULL.  The counts c_i are prg_icp_get_counts.  Synchronises. */
+int prg_icp_get_dbscan(prg_icp* h, int* labels_host, unsigned char* core_host, int* n_clusters_host, int* sizes_host);
 
 /* ---- Kernel fields: a non-rigid result evaluated at any points ------------------------------------------------------------
  * f(x)_c = sum_m k(|x - y_m|^2) w_mc over M control points y_m (D = 2 or 3) with C <= 4 weight columns, for Q query points x

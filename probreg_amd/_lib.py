@@ -258,6 +258,8 @@ SIGNATURES = {
     "prg_icp_outlier_statistical": [_vp, _i, _d],
     "prg_icp_outlier_radius": [_vp, _d, _i],
     "prg_icp_get_outlier": [_vp, _vp, _vp, _vp],
+    "prg_icp_dbscan": [_vp, _d, _i],
+    "prg_icp_get_dbscan": [_vp, _vp, _vp, _vp, _vp],
     "prg_field_create": [_pp, _i, _vp],
     "prg_field_destroy": [_vp],
     "prg_field_set_control": [_vp, _vp, _vp, _i64, _i, _i, _i, _d],

@@ -76,4 +76,38 @@ __host__ __device__ inline double shell_bound(int s, const CellGrid& g, double b
     return reach * reach + box2;
 }
 
+// The radius walk: every point that can lie within r of q goes to visit(p) exactly once (p: the point, its original index in
+// .w).  It runs on one level, the finest on which the cells that can hold such a point span at most kCountSpan + 1 an axis
+// (the last level otherwise).  Every point is in one cell of a level and every cell of the cube is visited once; on a hashed
+// level a bucket may hold points of other cells, which are left to their own cell.  The visitor decides d2 <= r r itself.  The
+// level loop is uniform.  The radius count and the DBSCAN link of the ICP plan are this walk with two visitors.
+template <class Visit>
+__host__ __device__ inline void radius_walk(const Levels& lv, const double (&q)[3], double r, Visit& visit) {
+    const double rho = r * kReach;
+    bool done = false;
+    for (int v = 0; v < lv.count; ++v) {
+        if (done) continue;
+        const CellGrid& g = lv.g[v];
+        int lo[3], hi[3];
+        clip_cells(q, rho, g, lo, hi);
+        const int span = greater(hi[0] - lo[0], greater(hi[1] - lo[1], hi[2] - lo[2]));
+        if (span > kCountSpan && v + 1 < lv.count) continue;
+        done = true;
+        const double4* __restrict__ sp = lv.sp[v];
+        const int2* __restrict__ cells = lv.cells[v];
+        for (int z = lo[2]; z <= hi[2]; ++z)
+            for (int y = lo[1]; y <= hi[1]; ++y)
+                for (int x = lo[0]; x <= hi[0]; ++x) {
+                    const int2 be = cells[cell_key(x, y, z, g)];
+                    for (int t = be.x; t < be.y; ++t) {
+                        const double4 p = sp[t];
+                        if (!g.dense && (cell_of(p.x, g.lo[0], g.edge) != x || cell_of(p.y, g.lo[1], g.edge) != y ||
+                                         cell_of(p.z, g.lo[2], g.edge) != z))
+                            continue;
+                        visit(p);
+                    }
+                }
+    }
+}
+
 }  // namespace prg

@@ -40,18 +40,8 @@ constexpr int kMaxK = kWave;    // one list entry per lane
 
 using prg::CellGrid;
 using prg::cell_key;
-using prg::cell_of;
 using prg::kReach;
 using prg::Levels;
-
-// source point m under the pose in the state
-__device__ __forceinline__ void moved_query(const double* __restrict__ state, const double* __restrict__ src, int64_t m,
-                                            double (&q)[3]) {
-    double pose[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pose[k] = state[kStPose + k];
-    moved(pose, src + m * 3, q);
-}
 
 __device__ __forceinline__ unsigned spread10(unsigned v) {  // 10 bits -> every third bit
     v &= 0x3ffu;
@@ -279,9 +269,19 @@ __global__ __launch_bounds__(kBlock) void k_icp_knn(Levels lv, const double* __r
     if (lane == 0) out_cnt[m] = b.cnt;
 }
 
-// c(q) = #{n : d2 <= r r}, r finite: one query per lane, on the finest level on which the cells that can hold such a point
-// span at most kCountSpan + 1 an axis (the last level otherwise).  Every point is in one cell of a level and every cell of the
-// cube is visited once; on a hashed level a bucket may hold points of other cells, which are left to their own cell.
+// d2 = (dx dx + dy dy) + dz dz <= r r: one more
+struct CountWithin {
+    double q[3];
+    double r2;
+    int count;
+
+    __device__ __forceinline__ void operator()(const double4& p) {
+        const double dx = p.x - q[0], dy = p.y - q[1], dz = p.z - q[2];
+        count += (dx * dx + dy * dy) + dz * dz <= r2 ? 1 : 0;
+    }
+};
+
+// c(q) = #{n : d2 <= r r}, r finite: one query per lane on the radius walk of grid_search.h.
 __global__ __launch_bounds__(kBlock) void k_icp_radius_count(Levels lv, const double* __restrict__ src,
                                                              const int* __restrict__ qorder, int64_t M,
                                                              const double* __restrict__ state, double r, double r2,
@@ -289,36 +289,12 @@ __global__ __launch_bounds__(kBlock) void k_icp_radius_count(Levels lv, const do
     const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (l >= M) return;
     const int m = qorder[l];
-    double q[3];
-    moved_query(state, src, m, q);
-    const double rho = r * kReach;
-    int count = 0;
-    bool done = false;
-    for (int v = 0; v < lv.count; ++v) {
-        if (done) continue;
-        const CellGrid& g = lv.g[v];
-        int lo[3], hi[3];
-        prg::clip_cells(q, rho, g, lo, hi);
-        const int span = max(hi[0] - lo[0], max(hi[1] - lo[1], hi[2] - lo[2]));
-        if (span > prg::kCountSpan && v + 1 < lv.count) continue;
-        done = true;
-        const double4* __restrict__ sp = lv.sp[v];
-        const int2* __restrict__ cells = lv.cells[v];
-        for (int z = lo[2]; z <= hi[2]; ++z)
-            for (int y = lo[1]; y <= hi[1]; ++y)
-                for (int x = lo[0]; x <= hi[0]; ++x) {
-                    const int2 be = cells[cell_key(x, y, z, g)];
-                    for (int t = be.x; t < be.y; ++t) {
-                        const double4 p = sp[t];
-                        if (!g.dense && (cell_of(p.x, g.lo[0], g.edge) != x || cell_of(p.y, g.lo[1], g.edge) != y ||
-                                         cell_of(p.z, g.lo[2], g.edge) != z))
-                            continue;
-                        const double dx = p.x - q[0], dy = p.y - q[1], dz = p.z - q[2];
-                        count += (dx * dx + dy * dy) + dz * dz <= r2 ? 1 : 0;
-                    }
-                }
-    }
-    out_cnt[m] = count;
+    CountWithin c;
+    moved_query(state, src, m, c.q);
+    c.r2 = r2;
+    c.count = 0;
+    prg::radius_walk(lv, c.q, r, c);
+    out_cnt[m] = c.count;
 }
 
 // ------------------------------------------------------------------------------------------------------------ cell edge
@@ -449,6 +425,7 @@ int run_radius_count(prg_icp* h, const char* who, double r) {
     const int64_t M = h->M;
     h->have_counts = false;
     if (h->have_outlier == 2) h->have_outlier = 0;  // its keep mask went with these counts
+    h->have_dbscan = false;                         // and so did the counts of a clustering
     PRG_HIP(h->counts.ensure(M, M));
     PRG_TRY(ensure_order(h));
     k_icp_radius_count<<<(unsigned)ceil_div(M, kBlock), kBlock, 0, h->stream>>>(h->lv, h->src.p, h->qvals.p + M, M, h->state.p, r,

@@ -405,6 +405,7 @@ void drop_lists(prg_icp* h) {
     h->have_knn = 0;
     h->have_counts = false;
     h->have_outlier = 0;
+    h->have_dbscan = false;
 }
 
 }  // namespace icp

@@ -1,6 +1,6 @@
-// The ICP plan and what its three translation units share: icp.hip (lifecycle, clouds, sums, step, loop), grid_search.hip (the
-// levels and the searches on them) and icp_outlier.hip (the two filters on the lists and counts).  Only host functions cross a
-// file; each kernel is launched from the file that defines it.
+// The ICP plan and what its four translation units share: icp.hip (lifecycle, clouds, sums, step, loop), grid_search.hip (the
+// levels and the searches on them), icp_outlier.hip (the two filters on the lists and counts) and icp_cluster.hip (DBSCAN on the
+// counts and the radius walk).  Only host functions cross a file; each kernel is launched from the file that defines it.
 #pragma once
 #include "dev_buf.h"
 #include "grid_search.h"
@@ -23,6 +23,15 @@ __device__ __forceinline__ void moved(const double (&m)[12], const double* __res
     for (int a = 0; a < 3; ++a) q[a] = ((m[3 * a] * p[0] + m[3 * a + 1] * p[1]) + m[3 * a + 2] * p[2]) + m[9 + a];
 }
 
+// source point m under the pose in the state: the query of every search
+__device__ __forceinline__ void moved_query(const double* __restrict__ state, const double* __restrict__ src, int64_t m,
+                                            double (&q)[3]) {
+    double pose[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pose[k] = state[kStPose + k];
+    moved(pose, src + m * 3, q);
+}
+
 }  // namespace icp
 }  // namespace prg
 
@@ -34,6 +43,8 @@ struct prg_icp {
     int have_knn = 0;                          // k of the lists in knn_*, 0: none
     bool have_counts = false;
     int have_outlier = 0;                      // 0 none, 1 statistical (score, stat, keep), 2 radius (counts, keep)
+    bool have_dbscan = false;                  // db_* hold a clustering (of the counts in `counts`)
+    int db_clusters = -1;                      // its number of clusters once it has been read back, -1: not yet
     bool have_cov[2] = {false, false};         // source, target
     prg::Levels lv;
     prg::DevBuf<double4> tp, tn;               // target points and normals, padded to four doubles
@@ -55,6 +66,13 @@ struct prg_icp {
     prg::DevBuf<double> score;                 // [M]: the mean neighbour distance
     prg::DevBuf<double> stat;                  // mu, s, thr
     prg::DevBuf<unsigned char> keep;           // [M]
+    prg::DevBuf<unsigned char> db_core;        // [M]: 1 core, 0 not
+    prg::DevBuf<int> db_parent;                // [M]: the union-find over the core points, -1 for the others
+    prg::DevBuf<int> db_near;                  // [M]: the nearest core neighbour of a point that is not core, -1: none
+    prg::DevBuf<int> db_id;                    // [M]: the cluster number, at the roots only
+    prg::DevBuf<int> db_labels;                // [M]
+    prg::DevBuf<int> db_sizes;                 // [M]: the first db_clusters are used
+    prg::DevBuf<int> db_tiles;                 // [2 tiles + 1]: roots per tile, their scan, the number of clusters
 };
 
 namespace prg {

@@ -347,6 +347,19 @@ class IcpPlan(_lib.Handle):
         _lib.check(_lib.lib.prg_icp_get_outlier(self._h, _lib.ptr(keep), None, None))
         return keep.astype(bool), self._counts()
 
+    def _dbscan(self, eps, min_points):
+        """For ``preprocess.cluster_dbscan``, as ``_outlier_statistical``: (labels (M,) int32, core (M,) bool, counts (M,) int32,
+        n_clusters, sizes (n_clusters,) int32)."""
+        _lib.check(_lib.lib.prg_icp_dbscan(self._h, eps, min_points))
+        labels = np.empty(self.n_source, dtype=np.int32)
+        core = np.empty(self.n_source, dtype=np.uint8)
+        n_clusters = ctypes.c_int(0)
+        _lib.check(_lib.lib.prg_icp_get_dbscan(self._h, _lib.ptr(labels), _lib.ptr(core), ctypes.byref(n_clusters), None))
+        sizes = np.empty(int(n_clusters.value), dtype=np.int32)
+        if sizes.shape[0] > 0:
+            _lib.check(_lib.lib.prg_icp_get_dbscan(self._h, None, None, None, _lib.ptr(sizes)))
+        return labels, core.astype(bool), self._counts(), int(n_clusters.value), sizes
+
     def sums(self, estimation):
         """The raw ordered sums of a step over the current matches (32 doubles, laid out as ``prg_icp_sums`` documents).
         ``estimation``: as in ``registration_icp``, or ``GENERALIZED`` / "generalized" (here, in ``step`` and in ``iterate``)."""

@@ -16,6 +16,13 @@ uniform outliers the reference's example set-up adds to every target (examples/u
 k-nearest-neighbour search and the radius count of ``probreg_amd.icp`` (``prg_icp_knn``, ``prg_icp_radius_count``, csrc/grid_search.hip; the filters: csrc/icp_outlier.hip;
 DESIGN.md section 3.17), in fp64 with every sum in a stated order.
 
+``cluster_dbscan`` is Open3D's ``cluster_dbscan(eps, min_points)``, which cuts a scene into its objects and marks the stray
+points between them as noise; ``DbscanResult.clusters()`` hands the objects to ``cpd.registration_cpd_batch``.  It runs on
+the same radius count and the same walk of the grid (``prg_icp_dbscan``, csrc/icp_cluster.hip): core
+points from the counts, their connected components by a union-find that only ever lowers 32-bit indices with integer
+atomics (csrc/union_find.h), clusters numbered by their smallest core index.  Core points, their labels and the noise are
+scikit-learn's; a border point goes to the cluster of its nearest core neighbour, not to the one a scan reaches first.
+
 The result of a global registration on the down-sampled clouds starts a local one on the full clouds::
 
     from probreg_amd import cpd, global_reg
@@ -300,3 +307,68 @@ def remove_radius_outlier(points, nb_points, radius, normals=None, attributes=No
     finally:
         plan.close()
     return _kept(pts, normals, attributes, keep, counts, int(nb))
+
+
+# ------------------------------------------------------------------------------------------------------------ clustering
+class DbscanResult(collections.namedtuple("DbscanResult", ["labels", "core", "counts", "n_clusters", "sizes"])):
+    """``labels (n,) int32`` (-1: noise), ``core (n,) bool``, ``counts (n,) int32`` (the neighbours within ``eps``, the point
+    itself included), ``n_clusters`` and ``sizes (n_clusters,) int32`` (core and border points of every cluster)."""
+    __slots__ = ()
+
+    def clusters(self, min_size=1):
+        """The clusters with at least ``min_size`` members as ascending int32 index arrays, in label order: one cloud per
+        object for ``cpd.registration_cpd_batch([model] * len(c), [scene[i] for i in c], "rigid")``."""
+        order = np.argsort(self.labels, kind="stable")  # noise first, then cluster by cluster, ascending inside each
+        ends = np.cumsum(self.sizes, dtype=np.int64) + (self.labels.shape[0] - int(np.sum(self.sizes, dtype=np.int64)))
+        return [np.ascontiguousarray(order[e - s:e], dtype=np.int32) for s, e in zip(self.sizes.tolist(), ends.tolist())
+                if s >= min_size]
+
+
+def _check_min_points(v):
+    try:
+        bad = isinstance(v, (bool, np.bool_, str, bytes)) or not np.isfinite(float(v)) or float(v) != int(v)
+    except (TypeError, ValueError, OverflowError):
+        bad = True
+    if bad or not 1 <= int(v) < 2 ** 31:
+        raise ValueError("min_points must be an integer in 1 .. 2^31 - 1, got %r" % (v,))
+    return int(v)
+
+
+def cluster_dbscan(points, eps, min_points, device=None):
+    """Open3D's ``cluster_dbscan(eps, min_points)``: split a cloud into its density-connected objects and mark the stray
+    points between them as noise (neighbour counts, union-find and numbering run on the GPU).
+
+    ``counts_i`` is the number of points with ``d2 <= eps eps``, the point itself included; point ``i`` is core iff
+    ``counts_i >= min_points`` (Open3D's and scikit-learn's convention).  The clusters are the connected components of the
+    core points under ``d2 <= eps eps``, numbered 0, 1, ... in ascending order of their smallest core index, which is the
+    numbering of a sequential scan: core labels equal scikit-learn's.  A point that is not core but has a core point within
+    ``eps`` is a border point; every other point is noise, label -1.
+
+    Deviation from Open3D and scikit-learn (their rule as it is remembered, not verified against their sources): there a
+    border point within reach of two clusters goes to the one whose scan reaches it first, which depends on the order of
+    the points; here it goes to the cluster of its nearest core neighbour, the minimum of ``(d2, index)``.  Core set, core
+    labels and noise are the same.
+
+    The result is byte-identical from run to run and does not depend on the search grid.
+
+    Args:
+        points: (n, 2) or (n, 3) array, or anything with ``.points``.
+        eps: finite, > 0.
+        min_points: integer in 1 .. 2^31 - 1.
+    Returns:
+        ``DbscanResult(labels, core, counts, n_clusters, sizes)``; ``result.clusters(min_size)`` lists the index arrays.
+    """
+    from . import icp
+
+    pts, _, _ = _filter_inputs(points, None, None)
+    r = icp._check_radius(eps, "eps", False)
+    mp = _check_min_points(min_points)
+    _single_process("cluster_dbscan")
+    cloud = _pad3(pts)
+    plan = icp.IcpPlan(device)
+    try:
+        plan.set_target(cloud)
+        plan.set_source(cloud)
+        return DbscanResult(*plan._dbscan(r, mp))
+    finally:
+        plan.close()
