@@ -909,6 +909,52 @@ int prg_field_set_control(prg_field* h, const double* control_hd, const double* 
  * control points the queries go through in batches that keep the slab sums within 64 MB.  Synchronises. */
 int prg_field_evaluate(prg_field* h, const double* points_hd, int64_t q, double* out_host);
 
+/* ---- plane segmentation (csrc/plane_seg.hip, csrc/plane_seg.h) ----
+ * The dominant plane of a 3-D cloud by RANSAC: hypotheses x points in fp64, every operation rounded once, sums in a stated
+ * order, no floating-point atomics; every stage can be driven on its own.  A plane is six doubles: the unit normal n (its
+ * component of largest magnitude positive) and an anchor a; the signed distance of x is
+ * (n_x (x - a_x) + n_y (y - a_y)) + n_z (z - a_z).  A point is an inlier iff |dist| <= tau and, with cos_theta >= 0 and normals
+ * m, |n . m| >= cos_theta |m| with |m| > 0; a negative cos_theta switches the normal test off. */
+typedef struct prg_plane prg_plane;
+/* One segmentation on one device / stream.  Replaces: none in the reference (as every prg_plane_* entry point below); Open3D's
+ * segment_plane(distance_threshold, ransac_n = 3, num_iterations), which users run on a scene before cluster_dbscan. */
+int prg_plane_create(prg_plane** out, int device, void* hip_stream);
+int prg_plane_destroy(prg_plane* h);
+/* The cloud (n x 3 float64, finite, host or device, 3 <= n < 2^31) and, optionally (NULL: none), one normal per point (n x 3;
+ * any length, its length is taken once here).  Synchronises. */
+int prg_plane_set_points(prg_plane* h, const double* points_hd, const double* normals_hd, int64_t n);
+/* The number of points of the handle's cloud: n, less what prg_plane_remove has dropped. */
+int prg_plane_count(prg_plane* h, int64_t* n_host);
+/* Hypotheses h_offset .. h_offset + H - 1 (1 <= H <= 2^24): point j of hypothesis g is splitmix64(seed, 3 g + j + 1) reduced to
+ * [0, n); valid iff the three are distinct and |e1 x e2| >= 0.05 |e1| |e2|, > 0; the plane is n = (e1 x e2) / |e1 x e2| with the
+ * sign rule, anchored at the first point. */
+int prg_plane_build(prg_plane* h, uint64_t seed, uint64_t h_offset, int64_t H);
+/* triples H x 3, planes H x 6 (zeros where invalid), valid H; any may be NULL.  Synchronises. */
+int prg_plane_get_hypotheses(prg_plane* h, int* triples_host, double* planes_host, int* valid_host);
+/* Installs H planes (H x 6) and their flags instead of drawing them (tests).  Synchronises. */
+int prg_plane_set_hypotheses(prg_plane* h, const double* planes_hd, const int* valid_hd, int64_t H);
+/* Per valid hypothesis the inlier count and the sum of dist^2 over the inliers: ascending index inside pieces of 1024 points,
+ * the pieces added in ascending order.  An invalid hypothesis reports (-1, 0). */
+int prg_plane_score(prg_plane* h, double tau, double cos_theta);
+int prg_plane_get_scores(prg_plane* h, int* counts_host, double* sums_host);
+/* The first hypothesis in the order (count descending, sum ascending, index ascending): its index (-1 when no hypothesis is
+ * valid: count 0, sum 0, a plane of zeros), the number of valid hypotheses, count, sum and plane (6).  Any output may be NULL.
+ * Synchronises. */
+int prg_plane_best(prg_plane* h, int64_t* index_host, int64_t* n_valid_host, int* count_host, double* sum_host,
+                   double* plane_host);
+/* `iters` (0 .. 1000) least-squares refits of plane_io_host (6): over the inliers of the current plane, in runs of 64 points
+ * added in ascending order, k = sum 1, s = sum q and sum q q^T (xx, xy, xz, yy, yz, zz) with q = x - a; c = s / k,
+ * C = sum q q^T / k - c c^T; n = the eigenvector of C's smallest eigenvalue, a += c.  With fewer than three inliers the plane is
+ * kept.  trace_host (iters x 10, may be NULL): the ten sums of every iteration.  Synchronises. */
+int prg_plane_refine(prg_plane* h, double tau, double cos_theta, int iters, double* plane_io_host, double* trace_host);
+/* Inlier mask (n, int) and signed distances (n) of plane_host (6), the inlier count and the sum of dist^2 in the order of
+ * prg_plane_score.  Outputs may be NULL.  Synchronises. */
+int prg_plane_classify(prg_plane* h, const double* plane_host, double tau, double cos_theta, int* mask_host, double* dist_host,
+                       int* count_host, double* sum_host);
+/* Drops the inliers of the last prg_plane_classify: the other points (and normals), in ascending index, become the handle's
+ * cloud, which stays on the device; the hypotheses go.  n_left_host (may be NULL): the points left.  Synchronises. */
+int prg_plane_remove(prg_plane* h, int64_t* n_left_host);
+
 #ifdef __cplusplus
 }
 #endif

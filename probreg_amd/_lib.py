@@ -264,6 +264,19 @@ SIGNATURES = {
     "prg_field_destroy": [_vp],
     "prg_field_set_control": [_vp, _vp, _vp, _i64, _i, _i, _i, _d],
     "prg_field_evaluate": [_vp, _vp, _i64, _vp],
+    "prg_plane_create": [_pp, _i, _vp],
+    "prg_plane_destroy": [_vp],
+    "prg_plane_set_points": [_vp, _vp, _vp, _i64],
+    "prg_plane_count": [_vp, _c.POINTER(_i64)],
+    "prg_plane_build": [_vp, _c.c_uint64, _c.c_uint64, _i64],
+    "prg_plane_get_hypotheses": [_vp, _vp, _vp, _vp],
+    "prg_plane_set_hypotheses": [_vp, _vp, _vp, _i64],
+    "prg_plane_score": [_vp, _d, _d],
+    "prg_plane_get_scores": [_vp, _vp, _vp],
+    "prg_plane_best": [_vp, _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i), _c.POINTER(_d), _vp],
+    "prg_plane_refine": [_vp, _d, _d, _i, _vp, _vp],
+    "prg_plane_classify": [_vp, _vp, _d, _d, _vp, _vp, _c.POINTER(_i), _c.POINTER(_d)],
+    "prg_plane_remove": [_vp, _c.POINTER(_i64)],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -23,6 +23,17 @@ points from the counts, their connected components by a union-find that only eve
 atomics (csrc/union_find.h), clusters numbered by their smallest core index.  Core points, their labels and the noise are
 scikit-learn's; a border point goes to the cluster of its nearest core neighbour, not to the one a scan reaches first.
 
+``segment_plane`` is Open3D's ``segment_plane(distance_threshold, ransac_n=3, num_iterations)``, which takes the table or
+floor out of a scene before ``cluster_dbscan`` (otherwise the supporting plane is the largest "cluster" and joins everything
+that stands on it); ``segment_planes`` repeats it on what is left.  It runs in ``prg_plane_*`` (csrc/plane_seg.hip; the
+decisions in the host-compilable csrc/plane_seg.h) in fp64 with every operation rounded once:
+counter-based draws, a sweep hypotheses x points with ordered sums, the winner by (count, sum, index), least-squares refits::
+
+    seg = preprocess.segment_plane(scene, 0.01)
+    rest = scene[~seg.mask]
+    objects = preprocess.cluster_dbscan(rest, eps, min_points).clusters(min_size)
+    results = cpd.registration_cpd_batch([model] * len(objects), [rest[i] for i in objects], "rigid")
+
 The result of a global registration on the down-sampled clouds starts a local one on the full clouds::
 
     from probreg_amd import cpd, global_reg
@@ -372,3 +383,272 @@ def cluster_dbscan(points, eps, min_points, device=None):
         return DbscanResult(*plan._dbscan(r, mp))
     finally:
         plan.close()
+
+
+# ---------------------------------------------------------------------------------------------------- plane segmentation
+PlaneSegmentation = collections.namedtuple("PlaneSegmentation", ["plane", "point", "inliers", "mask", "distance", "fitness",
+                                                                 "inlier_rmse", "hypothesis", "n_valid", "count", "sum"])
+PlaneSet = collections.namedtuple("PlaneSet", ["planes", "points", "labels", "sizes", "n_planes"])
+
+MAX_HYPOTHESES = 1 << 24
+
+
+def _check_tau(v):
+    try:
+        tau = float("nan") if isinstance(v, (bool, str, bytes)) else float(v)
+    except (TypeError, ValueError):
+        tau = float("nan")
+    if not (np.isfinite(tau) and tau >= 0.0):
+        raise ValueError("distance_threshold must be a finite number >= 0, got %r" % (v,))
+    return tau
+
+
+def _check_count(v, name, lo, hi):
+    try:
+        bad = isinstance(v, (bool, np.bool_, str, bytes)) or not np.isfinite(float(v)) or float(v) != int(v)
+    except (TypeError, ValueError, OverflowError):
+        bad = True
+    if bad or not lo <= int(v) <= hi:
+        raise ValueError("%s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+    return int(v)
+
+
+def _cos_theta(max_normal_angle, have_normals):
+    """cos of the angle for the library, -1.0 for "no normal test"."""
+    if max_normal_angle is None:
+        return -1.0
+    if not have_normals:
+        raise ValueError("max_normal_angle needs normals")
+    try:
+        a = float("nan") if isinstance(max_normal_angle, (bool, str, bytes)) else float(max_normal_angle)
+    except (TypeError, ValueError):
+        a = float("nan")
+    if not (np.isfinite(a) and 0.0 <= a <= np.pi / 2.0):
+        raise ValueError("max_normal_angle must lie in [0, pi / 2] (radians), got %r" % (max_normal_angle,))
+    return max(0.0, float(np.cos(a)))
+
+
+def _plane_row(plane):
+    plane = np.ascontiguousarray(plane, dtype=np.float64).reshape(-1)
+    if plane.shape[0] != 6 or not np.all(np.isfinite(plane)):
+        raise ValueError("a plane is six finite numbers (unit normal, anchor)")
+    return plane
+
+
+class PlanePlan(_lib.Handle):
+    """One ``prg_plane`` handle: a 3-D cloud (with or without normals) on one device / stream and the stages of the plane
+    search, each of which can be driven on its own.  A plane is six numbers: the unit normal and the anchor the distances
+    are taken from.  ``cos_theta`` is the cosine of the largest angle between a point's normal and the plane's, ``None``
+    for no normal test."""
+
+    def __init__(self, device=None):
+        super().__init__(_lib.lib.prg_plane_create, _lib.lib.prg_plane_destroy, device)
+        self.n = 0
+        self.n_hyp = 0
+        self.have_normals = False
+
+    @staticmethod
+    def _cos(cos_theta):
+        return -1.0 if cos_theta is None else float(cos_theta)
+
+    def set_points(self, points, normals=None):
+        points = _lib.as_cloud(points, "points", (3,), 3)
+        if normals is not None:
+            normals = _as_channel(normals, "normals", points.shape[0], 3)
+        _lib.check(_lib.lib.prg_plane_set_points(self._h, _lib.ptr(points), _lib.ptr(normals), points.shape[0]))
+        self.n = points.shape[0]
+        self.have_normals = normals is not None
+
+    def count(self):
+        """The points of the handle's cloud: those of ``set_points`` less what ``remove`` has dropped."""
+        n = ctypes.c_int64(0)
+        _lib.check(_lib.lib.prg_plane_count(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def build(self, seed, n_hypotheses, offset=0):
+        """Hypotheses ``offset .. offset + n_hypotheses - 1`` of the stream ``seed``."""
+        _lib.check(_lib.lib.prg_plane_build(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), int(n_hypotheses)))
+        self.n_hyp = int(n_hypotheses)
+
+    def hypotheses(self, triples=True):
+        """(triples (H, 3) int32 or None, planes (H, 6), valid (H,) bool)."""
+        tri = np.empty((self.n_hyp, 3), dtype=np.int32) if triples else None
+        planes = np.empty((self.n_hyp, 6))
+        valid = np.empty(self.n_hyp, dtype=np.int32)
+        _lib.check(_lib.lib.prg_plane_get_hypotheses(self._h, _lib.ptr(tri), _lib.ptr(planes), _lib.ptr(valid)))
+        return tri, planes, valid != 0
+
+    def set_hypotheses(self, planes, valid):
+        planes = np.ascontiguousarray(planes, dtype=np.float64)
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        if planes.ndim != 2 or planes.shape[1] != 6 or valid.shape != (planes.shape[0],):
+            raise ValueError("planes must be (H, 6) and valid (H,), got %s and %s" % (planes.shape, valid.shape))
+        if not np.all(np.isfinite(planes)):
+            raise ValueError("planes contains NaN or infinity")
+        _lib.check(_lib.lib.prg_plane_set_hypotheses(self._h, _lib.ptr(planes), _lib.ptr(valid), planes.shape[0]))
+        self.n_hyp = planes.shape[0]
+
+    def score(self, tau, cos_theta=None):
+        _lib.check(_lib.lib.prg_plane_score(self._h, _check_tau(tau), self._cos(cos_theta)))
+
+    def scores(self):
+        """(count (H,) int32 with -1 for an invalid hypothesis, sum (H,))."""
+        cnt = np.empty(self.n_hyp, dtype=np.int32)
+        sm = np.empty(self.n_hyp)
+        _lib.check(_lib.lib.prg_plane_get_scores(self._h, _lib.ptr(cnt), _lib.ptr(sm)))
+        return cnt, sm
+
+    def best(self):
+        """(index, n_valid, count, sum, plane (6,)) of the winner; index -1 when no hypothesis is valid."""
+        idx, nv, cnt, sm = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_double(0.0)
+        plane = np.empty(6)
+        _lib.check(_lib.lib.prg_plane_best(self._h, ctypes.byref(idx), ctypes.byref(nv), ctypes.byref(cnt), ctypes.byref(sm),
+                                           _lib.ptr(plane)))
+        return int(idx.value), int(nv.value), int(cnt.value), float(sm.value), plane
+
+    def refine(self, plane, tau, iters=3, cos_theta=None):
+        """(plane (6,), sums (iters, 10)) after ``iters`` refits that start from ``plane``; row i of ``sums`` holds the
+        inlier count, the sums of ``q = x - a`` and of ``q q^T`` (xx, xy, xz, yy, yz, zz) of iteration i."""
+        plane = _plane_row(plane).copy()
+        iters = _check_count(iters, "iters", 0, 1000)
+        trace = np.zeros((iters, 10))
+        _lib.check(_lib.lib.prg_plane_refine(self._h, _check_tau(tau), self._cos(cos_theta), iters, _lib.ptr(plane),
+                                             _lib.ptr(trace) if iters else None))
+        return plane, trace
+
+    def classify(self, plane, tau, cos_theta=None):
+        """(mask (n,) bool, signed distance (n,), count, sum of the squared inlier distances) of ``plane``."""
+        plane = _plane_row(plane)
+        n = self.count()
+        mask = np.empty(n, dtype=np.int32)
+        dist = np.empty(n)
+        cnt, sm = ctypes.c_int(0), ctypes.c_double(0.0)
+        _lib.check(_lib.lib.prg_plane_classify(self._h, _lib.ptr(plane), _check_tau(tau), self._cos(cos_theta), _lib.ptr(mask),
+                                               _lib.ptr(dist), ctypes.byref(cnt), ctypes.byref(sm)))
+        return mask != 0, dist, int(cnt.value), float(sm.value)
+
+    def remove(self):
+        """Drops the inliers of the last ``classify``; the rest stays on the device in ascending index.  Returns how many
+        points are left."""
+        n = ctypes.c_int64(0)
+        _lib.check(_lib.lib.prg_plane_remove(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def segment(self, tau, num_iterations, seed, refine_iters, cos_theta=None, offset=0):
+        """All stages on the handle's cloud: a ``PlaneSegmentation`` whose indices are rows of that cloud."""
+        n = self.count()
+        self.build(seed, num_iterations, offset)
+        self.score(tau, cos_theta)
+        idx, n_valid, cnt, sm, plane = self.best()
+        if idx < 0:
+            return PlaneSegmentation(None, None, np.zeros(0, dtype=np.int32), np.zeros(n, dtype=bool), np.zeros(n), 0.0, 0.0,
+                                     -1, n_valid, 0, 0.0)
+        plane, _ = self.refine(plane, tau, refine_iters, cos_theta)
+        mask, dist, k, total = self.classify(plane, tau, cos_theta)
+        nrm, a = plane[:3], plane[3:]
+        abcd = np.array([nrm[0], nrm[1], nrm[2], -((nrm[0] * a[0] + nrm[1] * a[1]) + nrm[2] * a[2])])
+        return PlaneSegmentation(abcd, a.copy(), np.nonzero(mask)[0].astype(np.int32), mask, dist, k / float(n),
+                                 float(np.sqrt(total / k)) if k else 0.0, idx, n_valid, cnt, sm)
+
+
+def _plane_inputs(points, normals, distance_threshold, num_iterations, refine_iters, max_normal_angle, what):
+    pts = _lib.as_cloud(points, "points", (3,), 3)
+    if normals is None and max_normal_angle is not None and not isinstance(points, np.ndarray) and hasattr(points, "points"):
+        own = getattr(points, "normals", None)
+        if own is not None and np.ndim(own) == 2 and np.shape(own)[0] == pts.shape[0]:
+            normals = own
+    if normals is not None:
+        normals = _as_channel(normals, "normals", pts.shape[0], 3)
+    tau = _check_tau(distance_threshold)
+    n_hyp = _check_count(num_iterations, "num_iterations", 1, MAX_HYPOTHESES)
+    iters = _check_count(refine_iters, "refine_iters", 0, 1000)
+    cos_theta = _cos_theta(max_normal_angle, normals is not None)
+    _single_process(what)
+    return pts, (normals if cos_theta >= 0.0 else None), tau, n_hyp, iters, (cos_theta if cos_theta >= 0.0 else None)
+
+
+def segment_plane(points, distance_threshold, num_iterations=1000, seed=0, refine_iters=3, normals=None,
+                  max_normal_angle=None, device=None, hypothesis_offset=0):
+    """Open3D's ``segment_plane(distance_threshold, ransac_n=3, num_iterations)``: the plane that most points of a cloud lie
+    within ``distance_threshold`` of - the table or floor a scene stands on, to be taken out before ``cluster_dbscan``
+    (the draws, the sweep hypotheses x points, the winner and the refits run on the GPU in fp64).
+
+    Hypothesis ``h`` is the plane through three points drawn by a counter-based generator from ``seed`` (so the result does
+    not depend on how the work is cut); its score is the number of points with ``|dist| <= distance_threshold`` and the sum
+    of their squared distances; the winner (most inliers, then the smaller sum, then the smaller ``h``) is refitted
+    ``refine_iters`` times by least squares on its inliers.  Distances are taken from an anchor point on the plane, never
+    as ``n . x + d``, so a cloud far from the origin loses nothing.  The result is byte-identical from run to run.
+
+    Deviations from Open3D (its behaviour as it is remembered, not verified against its source): a point exactly at the
+    threshold is an inlier (Open3D: ``<``); the draws are this module's own; ``ransac_n`` is 3 and there is no
+    ``probability`` early stop; the final plane is refitted more than once.
+
+    Args:
+        points: (n, 3) array with n >= 3, or anything with ``.points`` (its ``.normals`` are used when ``max_normal_angle`` is
+            given and ``normals`` is None).
+        distance_threshold: finite, >= 0.
+        num_iterations: the number of hypotheses, 1 .. 2^24.
+        seed: of the draws.
+        refine_iters: least-squares refits of the winner, 0 .. 1000.
+        normals, max_normal_angle: with both, an inlier's normal ``m`` must also lie within ``max_normal_angle`` (radians,
+            0 .. pi / 2) of the plane's, either way round: ``|n . m| >= cos(max_normal_angle) |m|``.  A zero normal never
+            passes.  ``max_normal_angle`` without normals is a ``ValueError``.
+        hypothesis_offset: the first hypothesis of the stream (``segment_planes`` gives round k the offset
+            ``k num_iterations``).
+    Returns:
+        ``PlaneSegmentation(plane (a, b, c, d) with unit (a, b, c) whose component of largest magnitude is positive and
+        d = -n . point, point (3,): the anchor, inliers (ascending int32), mask (n,) bool, distance (n,): signed, to the final
+        plane, fitness = len(inliers) / n, inlier_rmse, hypothesis, n_valid, count, sum)``; the last four describe the
+        RANSAC winner before the refit.  When no hypothesis is valid (no three distinct, non-collinear points were drawn)
+        ``plane`` and ``point`` are None, ``inliers`` is empty and ``hypothesis`` is -1.
+    """
+    pts, normals, tau, n_hyp, iters, cos_theta = _plane_inputs(points, normals, distance_threshold, num_iterations,
+                                                               refine_iters, max_normal_angle, "segment_plane")
+    offset = _check_count(hypothesis_offset, "hypothesis_offset", 0, 2 ** 62)
+    plan = PlanePlan(device)
+    try:
+        plan.set_points(pts, normals)
+        return plan.segment(tau, n_hyp, seed, iters, cos_theta, offset)
+    finally:
+        plan.close()
+
+
+def segment_planes(points, distance_threshold, max_planes, min_inliers=3, num_iterations=1000, seed=0, refine_iters=3,
+                   normals=None, max_normal_angle=None, device=None):
+    """Up to ``max_planes`` planes, one after the other: by definition ``segment_plane`` on the points that no earlier plane
+    has taken, kept in ascending original index, round ``k`` with ``hypothesis_offset = k num_iterations``.  It stops after
+    ``max_planes`` rounds, when a round's final inlier count is below ``min_inliers`` (that plane is dropped), when a round
+    has no valid hypothesis, or when fewer than three points are left.  The remaining cloud stays on the device between the
+    rounds and shrinks, so later rounds sweep fewer points.
+
+    Returns:
+        ``PlaneSet(planes (P, 4), points (P, 3): the anchors, labels (n,) int32: the plane of every point, -1 for the rest,
+        sizes (P,) int32, n_planes)``.
+    """
+    pts, normals, tau, n_hyp, iters, cos_theta = _plane_inputs(points, normals, distance_threshold, num_iterations,
+                                                               refine_iters, max_normal_angle, "segment_planes")
+    rounds = _check_count(max_planes, "max_planes", 0, 2 ** 31 - 1)
+    least = _check_count(min_inliers, "min_inliers", 0, 2 ** 31 - 1)
+    labels = np.full(pts.shape[0], -1, dtype=np.int32)
+    left = np.arange(pts.shape[0])
+    planes, anchors, sizes = [], [], []
+    plan = PlanePlan(device)
+    try:
+        plan.set_points(pts, normals)
+        for k in range(rounds):
+            if left.shape[0] < 3:
+                break
+            seg = plan.segment(tau, n_hyp, seed, iters, cos_theta, k * n_hyp)
+            if seg.hypothesis < 0 or seg.inliers.shape[0] < least:
+                break
+            labels[left[seg.mask]] = k
+            planes.append(seg.plane)
+            anchors.append(seg.point)
+            sizes.append(seg.inliers.shape[0])
+            left = left[~seg.mask]
+            if plan.remove() != left.shape[0]:
+                raise _lib.ProbregHipError("segment_planes: the device kept %d points, the host %d" % (plan.count(), left.shape[0]))
+    finally:
+        plan.close()
+    return PlaneSet(np.array(planes, dtype=np.float64).reshape(-1, 4), np.array(anchors, dtype=np.float64).reshape(-1, 3),
+                    labels, np.array(sizes, dtype=np.int32), len(planes))
