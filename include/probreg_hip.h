@@ -955,6 +955,59 @@ int prg_plane_classify(prg_plane* h, const double* plane_host, double tau, doubl
  * cloud, which stays on the device; the hypotheses go.  n_left_host (may be NULL): the points left.  Synchronises. */
 int prg_plane_remove(prg_plane* h, int64_t* n_left_host);
 
+/* ---- fast global registration (csrc/fgr.hip, csrc/fgr.h) ----
+ * Zhou, Park, Koltun (ECCV 2016), as Open3D's registration_fgr_based_on_correspondence runs it: one rigid pose (no scale) for
+ * all correspondences by Gauss-Newton under a Geman-McClure line process whose scale mu is annealed, after a tuple test that
+ * removes most wrong matches.  fp64, every operation rounded once, sums in runs of 64 rows added in ascending order, no
+ * floating-point atomics; every stage can be driven on its own.  A pose is 12 doubles: the rotation row-major, then the shift. */
+typedef struct prg_fgr prg_fgr;
+/* One registration on one device / stream.  Replaces: none in the reference (as every prg_fgr_* entry point below); Open3D's
+ * registration_fgr_based_on_correspondence, which users of the reference can get their start pose from. */
+int prg_fgr_create(prg_fgr** out, int device, void* hip_stream);
+int prg_fgr_destroy(prg_fgr* h);
+/* Both clouds (m x 3 and n x 3 float64, finite, host or device, 1 <= m, n < 2^31).  Synchronises. */
+int prg_fgr_set_clouds(prg_fgr* h, const double* source_hd, int64_t m, const double* target_hd, int64_t n);
+/* c pairs (source index, target index), c x 2 int32, 3 <= c <= 2^31 / 100; the indices are checked by prg_fgr_normalise.
+ * Synchronises. */
+int prg_fgr_set_correspondences(prg_fgr* h, const int* corr_hd, int64_t c);
+/* The mean of every cloud (all of its points: runs of 64 rows added in ascending order, the runs added in ascending order,
+ * divided by the count), scale = the largest |x - mean| of both clouds, and the matched pairs as (x - mean) / scale_global with
+ * scale_global = scale, or 1 with use_absolute_scale.  Outputs (3, 3, 1) may be NULL.  With a scale of 0 the pairs are not formed
+ * and the later stages report PRG_ERR_STATE.  PRG_ERR_INVALID: a correspondence indexes outside its cloud.  Synchronises. */
+int prg_fgr_normalise(prg_fgr* h, int use_absolute_scale, double* mean_p_host, double* mean_q_host, double* scale_host);
+/* Trials per launch of prg_fgr_tuples (0: the default); bounds buffers, changes no result. */
+int prg_fgr_set_chunk(prg_fgr* h, int64_t trials);
+/* The tuple test: trial t = 0, 1, .. < 100 c draws three correspondences (splitmix64(seed, 3 t + j + 1) reduced to [0, c)) and
+ * passes iff li s < lj and lj s < li on each of the edges (0, 1), (1, 2), (2, 0), li and lj the edge's lengths in the two
+ * normalised clouds, s = tuple_scale in (0, 1].  The first maximum_tuple_count passing trials in ascending t are accepted; their
+ * 3 indices each, in that order, become the used pairs.  n_trials: the last accepted trial + 1, or 100 c when the limit ended
+ * the search.  Synchronises. */
+int prg_fgr_tuples(prg_fgr* h, uint64_t seed, double tuple_scale, int64_t maximum_tuple_count, int64_t* n_tuples_host,
+                   int64_t* n_trials_host);
+/* Installs k >= 0 used pairs by their indices into the correspondences (k int32; repeats allowed).  PRG_ERR_INVALID: an index
+ * outside [0, c).  Synchronises. */
+int prg_fgr_set_used(prg_fgr* h, const int* index_hd, int64_t k);
+/* The k indices of the used pairs.  Synchronises. */
+int prg_fgr_get_used(prg_fgr* h, int* index_host);
+/* Pose (of the normalised clouds) and mu > 0; clears the status and the step counter.  Synchronises. */
+int prg_fgr_set_state(prg_fgr* h, const double* pose_host, double mu);
+/* The 28 sums over the used pairs at the state's pose and mu: l J^T J (upper triangle, row-major, 21), l J^T r (6) and the
+ * objective sum l r2 + mu (1 - sqrt l)^2, with s = R p + t, r = s - q, l = (mu / (mu + r2))^2, J = (-[s]x | I); runs of 64
+ * pairs in ascending order, the runs added in ascending order.  sums_host (28) may be NULL.  Synchronises. */
+int prg_fgr_sums(prg_fgr* h, double* sums_host);
+/* One step from the sums: x = -A^-1 g by Cholesky (a pivot <= 1e-12 max diag A: degenerate), T <- dT(x) T with Open3D's
+ * TransformVector6dToMatrix4d; then, with decrease_mu, after step i = 0, 4, 8, .. and while mu > maximum_correspondence_distance,
+ * mu <- mu / division_factor.  Fewer than three used pairs or a failed pivot set the status, stop the loop and leave the pose. */
+int prg_fgr_step(prg_fgr* h, int decrease_mu, double division_factor, double maximum_correspondence_distance);
+/* `iterations` (0 .. 100000) times "sums, step" without a host round trip per iteration. */
+int prg_fgr_iterate(prg_fgr* h, int iterations, int decrease_mu, double division_factor, double maximum_correspondence_distance);
+/* Pose (12; with caller_units: R and scale_global t + mean_q - R mean_p), mu, the steps done, the status (0 ok, 1 fewer than
+ * three used pairs, 2 degenerate) and the objective of the last sums.  Any output may be NULL.  Synchronises. */
+int prg_fgr_get_state(prg_fgr* h, int caller_units, double* pose_host, double* mu_host, int64_t* n_iter_host, int* status_host,
+                      double* objective_host);
+/* The line-process value l of every used pair (k doubles) at the state's pose and mu.  Synchronises. */
+int prg_fgr_get_weights(prg_fgr* h, double* weights_host);
+
 #ifdef __cplusplus
 }
 #endif

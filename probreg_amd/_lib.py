@@ -277,6 +277,21 @@ SIGNATURES = {
     "prg_plane_refine": [_vp, _d, _d, _i, _vp, _vp],
     "prg_plane_classify": [_vp, _vp, _d, _d, _vp, _vp, _c.POINTER(_i), _c.POINTER(_d)],
     "prg_plane_remove": [_vp, _c.POINTER(_i64)],
+    "prg_fgr_create": [_pp, _i, _vp],
+    "prg_fgr_destroy": [_vp],
+    "prg_fgr_set_clouds": [_vp, _vp, _i64, _vp, _i64],
+    "prg_fgr_set_correspondences": [_vp, _vp, _i64],
+    "prg_fgr_normalise": [_vp, _i, _vp, _vp, _c.POINTER(_d)],
+    "prg_fgr_set_chunk": [_vp, _i64],
+    "prg_fgr_tuples": [_vp, _c.c_uint64, _d, _i64, _c.POINTER(_i64), _c.POINTER(_i64)],
+    "prg_fgr_set_used": [_vp, _vp, _i64],
+    "prg_fgr_get_used": [_vp, _vp],
+    "prg_fgr_set_state": [_vp, _vp, _d],
+    "prg_fgr_sums": [_vp, _vp],
+    "prg_fgr_step": [_vp, _i, _d, _d],
+    "prg_fgr_iterate": [_vp, _i, _i, _d, _d],
+    "prg_fgr_get_state": [_vp, _i, _vp, _c.POINTER(_d), _c.POINTER(_i64), _c.POINTER(_i), _c.POINTER(_d)],
+    "prg_fgr_get_weights": [_vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -22,12 +22,14 @@
 
 #include "icp_plan.h"
 #include "kabsch_pose.h"
+#include "pose_step.h"
 
 using namespace prg::icp;
+using prg::cholesky6;
+using prg::kPivot;
 
 namespace {
 
-constexpr double kPivot = 1.0e-12;  // a Cholesky pivot <= kPivot max diag(A) is degenerate (part of the definition)
 constexpr int kStatusOk = 0, kStatusTooFew = 1, kStatusDegenerate = 2;
 constexpr int kPointToPoint = 0, kPointToPlane = 1, kGeneralized = 2;
 constexpr int kCov = 6;  // doubles per covariance: xx, xy, xz, yy, yz, zz
@@ -220,52 +222,6 @@ __global__ __launch_bounds__(kBlock) void k_icp_cov_from_normals(const double* _
 }
 
 // ----------------------------------------------------------------------------------------------------------------- step
-// x of A x = b by Cholesky, A from its upper triangle (row-major, 21), b = -g.  false: a pivot <= kPivot max diag(A).
-__device__ inline bool cholesky6(const double* __restrict__ a21, const double* __restrict__ g, double (&x)[6]) {
-    double L[6][6];
-    int s = 0;
-    double top = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) {
-            L[j][i] = a21[s++];
-            if (i == j) top = fmax(top, L[i][i]);
-        }
-    const double floor_ = kPivot * top;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double d = L[k][k];
-#pragma unroll
-        for (int j = 0; j < k; ++j) d -= L[k][j] * L[k][j];
-        if (!(d > floor_)) return false;
-        L[k][k] = sqrt(d);
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) {
-            double v = L[i][k];
-#pragma unroll
-            for (int j = 0; j < k; ++j) v -= L[i][j] * L[k][j];
-            L[i][k] = v / L[k][k];
-        }
-    }
-    double w[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int j = 0; j < i; ++j) v -= L[i][j] * w[j];
-        w[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = w[i];
-#pragma unroll
-        for (int j = i + 1; j < 6; ++j) v -= L[j][i] * x[j];
-        x[i] = v / L[i][i];
-    }
-    return true;
-}
-
 // One lane.  The step from the sums in the state; a missing step (too few matches, degenerate) sets the stop flag and the
 // status and leaves the pose as it is.  R <- dR R, t <- dR t + dt.
 __global__ void k_icp_step(int kind, double* __restrict__ state) {
@@ -292,20 +248,9 @@ __global__ void k_icp_step(int kind, double* __restrict__ state) {
             state[kStStatus] = (double)kStatusDegenerate;
             return;
         }
-        // Open3D's TransformVector6dToMatrix4d: Rz(x2) Ry(x1) Rx(x0), shift (x3, x4, x5)
-        const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-        d[0] = cg * cb; d[1] = cg * sb * sa - sg * ca; d[2] = cg * sb * ca + sg * sa;
-        d[3] = sg * cb; d[4] = sg * sb * sa + cg * ca; d[5] = sg * sb * ca - cg * sa;
-        d[6] = -sb;     d[7] = cb * sa;                d[8] = cb * ca;
-        d[9] = x[3]; d[10] = x[4]; d[11] = x[5];
+        prg::twist_to_pose(x, d);  // Open3D's TransformVector6dToMatrix4d
     }
-    double old[12];
-    for (int k = 0; k < 12; ++k) old[k] = state[kStPose + k];
-    for (int a = 0; a < 3; ++a) {
-        for (int b = 0; b < 3; ++b)
-            state[kStPose + 3 * a + b] = (d[3 * a] * old[b] + d[3 * a + 1] * old[3 + b]) + d[3 * a + 2] * old[6 + b];
-        state[kStPose + 9 + a] = ((d[3 * a] * old[9] + d[3 * a + 1] * old[10]) + d[3 * a + 2] * old[11]) + d[9 + a];
-    }
+    prg::compose_pose(d, state + kStPose);
     state[kStIter] += 1.0;
 }
 

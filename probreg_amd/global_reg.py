@@ -21,6 +21,11 @@ Stages, each of which can be driven and read on its own (``RansacPlan``):
   * ``score``: inlier count and ordered sum of squared residuals per hypothesis; the winner has the largest count, then the
     smallest sum, then the smallest index;
   * ``refine``: Kabsch over the inliers of the current pose, repeated.
+
+``registration_fgr`` (``FgrPlan``, ``prg_fgr_*``, csrc/fgr.hip) is the second estimator, for
+correspondences that are mostly wrong: fast global registration (Zhou, Park, Koltun, ECCV 2016) samples no poses; it runs
+Gauss-Newton over all pairs at once under a Geman-McClure line process whose scale is annealed, after a tuple test that
+removes most wrong matches.  It is deterministic and needs no hypothesis budget.
 """
 import collections
 import ctypes
@@ -35,6 +40,12 @@ from .transformation import RigidTransformation
 MAX_DIM = 64
 
 GlobalResult = collections.namedtuple("GlobalResult", ["transformation", "fitness", "inlier_rmse", "inliers"])
+FgrResult = collections.namedtuple("FgrResult", ["transformation", "fitness", "inlier_rmse", "inliers", "used", "weights", "mu",
+                                                 "n_iter", "n_tuples", "n_trials", "status"])
+FgrState = collections.namedtuple("FgrState", ["pose", "mu", "n_iter", "status", "objective"])
+FGR_STATUS = ("ok", "too_few", "degenerate")
+FGR_MAX_CORRESPONDENCES = 2 ** 31 // 100   # the trial counter 100 C and the draw stay in range
+FGR_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
 
 
 def _as_rows(a, name, cols=None):
@@ -197,18 +208,195 @@ def registration_ransac(source, target, correspondences, max_distance, n_hypothe
     return GlobalResult(tf, cnt / float(corr.shape[0]), float(np.sqrt(sm / cnt)) if cnt else 0.0, np.nonzero(inl)[0])
 
 
-def registration_global(source, target, feature_fn=None, max_distance=0.05, mutual=True, voxel_size=None, **ransac_kwargs):
-    """Descriptors of both clouds (default ``fpfh.FPFH()``), their matches, then ``registration_ransac``.  ``source`` and
-    ``target`` are (n, 3) arrays or anything with ``.points``.
+class FgrPlan(_lib.Handle):
+    """One ``prg_fgr`` handle: two clouds and their correspondences on one device / stream and the stages of fast global
+    registration.  Poses are 12 doubles (rotation row-major, then the shift) and, but for
+    ``state(caller_units=True)``, move the normalised clouds."""
+
+    def __init__(self, device=None):
+        super().__init__(_lib.lib.prg_fgr_create, _lib.lib.prg_fgr_destroy, device)
+        self.n_corr = 0
+        self.n_used = 0
+        self.chunk = 0
+
+    def set_clouds(self, source, target):
+        src, tgt = _as_rows(source, "source", 3), _as_rows(target, "target", 3)
+        _lib.check(_lib.lib.prg_fgr_set_clouds(self._h, _lib.ptr(src), src.shape[0], _lib.ptr(tgt), tgt.shape[0]))
+        self.n_corr = self.n_used = 0
+
+    def set_correspondences(self, corr):
+        """(C, 2) integer pairs (source index, target index); ``normalise`` checks them against the clouds."""
+        corr = np.ascontiguousarray(corr, dtype=np.int32)
+        if corr.ndim != 2 or corr.shape[1] != 2:
+            raise ValueError("correspondences must have shape (C, 2), got %s" % (corr.shape,))
+        _lib.check(_lib.lib.prg_fgr_set_correspondences(self._h, _lib.ptr(corr), corr.shape[0]))
+        self.n_corr = corr.shape[0]
+        self.n_used = 0
+
+    def normalise(self, use_absolute_scale=False):
+        """(mean_p (3,), mean_q (3,), scale): the means of all source and all target points and the largest distance of a
+        point from the mean of its cloud."""
+        mp, mq, sc = np.empty(3), np.empty(3), ctypes.c_double(0.0)
+        _lib.check(_lib.lib.prg_fgr_normalise(self._h, int(bool(use_absolute_scale)), _lib.ptr(mp), _lib.ptr(mq),
+                                              ctypes.byref(sc)))
+        return mp, mq, float(sc.value)
+
+    def set_chunk(self, trials):
+        """Trials per launch of ``tuples`` (0: the default); changes no result."""
+        _lib.check(_lib.lib.prg_fgr_set_chunk(self._h, int(trials)))
+        self.chunk = int(trials)
+
+    def tuples(self, seed=0, tuple_scale=0.95, maximum_tuple_count=1000):
+        """(used (3 n_tuples,) int32, n_tuples, n_trials); the used pairs are installed."""
+        nt, ntr = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.lib.prg_fgr_tuples(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, float(tuple_scale), int(maximum_tuple_count),
+                                           ctypes.byref(nt), ctypes.byref(ntr)))
+        self.n_used = 3 * int(nt.value)
+        return self.used(), int(nt.value), int(ntr.value)
+
+    def set_used(self, idx):
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError("the used indices must have shape (K,), got %s" % (idx.shape,))
+        _lib.check(_lib.lib.prg_fgr_set_used(self._h, _lib.ptr(idx), idx.shape[0]))
+        self.n_used = idx.shape[0]
+
+    def used(self):
+        idx = np.empty(self.n_used, dtype=np.int32)
+        if self.n_used:
+            _lib.check(_lib.lib.prg_fgr_get_used(self._h, _lib.ptr(idx)))
+        return idx
+
+    def set_state(self, pose=FGR_IDENTITY, mu=1.0):
+        pose = np.array(pose, dtype=np.float64).reshape(12)
+        _lib.check(_lib.lib.prg_fgr_set_state(self._h, _lib.ptr(pose), float(mu)))
+
+    def sums(self, pose=None, mu=None):
+        """The 28 raw sums (A's upper triangle row-major, g, the objective) at ``pose`` and ``mu`` (default: the state's)."""
+        if pose is not None or mu is not None:
+            if pose is None or mu is None:
+                raise ValueError("give both pose and mu, or neither")
+            self.set_state(pose, mu)
+        out = np.empty(28)
+        _lib.check(_lib.lib.prg_fgr_sums(self._h, _lib.ptr(out)))
+        return out
+
+    def step(self, decrease_mu=False, division_factor=1.4, maximum_correspondence_distance=0.025):
+        """One step from the last ``sums``; the pose after it."""
+        _lib.check(_lib.lib.prg_fgr_step(self._h, int(bool(decrease_mu)), float(division_factor),
+                                         float(maximum_correspondence_distance)))
+        return self.state().pose
+
+    def iterate(self, n, decrease_mu=True, division_factor=1.4, maximum_correspondence_distance=0.025):
+        """``n`` times "sums, step" from the state; the final ``FgrState``."""
+        _lib.check(_lib.lib.prg_fgr_iterate(self._h, int(n), int(bool(decrease_mu)), float(division_factor),
+                                            float(maximum_correspondence_distance)))
+        return self.state()
+
+    def state(self, caller_units=False):
+        pose = np.empty(12)
+        mu, it, st, obj = ctypes.c_double(0.0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_double(0.0)
+        _lib.check(_lib.lib.prg_fgr_get_state(self._h, int(bool(caller_units)), _lib.ptr(pose), ctypes.byref(mu), ctypes.byref(it),
+                                              ctypes.byref(st), ctypes.byref(obj)))
+        return FgrState(pose, float(mu.value), int(it.value), FGR_STATUS[st.value], float(obj.value))
+
+    def weights(self):
+        """The line-process value of every used pair at the state's pose and mu."""
+        w = np.empty(self.n_used)
+        if self.n_used:
+            _lib.check(_lib.lib.prg_fgr_get_weights(self._h, _lib.ptr(w)))
+        return w
+
+
+def _check_correspondences(corr, src, tgt):
+    corr = np.asarray(corr)
+    if corr.ndim != 2 or corr.shape[1] != 2 or not np.issubdtype(corr.dtype, np.integer):
+        raise ValueError("correspondences must be an integer array of shape (C, 2), got %s %s" % (corr.dtype, corr.shape))
+    if corr.shape[0] < 3:
+        raise ValueError("need at least 3 correspondences, got %d" % corr.shape[0])
+    if corr.min() < 0 or corr[:, 0].max() >= src.shape[0] or corr[:, 1].max() >= tgt.shape[0]:
+        raise ValueError("correspondences index outside the clouds")
+    return corr
+
+
+def registration_fgr(source, target, correspondences, maximum_correspondence_distance=0.025, iteration_number=64,
+                     division_factor=1.4, decrease_mu=True, use_absolute_scale=False, tuple_test=True, tuple_scale=0.95,
+                     maximum_tuple_count=1000, seed=0, max_distance=None, device=None):
+    """Fast global registration (Open3D's ``registration_fgr_based_on_correspondence``) of ``correspondences`` (C, 2) of
+    (source index, target index): ``FgrResult(transformation, fitness, inlier_rmse, inliers, used, weights, mu, n_iter,
+    n_tuples, n_trials, status)``.
+
+    ``transformation`` is rigid (no scale) in the caller's units.  ``fitness``, ``inlier_rmse`` and ``inliers`` are taken over
+    all correspondences within ``max_distance`` at the final pose, as in ``GlobalResult``; ``max_distance=None`` means
+    ``maximum_correspondence_distance`` in the caller's units (times the clouds' scale unless ``use_absolute_scale``).
+    ``used`` are the indices into ``correspondences`` the optimisation ran on: three per accepted tuple in acceptance order
+    with repeats kept, or ``arange(C)`` without the tuple test; ``weights`` their final line-process values, ``mu`` the final
+    scale of the line process.  ``status`` is "ok", "too_few" (fewer than three used pairs: the normalised pose stays the
+    identity, so the result only moves the source's mean onto the target's) or "degenerate" (a failed pivot: the pose of
+    the last good step)."""
+    src, tgt = _as_rows(source, "source", 3), _as_rows(target, "target", 3)
+    corr = _check_correspondences(correspondences, src, tgt)
+    if corr.shape[0] > FGR_MAX_CORRESPONDENCES:
+        raise ValueError("at most %d correspondences, got %d" % (FGR_MAX_CORRESPONDENCES, corr.shape[0]))
+    mcd = _check_tau(maximum_correspondence_distance)
+    if int(iteration_number) != iteration_number or iteration_number < 0:
+        raise ValueError("iteration_number must be an integer >= 0, got %r" % (iteration_number,))
+    if not (np.isfinite(division_factor) and division_factor > 1.0):
+        raise ValueError("division_factor must be finite and > 1, got %r" % (division_factor,))
+    if not 0.0 < tuple_scale <= 1.0:
+        raise ValueError("tuple_scale must lie in (0, 1], got %r" % (tuple_scale,))
+    if int(maximum_tuple_count) != maximum_tuple_count or maximum_tuple_count < 1:
+        raise ValueError("maximum_tuple_count must be an integer >= 1, got %r" % (maximum_tuple_count,))
+    if max_distance is not None:
+        max_distance = _check_tau(max_distance)
+    _single_process("registration_fgr")
+    plan = FgrPlan(device)
+    try:
+        plan.set_clouds(src, tgt)
+        plan.set_correspondences(corr)
+        _, _, scale = plan.normalise(use_absolute_scale)
+        if not scale > 0.0:
+            raise ValueError("both clouds are a single point: there is nothing to register")
+        if tuple_test:
+            used, n_tuples, n_trials = plan.tuples(seed, tuple_scale, maximum_tuple_count)
+        else:
+            used, n_tuples, n_trials = np.arange(corr.shape[0], dtype=np.int32), 0, 0
+            plan.set_used(used)
+        plan.set_state(FGR_IDENTITY, scale if use_absolute_scale else 1.0)
+        st = plan.iterate(int(iteration_number), decrease_mu, division_factor, mcd)
+        weights = plan.weights()
+        pose = plan.state(caller_units=True).pose
+    finally:
+        plan.close()
+    status = "too_few" if used.shape[0] < 3 else st.status
+    tau = max_distance if max_distance is not None else mcd * (1.0 if use_absolute_scale else scale)
+    ev = RansacPlan(device)
+    try:
+        ev.set_correspondences(src[corr[:, 0]], tgt[corr[:, 1]])
+        pose, cnt, sm, inl = ev.refine(pose, tau, 0)
+    finally:
+        ev.close()
+    tf = RigidTransformation(pose[:9].reshape(3, 3).copy(), pose[9:].copy(), 1.0)
+    return FgrResult(tf, cnt / float(corr.shape[0]), float(np.sqrt(sm / cnt)) if cnt else 0.0, np.nonzero(inl)[0], used, weights,
+                     st.mu, st.n_iter, n_tuples, n_trials, status)
+
+
+def registration_global(source, target, feature_fn=None, max_distance=0.05, mutual=True, voxel_size=None, method="ransac",
+                        **kwargs):
+    """Descriptors of both clouds (default ``fpfh.FPFH()``), their matches, then ``registration_ransac``
+    (``method="ransac"``, the default) or ``registration_fgr`` (``method="fgr"``), which gets ``kwargs``; the result is a
+    ``GlobalResult`` either way.  ``source`` and ``target`` are (n, 3) arrays or anything with ``.points``.
 
     ``voxel_size``: when given, both clouds go through ``preprocess.voxel_down_sample(cloud, voxel_size)`` first, and
     descriptors, matching and the pose search run on the down-sampled clouds (FPFH stops being discriminative on dense
     clouds).  ``fitness`` and ``inliers`` of the result then refer to the down-sampled clouds and their correspondences, not
     to the rows of ``source`` and ``target``; the pose holds for the full clouds all the same."""
+    if method not in ("ransac", "fgr"):
+        raise ValueError("method must be 'ransac' or 'fgr', got %r" % (method,))
     src, tgt = _as_rows(source, "source", 3), _as_rows(target, "target", 3)
     _check_tau(max_distance)
     _single_process("registration_global")
-    device = ransac_kwargs.get("device")
+    device = kwargs.get("device")
     if voxel_size is not None:
         from . import preprocess
         voxel_size = preprocess._check_voxel_size(voxel_size)
@@ -220,4 +408,6 @@ def registration_global(source, target, feature_fn=None, max_distance=0.05, mutu
     pairs, _ = feature_matching(feature_fn(src), feature_fn(tgt), mutual, device=device)
     if pairs.shape[0] < 3:
         raise ValueError("fewer than 3 correspondences are left after matching (%d)" % pairs.shape[0])
-    return registration_ransac(src, tgt, pairs, max_distance, **ransac_kwargs)
+    if method == "fgr":
+        return GlobalResult(*registration_fgr(src, tgt, pairs, max_distance=max_distance, **kwargs)[:4])
+    return registration_ransac(src, tgt, pairs, max_distance, **kwargs)
