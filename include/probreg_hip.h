@@ -340,10 +340,13 @@ int prg_gauss_transform_direct_f64(int device, void* hip_stream, const double* s
                                const double* target_hd, int64_t t, int dim, const double* weights_hd,
                                int n_weight_rows, double h, double* out_hd);
 
-/* sum_{m,n} |x_m - y_n|^2 / (M*D*N), closed form in fp64 on the device.
+/* sum_{m,n} |x_m - y_n|^2 / (M*D*N), closed form in fp64 on the device: (n sum|x|^2 + m sum|y|^2 - 2 sum x . sum y) / (M*D*N)
+ * over fp64 clouds of any dim in [1, 64].  The three terms cancel: the result is good to about 1e-16 x (their size / the result),
+ * so the caller passes clouds it has moved near the origin by one common point (the quantity is a sum of differences and does
+ * not change); probreg_amd.math_utils.squared_kernel_sum subtracts the mean of all points in fp64.
  * Replaces: mu.squared_kernel_sum, math_utils.py:28-29. */
-int prg_squared_kernel_sum(int device, void* hip_stream, const float* x_hd, int64_t m,
-                           const float* y_hd, int64_t n, int dim, double* out_host);
+int prg_squared_kernel_sum(int device, void* hip_stream, const double* x_hd, int64_t m,
+                           const double* y_hd, int64_t n, int dim, double* out_host);
 /* Dense K = exp(-|x_i-y_j|^2/(2*beta)) float32 (rows = x). Replaces mu.rbf_kernel, math_utils.py:36-37. */
 int prg_rbf_kernel(int device, void* hip_stream, const float* x_hd, int64_t m, const float* y_hd,
                    int64_t n, int dim, double beta, float* out_hd);

@@ -2,6 +2,7 @@
 //   prg_squared_kernel_sum     (probreg/math_utils.py:28-29 -> cc/math_utils.cc:5-15)
 //   prg_rbf_kernel             (probreg/math_utils.py:36-37 -> cc/math_utils.cc:17-19)
 //   prg_gauss_transform_direct (probreg/gauss_transform.py:10-25, 46-60)
+#include <float.h>
 #include <math.h>
 
 #include <algorithm>
@@ -24,8 +25,8 @@ void set_error(const char* fmt, ...) {
 namespace {
 constexpr int kBlock = 256;
 
-// partial sums (sum x, sum y, sum z, sum |p|^2) in fp64 over a row-major n x dim float cloud
-__global__ __launch_bounds__(kBlock) void k_sums_rowmajor(const float* __restrict__ p, int64_t n, int dim,
+// partial sums (sum x, sum y, sum z, sum |p|^2) in fp64 over a row-major n x dim fp64 cloud
+__global__ __launch_bounds__(kBlock) void k_sums_rowmajor(const double* __restrict__ p, int64_t n, int dim,
                                                           double* __restrict__ part) {
     __shared__ double sh[4][4];
     double a[4] = {0, 0, 0, 0};
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void k_sums_rowmajor(const float* __restric
 }
 
 // any dimension (feature clouds, d <= 64): out[0..dim) += column sums, out[dim] += sum of squared norms (fp64 atomics)
-__global__ __launch_bounds__(kBlock) void k_sums_generic(const float* __restrict__ p, int64_t n, int dim,
+__global__ __launch_bounds__(kBlock) void k_sums_generic(const double* __restrict__ p, int64_t n, int dim,
                                                          double* __restrict__ out) {
     double sq = 0.0;
     for (int k = 0; k < dim; ++k) {
@@ -283,7 +284,7 @@ int prg_device_count(int* count) {
     return PRG_OK;
 }
 
-int prg_squared_kernel_sum(int device, void* hip_stream, const float* x_hd, int64_t m, const float* y_hd, int64_t n,
+int prg_squared_kernel_sum(int device, void* hip_stream, const double* x_hd, int64_t m, const double* y_hd, int64_t n,
                            int dim, double* out_host) {
     PRG_REQUIRE(x_hd && y_hd && out_host, PRG_ERR_INVALID, "prg_squared_kernel_sum: NULL argument");
     PRG_REQUIRE(m > 0 && n > 0 && dim >= 1 && dim <= 64, PRG_ERR_INVALID,
@@ -291,13 +292,12 @@ int prg_squared_kernel_sum(int device, void* hip_stream, const float* x_hd, int6
     PRG_ENTER(device);
     hipStream_t st = (hipStream_t)hip_stream;
     if (dim != 2 && dim != 3) {  // feature clouds (FilterReg with a feature_fn, filterreg.py:126-128)
-        DevBuf<float> fx, fy;
-        DevBuf<double> fs;
+        DevBuf<double> fx, fy, fs;
         PRG_HIP(fx.reset(m * dim));
         PRG_HIP(fy.reset(n * dim));
         PRG_HIP(fs.reset(2 * (dim + 1) + 1));
-        PRG_HIP(hipMemcpyAsync(fx.p, x_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, st));
-        PRG_HIP(hipMemcpyAsync(fy.p, y_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault, st));
+        PRG_HIP(hipMemcpyAsync(fx.p, x_hd, (size_t)m * dim * sizeof(double), hipMemcpyDefault, st));
+        PRG_HIP(hipMemcpyAsync(fy.p, y_hd, (size_t)n * dim * sizeof(double), hipMemcpyDefault, st));
         PRG_HIP(hipMemsetAsync(fs.p, 0, (size_t)(2 * (dim + 1) + 1) * sizeof(double), st));
         double* sx = fs.p;
         double* sy = sx + dim + 1;
@@ -311,13 +311,12 @@ int prg_squared_kernel_sum(int device, void* hip_stream, const float* x_hd, int6
     }
     const int nbx = (int)(prg::ceil_div(m, kBlock) < 256 ? prg::ceil_div(m, kBlock) : 256);
     const int nby = (int)(prg::ceil_div(n, kBlock) < 256 ? prg::ceil_div(n, kBlock) : 256);
-    DevBuf<float> bx, by;
-    DevBuf<double> bp;
+    DevBuf<double> bx, by, bp;
     PRG_HIP(bx.reset(m * dim));
     PRG_HIP(by.reset(n * dim));
     PRG_HIP(bp.reset((int64_t)(nbx + nby) * 4 + 1));
-    PRG_HIP(hipMemcpyAsync(bx.p, x_hd, (size_t)m * dim * sizeof(float), hipMemcpyDefault, st));
-    PRG_HIP(hipMemcpyAsync(by.p, y_hd, (size_t)n * dim * sizeof(float), hipMemcpyDefault, st));
+    PRG_HIP(hipMemcpyAsync(bx.p, x_hd, (size_t)m * dim * sizeof(double), hipMemcpyDefault, st));
+    PRG_HIP(hipMemcpyAsync(by.p, y_hd, (size_t)n * dim * sizeof(double), hipMemcpyDefault, st));
     double* px = bp.p;
     double* py = px + (size_t)nbx * 4;
     double* res = py + (size_t)nby * 4;
@@ -425,7 +424,9 @@ int prg_gauss_transform_direct(int device, void* hip_stream, const double* sourc
     PRG_HIP(hipMemcpyAsync(bs.p, source_hd, (size_t)s * dim * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(bt.p, target_hd, (size_t)t * dim * sizeof(double), hipMemcpyDefault, st));
     PRG_HIP(hipMemcpyAsync(bw.p, weights_hd, (size_t)s * rows * sizeof(double), hipMemcpyDefault, st));
-    const float kk = (float)(-1.4426950408889634 / (h * h));
+    // kept finite: below h ~ 6.5e-20 the quotient is -inf in float32, and -inf x 0 on a target that coincides with a source
+    // point is NaN where the sum has the term w_j; -FLT_MAX x 0 = -0 gives it, and every other pair still underflows to 0
+    const float kk = fmaxf((float)(-1.4426950408889634 / (h * h)), -FLT_MAX);
     k_pack_gauss<<<(unsigned)prg::ceil_div(cap, kBlock), kBlock, 0, st>>>(bs.p, bw.p, s, dim, rows, cap, b3.p, bwr.p);
     const unsigned grid = (unsigned)prg::ceil_div(t, kBlock);
     for (int c = 0; c < rows;) {  // four weight rows per sweep (compute_l2_dist: 1 + D rows = one sweep), then 2, then 1

@@ -11,14 +11,23 @@ from .engine import _current_device_and_stream
 def squared_kernel_sum(x, y):
     """sum_{m,n} |x_m - y_n|^2 / (M*D*N)  (reference math_utils.py:28-29 -> cc/math_utils.cc:5-15).
 
-    Evaluated on the GPU in closed form in fp64 - the M x N float32 matrix of the reference is
-    never built; the two agree to float32 rounding of the reference's sum (~1e-7 relative).
+    Evaluated on the GPU in closed form in fp64, ``n sum|x|^2 + m sum|y|^2 - 2 sum x . sum y`` - the M x N float32 matrix of the
+    reference is never built.  The three terms cancel, so the mean of all points is subtracted from both clouds in fp64 first
+    (the quantity is a sum of squared differences: a common shift does not change it) and the kernels read fp64 coordinates:
+    clouds of any dimension, at any distance from the origin, give the pairwise sum of the arrays as passed to ~1e-12
+    relative.  (The reference rounds the coordinates to float32 and sums in float32: ~1e-7 relative near the origin.)
     """
     _lib.require_gpu()
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    y = np.ascontiguousarray(y, dtype=np.float32)
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
     if x.ndim != 2 or y.ndim != 2 or x.shape[1] != y.shape[1]:
         raise ValueError("x and y must be 2-D with the same number of columns.")
+    if x.shape[0] and y.shape[0]:
+        c = (x.sum(axis=0) + y.sum(axis=0)) / (x.shape[0] + y.shape[0])
+        x = x - c
+        y = y - c
+    x = np.ascontiguousarray(x)
+    y = np.ascontiguousarray(y)
     dev, st = _current_device_and_stream()
     out = ctypes.c_double(0.0)
     check(lib.prg_squared_kernel_sum(dev, ctypes.c_void_p(st), ptr(x), x.shape[0], ptr(y), y.shape[0], x.shape[1],

@@ -309,7 +309,8 @@ def test_error_behaviour():
 
 
 def test_gauss_transform_direct():
-    """reference gauss_transform.py:10-16 and tests/test_gauss_transform.py:17-28 (1e-4)."""
+    """reference gauss_transform.py:10-16 and tests/test_gauss_transform.py:17-28 (1e-4).
+    (Per-entry derived bounds at the launch edges: tests/test_helpers_gpu.py.)"""
     from probreg_amd import gauss_transform as gt
 
     rng = np.random.default_rng(9)

@@ -5,7 +5,8 @@ tests/golden/make_golden.py gauss from probreg/gauss_transform.py and probreg/co
 
 Tolerance: 1e-5 of the largest |output| of the case (the GPU forms the differences in fp64 and evaluates the squared
 distance and the exponential in fp32: a term's relative error is ~ (d / h)^2 x 1.2e-7, sums are fp64; v_exp_f32 flushes
-terms below 2^-126 of the largest, which 1e-5 of the largest |output| does not see)."""
+terms below 2^-126 of the largest, which 1e-5 of the largest |output| does not see).  A bound per entry, derived from that
+count, at the sizes where the launches change: tests/test_helpers_gpu.py."""
 import os
 
 import numpy as np
